@@ -14,6 +14,12 @@ A "step" = one full MPC step on device-resident inputs: fused rollout kernel + a
 (+ all-reduce(min) + select when sharded).  Inputs are resident in HBM before the timed region;
 a pool of independent synthetic candidate batches is cycled so no step re-reads the previous
 step's batch.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, untimed steps, the --steps timed steps and the result line.
+`--full` adds everything else the line can carry: the per-launch kernel timing pass, two steps in flight, the batched /
+worst-path / dt = 0.05 / closed-loop extras, the sharded closed loop, the timing of the native collective modes that are
+not the headline, and the CPU baseline (each still subject to its --no-* switch).  `--dump-outputs DIR` writes the
+result record of the last timed step to DIR/*.npy (float64), for output-for-output comparison of two builds.
 """
 import argparse
 import hashlib
@@ -74,6 +80,11 @@ def build_parser():
                     help="single GPU rehearsal of the sharded step: nccl world of 1 with the all-reduce kept")
     ap.add_argument("--streams", type=int, default=1,
                     help="independent MPC steps in flight on one GPU (one engine handle + HIP stream each); 1 = strictly sequential steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements the headline does not need (kernel timing pass, two steps in flight, "
+                         "batched / worst-path / dt=0.05 / closed-loop extras, sharded closed loop, other native modes, CPU baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the result record of the last timed step (and its fields) to DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-pipelined-extra", action="store_true")
@@ -304,6 +315,17 @@ def metric_name(args, world):
     if (args.N, args.K) == (20, 4096):
         return "MPC rollouts/sec (horizon-steps/sec) at N=20, K=4096; 1/2/4/8 GPU"      # BASELINE.json's metric, verbatim
     return f"MPC rollouts/sec (horizon-steps/sec) at N={args.N}, K={args.K}; {world} GPU"
+
+
+def dump_outputs(out_dir, rec, N):
+    """The last timed step's result record as a caller of the step receives it, [J*, k*, u(3), (theta, gamma)_0..N]
+    (include/rovmpc.h), whole and split into its fields; float64, a few hundred bytes."""
+    rec = np.asarray(rec, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    fields = {"record": rec, "best_cost": rec[0:1], "best_index": rec[1:2], "u": rec[2:5],
+              "traj": rec[5:5 + 2 * (N + 1)].reshape(N + 1, 2)}
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 # ---- a rank -------------------------------------------------------------------------------------------------------------
@@ -548,6 +570,8 @@ def main():
         steady["headline"] = steady_state(smpc)
         for comms, (e_n, s_n) in native.items():
             if s_n is not smpc:
+                if not args.full:             # the other checked mode is timed only in a --full run
+                    continue
                 for i in range(presteps + args.warmup):
                     one_step(i, s_n)
                 steady[comms] = steady_state(s_n)
@@ -557,7 +581,7 @@ def main():
     # second, untimed pass: per-launch event pairs around the rollout kernel alone (each pair
     # costs ~3 us of its own, so this pass is not the one `value` comes from)
     kev_ms = kev_min_ms = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         n_ev = min(args.steps, 200)
         eng.timing_enable(n_ev)
         for i in range(n_ev * S):
@@ -569,7 +593,7 @@ def main():
     # BASELINE config 5 in its sharded form: the closed loop of Rov_traj_gen case 12 with the model's own (theta, gamma) fed
     # back, every step the candidate-sharded one (rollout + all-reduce(min) + select); every rank runs it, rank 0 reports
     closed_loop_sharded = None
-    if smpc is not None and args.closed_loop != 0:
+    if smpc is not None and args.closed_loop != 0 and args.full:
         import hashlib as _hl
         from rovmpc.closed_loop import run_closed_loop_sharded
         native_loop = (collective or "").startswith("ncclAllReduce")
@@ -674,7 +698,9 @@ def main():
             if (args.N, args.K, args.dtype, world) == (50, 16384, "f32", 1) and args.model == "default" and args.debug_flags == 0:
                 bench_extras.attach_pmc(out["roofline"], os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_pmc_summary_C3.json"), sha,
                                         kavg_ms * 1e-3, FP64_VECTOR_PEAK_TFLOPS, dtype="f32")
-        if world == 1 and smpc is None and S == 1 and not args.no_pipelined_extra:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, args.N)
+        if world == 1 and smpc is None and S == 1 and args.full and not args.no_pipelined_extra:
             # extra, not the headline: two independent MPC steps in flight on one GPU (second engine handle
             # on a high-priority stream = its own hardware queue), so one step's launch ramp / arg-min tail
             # overlaps the other's work
@@ -703,11 +729,11 @@ def main():
             eng2.close(); enga.close()
             del st2, pair                     # (every live stream competes for the runtime's few hardware queues)
         default_size = (args.N, args.K, args.dtype, args.model) == (20, 4096, "f64", "default") and args.debug_flags == 0
-        if world == 1 and smpc is None and S == 1 and default_size and not args.no_extras:
+        if world == 1 and smpc is None and S == 1 and default_size and args.full and not args.no_extras:
             bench_extras.run_extras(out, args, cfg, model, dev,
                                     pmc_ctx={"dir": os.path.join(ROOT, "profiles"), "tag": PROFILE_TAG, "sha": sha,
                                              "hbm_peak": HBM_PEAK_GBS, "fp64_peak": FP64_VECTOR_PEAK_TFLOPS})
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.N)
         print(json.dumps(out))
     if dist is not None:

@@ -1272,7 +1272,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(rv):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--devices", "0,0",
-                        "--steps", "30", "--warmup", "5", "--K", "1024", "--no-kernel-timing"],
+                        "--steps", "30", "--warmup", "5", "--K", "1024", "--no-kernel-timing", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -1301,7 +1301,9 @@ def test_bench_checks_the_native_collective_path_and_records_a_fallback(rv):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    # (GPU_MAX_HW_QUEUES left unset: the queue count asserted below is the one bench.py chooses for its ranks)
+    base = {k: v for k, v in os.environ.items()
+            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "GPU_MAX_HW_QUEUES")}
     out = {}
     for hook in ("1", "fail", "abort"):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-collective", "--steps", "20", "--warmup", "5",
@@ -1318,6 +1320,40 @@ def test_bench_checks_the_native_collective_path_and_records_a_fallback(rv):
     assert aborted["config"]["collective"].startswith("torch.distributed") and "aborted" in aborted["config"]["collective_fallback_reason"]
     assert aborted["best"] == ok["best"]
     assert ok["config"]["hw_queues"] == "8"
+
+
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_last_record(rv, tmp_path):
+    """A plain single-GPU bench run sets up, warms up, times --steps steps and prints the line, nothing of --full;
+    --dump-outputs writes the record of the last timed step, which must be the step of the same inputs on one handle."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--K", "1024", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["ms_per_step"] > 0 and d["unit"] == "horizon-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["value"] > 0
+    for key in ("cpu_baseline", "two_steps_in_flight", "batched", "worst_path", "dt_0p05", "closed_loop"):
+        assert key not in d
+    assert d["roofline"]["kernel_event_pair_us"] is None          # the per-launch timing pass is --full only
+    # the last timed step used pool (steps - 1) % 8 of seed 20250523 + p
+    state, _ = rv.synthetic_problem(1, 20)
+    _, U = rv.synthetic_problem(1024, 20, seed=20250523 + (20 - 1) % 8)
+    with rv.Engine(rv.MPCConfig(N=20, K=1024)) as e:
+        want = e.step(state, U)
+    rec = np.load(dump / "record.npy")
+    assert rec.dtype == np.float64 and rec.shape == (5 + 2 * 21,)
+    assert np.load(dump / "best_cost.npy")[0] == want.cost == d["best"]["cost"]
+    assert int(np.load(dump / "best_index.npy")[0]) == want.index == d["best"]["index"]
+    assert np.array_equal(np.load(dump / "u.npy"), want.u)
+    np.testing.assert_allclose(np.load(dump / "traj.npy"), want.traj, rtol=1e-12, atol=0)
 
 
 def test_handoff_timeouts_are_errors_not_wrong_records(rv):

@@ -353,3 +353,21 @@ def test_bench_quotes_a_pmc_profile_only_for_the_kernel_it_was_taken_on(tmp_path
     # the committed round profile belongs to SOME build of these sources: it must at least be stamped
     meta = json.load(open(os.path.join(ROOT, "profiles", f"{bench.PROFILE_TAG}_pmc_summary.json")))["_meta"]
     assert len(meta["kernel_sources_sha16"]) == 16 and meta["commit"]
+
+
+def test_bench_options_and_output_dump(tmp_path):
+    """--full is off by default (a plain run times the headline alone); --dump-outputs writes the result record
+    [J*, k*, u(3), (theta, gamma)_0..N] whole and field by field, float64."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.build_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    N = 3
+    rec = np.arange(5 + 2 * (N + 1), dtype=np.float64) + 0.5
+    bench.dump_outputs(str(tmp_path / "o"), rec, N)
+    got = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in ("record", "best_cost", "best_index", "u", "traj")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["record"], rec) and got["best_cost"][0] == 0.5 and got["best_index"][0] == 1.5
+    assert np.array_equal(got["u"], rec[2:5]) and np.array_equal(got["traj"], rec[5:].reshape(N + 1, 2))

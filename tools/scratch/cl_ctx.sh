@@ -1,5 +1,5 @@
 for q in 4 8; do
-  GPU_MAX_HW_QUEUES=$q python bench.py --no-cpu-baseline --steps 300 --warmup 30 --no-kernel-timing 2>/dev/null | python -c "
+  GPU_MAX_HW_QUEUES=$q python bench.py --full --no-cpu-baseline --steps 300 --warmup 30 --no-kernel-timing 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 m = d['closed_loop']['modes']
