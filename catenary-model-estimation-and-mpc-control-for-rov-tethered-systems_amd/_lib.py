@@ -47,6 +47,29 @@ class State(C.Structure):
                 ("theta", C.c_double), ("gamma", C.c_double), ("theta_prev", C.c_double), ("gamma_prev", C.c_double)]
 
 
+class MPPIParams(C.Structure):
+    """Mirror of ``rovmpc_mppi_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("n_iter", C.c_int32), ("lambda_", C.c_double), ("std", C.c_double * 3)]
+
+    @classmethod
+    def make(cls, n_iter: int = 1, lam: float = 1.0, std=(0.0, 0.0, 0.0)) -> "MPPIParams":
+        import math
+        if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 1 <= int(n_iter) <= 64:
+            raise ValueError(f"n_iter must be an integer in 1..64 (got {n_iter!r})")
+        lam = float(lam)
+        if not (math.isfinite(lam) and lam > 0):
+            raise ValueError(f"lambda must be finite and > 0 (got {lam!r})")
+        sd = [float(v) for v in std]
+        if len(sd) != 3 or not all(math.isfinite(v) and v >= 0 for v in sd):
+            raise ValueError(f"std must be 3 finite values >= 0 (got {std!r})")
+        p = cls()
+        p.struct_size = C.sizeof(cls)
+        p.n_iter = int(n_iter)
+        p.lambda_ = lam
+        p.std = (C.c_double * 3)(*sd)
+        return p
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -60,6 +83,10 @@ _SIGNATURES = {
     "rovmpc_model_structure": (C.c_int32, [_P]),
     "rovmpc_step": (C.c_int, [_P, C.POINTER(State), _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "rovmpc_rollout_costs": (C.c_int, [_P, C.POINTER(State), _P, _P, _P]),
+    "rovmpc_mppi_reset": (C.c_int, [_P, _P]),
+    "rovmpc_mppi_step": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P, _P, _P]),
+    "rovmpc_mppi_last": (C.c_int, [_P, _P, _P]),
+    "rovmpc_mppi_update_device": (C.c_int, [_P, _P, _P, C.c_double, _P, _P, _P, _P]),
     "rovmpc_mpc_step_sampled": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, _P, _P, C.c_int32, _P]),
     "rovmpc_sampled_candidates": (C.c_int, [_P, _P]),
     "rovmpc_sample_candidates_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),

@@ -85,6 +85,18 @@ struct rovmpc_handle {
     // what the last sampled step drew with (rovmpc_sampled_candidates re-draws the tensor for inspection)
     unsigned long long last_seed = 0, last_step = 0; double last_mean[3] = {}, last_std[3] = {}; int last_warm = 0; bool last_fused = false;
     double *arg_result_host = nullptr; unsigned long long *arg_done_flag = nullptr; unsigned long long arg_done_seq = 0;
+    void *arg_J = nullptr;                       // costs of the launch being enqueued go here instead of d_J (null: d_J)
+    // MPPI (rovmpc_mppi_*), allocated at the first rovmpc_mppi_reset: candidate tensor, costs, state and record of its own
+    // (the other entry points' buffers are never touched), the nominal double-buffered by iteration, the update's slab and
+    // ticket, and the mapped host block [record, nu*, stats] + sequence word the host spins on
+    void *d_mppi_U = nullptr, *d_mppi_J = nullptr;
+    double *d_mppi_state = nullptr, *d_mppi_record = nullptr, *d_mppi_nu = nullptr;
+    int mppi_cur = 0;                            // half of d_mppi_nu holding the handle's nominal
+    double *d_mppi_slab = nullptr; unsigned *d_mppi_ticket = nullptr;
+    double *d_mppi_slab_x = nullptr; unsigned *d_mppi_ticket_x = nullptr;   // rovmpc_mppi_update_device's own
+    double *h_mppi_out = nullptr, *d_mppi_out = nullptr;
+    unsigned long long *h_mppi_done = nullptr, *d_mppi_done = nullptr;
+    unsigned long long mppi_seq = 0, mppi_steps = 0;
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -410,12 +422,16 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     void *ptrs[] = {h->d_U, h->d_J, h->d_traj_all, h->d_state, h->d_blk_traj,
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
-                    h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u};
+                    h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
+                    h->d_mppi_U, h->d_mppi_J, h->d_mppi_state, h->d_mppi_record, h->d_mppi_nu, h->d_mppi_slab, h->d_mppi_ticket,
+                    h->d_mppi_slab_x, h->d_mppi_ticket_x};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     if (h->h_record) (void)hipHostFree(h->h_record);
     if (h->h_done) (void)hipHostFree(h->h_done);
     if (h->h_err) (void)hipHostFree(h->h_err);
+    if (h->h_mppi_out) (void)hipHostFree(h->h_mppi_out);
+    if (h->h_mppi_done) (void)hipHostFree(h->h_mppi_done);
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete h->epoch_ctr;
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -845,7 +861,7 @@ template <typename T> static void fill_args(const rovmpc_handle *h, RolloutArgs<
     a.U = (const T *)d_U; a.state = d_state; a.k = (const RolloutConsts<T> *)h->d_k;
     a.code_th = h->d_code_th; a.code_ga = h->d_code_ga;
     a.consts = (const T *)h->d_consts; a.Rtab = (const T *)h->d_Rtab;
-    a.J = (T *)h->d_J; a.traj_all = (T *)d_traj_all;
+    a.J = (T *)(h->arg_J ? h->arg_J : h->d_J); a.traj_all = (T *)d_traj_all;
     a.blk_traj = h->d_blk_traj;
     a.N = c.N; a.K = c.K; a.CK = g.CK; a.M = c.n_shape_pts; a.n_th = h->n_th; a.n_ga = h->n_ga;
     a.prev_mode = c.prev_mode; a.integrator = c.integrator; a.debug = c.debug_flags; a.fmap = c.feature_map;
@@ -1245,6 +1261,176 @@ extern "C" int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state,
     if (traj_all) HIPCHK(h, hipMemcpyAsync(traj_all, h->d_traj_all, tbytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ROVMPC_OK;
+}
+
+// ---- MPPI: sampling around a warm-started nominal, exp(-J/lambda)-weighted update on the GPU -------------------------
+struct MppiGeo { int G; long long slice; };
+static MppiGeo mppi_geometry(long long K) {
+    long long G = (K + MPPI_ROWS_PER_WG - 1) / MPPI_ROWS_PER_WG;
+    if (G > MPPI_MAX_WG) G = MPPI_MAX_WG;
+    const long long slice = (K + G - 1) / G;
+    return {(int)((K + slice - 1) / slice), slice};
+}
+
+static int mppi_check_params(rovmpc_handle *h, const rovmpc_mppi_params *p) {
+    if (!p) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step: null params");
+    if (p->struct_size != (int32_t)sizeof(rovmpc_mppi_params))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_params.struct_size %d != %d (ABI mismatch)", p->struct_size, (int)sizeof(rovmpc_mppi_params));
+    if (p->n_iter < 1 || p->n_iter > 64) FAIL(h, ROVMPC_ERR_INVALID, "n_iter must be in 1..64 (got %d)", p->n_iter);
+    if (!(isfinite(p->lambda) && p->lambda > 0)) FAIL(h, ROVMPC_ERR_INVALID, "lambda must be finite and > 0 (got %g)", p->lambda);
+    for (int i = 0; i < 3; ++i)
+        if (!(isfinite(p->std[i]) && p->std[i] >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "std[%d] must be finite and >= 0 (got %g)", i, p->std[i]);
+    return ROVMPC_OK;
+}
+
+// slab [G][3 + 3N] and its ticket word (zeroed once: the last workgroup of every launch re-arms it)
+static int mppi_alloc_slab(rovmpc_handle *h, double **slab, unsigned **ticket) {
+    const MppiGeo g = mppi_geometry(h->cfg.K);
+    HIPCHK(h, hipMalloc((void **)slab, (size_t)g.G * (3 + 3 * (size_t)h->cfg.N) * sizeof(double)));
+    HIPCHK(h, hipMalloc((void **)ticket, 16));
+    HIPCHK(h, hipMemset(*ticket, 0, 16));
+    return ROVMPC_OK;
+}
+
+static int launch_mppi_update(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda, const double *nu_in, double *nu_out,
+                              int shift, double *stats, double *slab, unsigned *ticket, double *record, double *host_out,
+                              unsigned long long *done_flag, unsigned long long done_seq, hipStream_t s) {
+    const MppiGeo g = mppi_geometry(h->cfg.K);
+    MppiUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.lambda = lambda;
+    a.nu_in = nu_in; a.nu_out = nu_out; a.shift = shift; a.stats = stats; a.slab = slab; a.ticket = ticket;
+    a.record = record; a.R = rovmpc_result_len(h); a.host_out = host_out; a.done_flag = done_flag; a.done_seq = done_seq;
+    const bool wide = a.C3 > MPPI_NT;
+    if (h->cfg.dtype == ROVMPC_F64) {
+        if (wide) hipLaunchKernelGGL((mppi_update_kernel<double, 4>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
+        else hipLaunchKernelGGL((mppi_update_kernel<double, 1>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
+    } else {
+        if (wide) hipLaunchKernelGGL((mppi_update_kernel<float, 4>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
+        else hipLaunchKernelGGL((mppi_update_kernel<float, 1>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "MPPI update launch failed: %s", hipGetErrorString(e));
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_mppi_reset(rovmpc_handle *h, const double *nominal) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!nominal) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_reset: null nominal");
+    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "MPPI is single-GPU: not available once rovmpc_comm_init has run");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const rovmpc_config &c = h->cfg;
+    const size_t C3 = 3 * (size_t)c.N;
+    if (!h->d_mppi_nu) {
+        const size_t R = (size_t)rovmpc_result_len(h);
+        HIPCHK(h, hipMalloc(&h->d_mppi_U, (size_t)c.K * C3 * h->esz));
+        HIPCHK(h, hipMalloc(&h->d_mppi_J, (size_t)c.K * h->esz));
+        HIPCHK(h, hipMalloc((void **)&h->d_mppi_state, ROVMPC_STATE_LEN * sizeof(double)));
+        HIPCHK(h, hipMalloc((void **)&h->d_mppi_record, R * sizeof(double)));
+        int rc = mppi_alloc_slab(h, &h->d_mppi_slab, &h->d_mppi_ticket);
+        if (rc) return rc;
+        HIPCHK(h, hipHostMalloc((void **)&h->h_mppi_out, (R + C3 + 4) * sizeof(double), hipHostMallocMapped));
+        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_mppi_out, h->h_mppi_out, 0));
+        HIPCHK(h, hipHostMalloc((void **)&h->h_mppi_done, 64, hipHostMallocMapped));
+        *h->h_mppi_done = 0;
+        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_mppi_done, h->h_mppi_done, 0));
+        HIPCHK(h, hipMalloc((void **)&h->d_mppi_nu, 2 * C3 * sizeof(double)));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_mppi_nu, nominal, C3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->mppi_cur = 0;
+    return ROVMPC_OK;
+}
+
+template <typename T>
+static int launch_mppi_sample(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t counter, const double *std3,
+                              const double *nu) {
+    MppiSampleArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    if (state) { sa.state = *state; sa.d_state = h->d_mppi_state; }
+    sa.seed = seed; sa.counter = counter;
+    for (int i = 0; i < 3; ++i) sa.std[i] = std3[i];
+    sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.nu = nu;
+    const int bs = 256;
+    const int grid = (int)(((sa.total + 3) / 4 + bs - 1) / bs);
+    hipLaunchKernelGGL(mppi_sample_kernel<T>, dim3(grid), dim3(bs), 0, h->stream, sa, (T *)h->d_mppi_U);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "MPPI sampler launch failed: %s", hipGetErrorString(e));
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step,
+                                const rovmpc_mppi_params *p, double *record_out, double *nominal_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step: null pointer");
+    int rc = mppi_check_params(h, p);
+    if (rc) return rc;
+    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "MPPI is single-GPU: not available once rovmpc_comm_init has run");
+    if (!h->d_mppi_nu) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step before rovmpc_mppi_reset");
+    if ((rc = check_ready(h))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    const unsigned long long seq = ++h->mppi_seq;
+    int cur = h->mppi_cur;
+    for (int i = 0; i < p->n_iter; ++i) {
+        const bool last = i + 1 == p->n_iter;
+        const uint64_t counter = step * (uint64_t)p->n_iter + (uint64_t)i;        // wraps
+        const double *nu_in = h->d_mppi_nu + cur * C3;
+        double *nu_out = h->d_mppi_nu + (cur ^ 1) * C3;
+        rc = h->cfg.dtype == ROVMPC_F64 ? launch_mppi_sample<double>(h, i == 0 ? state : nullptr, seed, counter, p->std, nu_in)
+                                        : launch_mppi_sample<float>(h, i == 0 ? state : nullptr, seed, counter, p->std, nu_in);
+        if (rc) return rc;
+        // the rollout of rovmpc_step on this tensor, costs into MPPI's own buffer
+        h->arg_J = h->d_mppi_J;
+        rc = enqueue_step(h, h->d_mppi_state, h->d_mppi_U, nullptr, h->d_mppi_record, 0, nullptr, 0, 1, h->stream);
+        h->arg_J = nullptr;
+        if (rc) return rc;
+        rc = launch_mppi_update(h, h->d_mppi_J, h->d_mppi_U, p->lambda, nu_in, nu_out, last ? 1 : 0, nullptr, h->d_mppi_slab,
+                                h->d_mppi_ticket, last ? h->d_mppi_record : nullptr, last ? h->d_mppi_out : nullptr,
+                                last ? h->d_mppi_done : nullptr, seq, h->stream);
+        if (rc) return rc;
+        cur ^= 1;
+    }
+    h->mppi_cur = cur;
+    ++h->mppi_steps;
+    // the last update releases `seq` behind the record in mapped host memory: spin on it, as rovmpc_mpc_step_sampled does
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; ++spins) {
+        if (__atomic_load_n(h->h_mppi_done, __ATOMIC_ACQUIRE) == seq) break;
+        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (__atomic_load_n(h->h_mppi_done, __ATOMIC_ACQUIRE) != seq) FAIL(h, ROVMPC_ERR_HIP, "the MPPI step finished without publishing its record");
+            break;
+        }
+    }
+    memcpy(record_out, h->h_mppi_out, R * sizeof(double));
+    if (nominal_out) memcpy(nominal_out, h->h_mppi_out + R, C3 * sizeof(double));
+    if (stats_out) memcpy(stats_out, h->h_mppi_out + R + C3, 4 * sizeof(double));
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_mppi_last(rovmpc_handle *h, void *U_out, void *J_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (h->mppi_steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_last: no MPPI step yet");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (U_out) HIPCHK(h, hipMemcpy(U_out, h->d_mppi_U, (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
+    if (J_out) HIPCHK(h, hipMemcpy(J_out, h->d_mppi_J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost));
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda,
+                                         const double *d_nominal_in, double *d_nominal_out, double *d_stats, void *stream) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!d_J || !d_U || !d_nominal_in || !d_nominal_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_update_device: null pointer");
+    if (!(isfinite(lambda) && lambda > 0)) FAIL(h, ROVMPC_ERR_INVALID, "lambda must be finite and > 0 (got %g)", lambda);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->d_mppi_slab_x) {
+        int rc = mppi_alloc_slab(h, &h->d_mppi_slab_x, &h->d_mppi_ticket_x);
+        if (rc) return rc;
+    }
+    return launch_mppi_update(h, d_J, d_U, lambda, d_nominal_in, d_nominal_out, 0, d_stats, h->d_mppi_slab_x, h->d_mppi_ticket_x,
+                              nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // ---- timing ---------------------------------------------------------------------------------

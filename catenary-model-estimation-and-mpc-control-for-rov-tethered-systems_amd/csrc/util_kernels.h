@@ -52,6 +52,263 @@ sample_candidates_kernel(const SampleArgs a, T *__restrict__ U) {
 }
 
 
+// ---- MPPI (rovmpc_mppi_*): sampling around a per-node nominal and the exp(-J/lambda)-weighted update --------------------
+// Sampling: U[0] = (T) nu, U[k][n][c] = (T) fma(std[c], z_e, nu[n][c]) for k >= 1, z_e the sampler's stream above with
+// `counter` in place of the step (e = (k N + n) 3 + c).  The state crosses as a kernel argument, as for the sampler.
+struct MppiSampleArgs {
+    rovmpc_state state;                 // written to d_state by block 0 (null d_state: not written)
+    double *d_state;
+    unsigned long long seed, counter;
+    double std[3];
+    long long total;                    // K * N * 3
+    int N;
+    const double *nu;                   // nominal [N][3]
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+mppi_sample_kernel(const MppiSampleArgs a, T *__restrict__ U) {
+    if (a.d_state && blockIdx.x == 0 && threadIdx.x < ROVMPC_STATE_LEN)
+        a.d_state[threadIdx.x] = reinterpret_cast<const double *>(&a.state)[threadIdx.x];
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, e0 = 4 * j;
+    if (e0 >= a.total) return;
+    double z[4];
+    philox_normal4(a.seed, a.counter, j, z);
+    const int row3 = 3 * a.N;
+    int col = (int)(e0 % row3);                         // = 3 n + c
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long long e = e0 + i;
+        if (e >= a.total) break;
+        const double m = a.nu[col];
+        U[e] = e < row3 ? (T)m : (T)::fma(a.std[col % 3], z[i], m);
+        if (++col == row3) col = 0;
+    }
+}
+
+// Update: one read of J[K] and U[K][3N].  Workgroup b takes candidates [b slice, (b + 1) slice) and writes to its slab row
+// (rho_b, eta_b, sum w^2_b, S_b[3N]) with rho_b its finite minimum and w = exp(-(J - rho_b) / lambda); the last workgroup to
+// take a ticket rescales the rows by exp(-(rho_b - rho) / lambda) and sums them in workgroup order.  Every sum has a fixed
+// order (no float atomics), so the result is bitwise reproducible.  Hand-off: wave 0 stores the slab row write-through at
+// agent scope and drains its stores before it takes the ticket; the last workgroup reads every slab row with agent-scope
+// loads (which bypass the CU's L1), so no cache write-back or invalidate is needed on either side.
+constexpr int MPPI_NT = 256;                // threads of the update kernel
+constexpr int MPPI_MAX_COLS = 1024;         // 3 N (N < 341)
+constexpr int MPPI_ROWS_PER_WG = 64;        // candidates per workgroup, until the grid reaches MPPI_MAX_WG
+constexpr int MPPI_MAX_WG = MPPI_NT;        // the combine reads one slab row per thread
+
+struct MppiUpdateArgs {
+    const void *J, *U;                  // T [K], T [K][3N]
+    long long K, slice;                 // candidates, candidates per workgroup
+    int C3, G;                          // 3 N, workgroups
+    double lambda;
+    const double *nu_in;                // [3N]
+    double *nu_out;                     // [3N]: nu_{i+1}, or with shift != 0 the kept nominal nu[n] = nu*[min(n + 1, N - 1)]
+    int shift;
+    double *stats;                      // [4] (rho, eta, ESS, J_0) or null
+    double *slab;                       // [G][3 + 3N]
+    unsigned *ticket;                   // 0 between launches (the last workgroup re-arms it)
+    // last iteration of a control step (null record: none): u of the device record <- nu*[0]; then host_out (mapped) =
+    // [record (R), nu* (3N), stats (4)] and done_seq released into *done_flag at system scope
+    double *record;
+    int R;
+    double *host_out;
+    unsigned long long *done_flag, done_seq;
+};
+
+RV_DEV double wave_min(double v) {
+    for (int off = 32; off > 0; off >>= 1) v = ::fmin(v, __shfl_xor(v, off, 64));
+    return v;
+}
+RV_DEV double wave_sum(double v) {          // butterfly: every lane ends with the same bits
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+constexpr int MPPI_CHUNK = 8;             // rows (slab rows in the combine) whose loads are issued together
+
+// QC = columns per thread: 1 when 3 N <= MPPI_NT, else 4
+template <typename T, int QC>
+__global__ void __launch_bounds__(MPPI_NT)
+mppi_update_kernel(const MppiUpdateArgs a) {
+    __shared__ double sS[MPPI_MAX_COLS];                // row-lane partials [R][3N]
+    __shared__ double sNu[MPPI_MAX_COLS];               // nu* (combine)
+    __shared__ double sScale[MPPI_MAX_WG], sW[MPPI_NT], sEta[4], sW2[4];
+    __shared__ double sRed[16];
+    __shared__ int sLast;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const T *__restrict__ J = static_cast<const T *>(a.J);
+    const T *__restrict__ U = static_cast<const T *>(a.U);
+    const int C3 = a.C3, G = a.G;
+    // threads map to columns so that each candidate row is one coalesced read; R rows side by side when 3N <= 256,
+    // otherwise one row with up to four columns per thread
+    const int R = C3 <= MPPI_NT ? MPPI_NT / C3 : 1;
+    const int r = C3 <= MPPI_NT ? tid / C3 : 0, c0 = C3 <= MPPI_NT ? tid - r * C3 : tid;
+    const bool active = r < R;
+    const long long k0 = (long long)blockIdx.x * a.slice, k1 = k0 + a.slice < a.K ? k0 + a.slice : a.K;
+    const double inf = __builtin_inf();
+
+    // (1) the workgroup's finite minimum
+    double m = inf;
+    for (long long k = k0 + tid; k < k1; k += MPPI_NT) {
+        const double v = (double)J[k];
+        if (::isfinite(v) && v < m) m = v;
+    }
+    m = wave_min(m);
+    if (lane == 0) sRed[wv] = m;
+    __syncthreads();
+    const double rho_b = ::fmin(::fmin(sRed[0], sRed[1]), ::fmin(sRed[2], sRed[3]));
+
+    // (2) weights, a tile of MPPI_NT rows at a time: one lane per row computes w into LDS, then row-lane r takes rows
+    //     r, r + R, ... of the tile in order, the loads of MPPI_CHUNK rows issued before any of them is used
+    double S[4] = {0.0, 0.0, 0.0, 0.0}, eta = 0.0, w2 = 0.0;
+    for (long long kt = k0; kt < k1; kt += MPPI_NT) {
+        double w = 0.0;
+        if (kt + tid < k1) {
+            const double v = (double)J[kt + tid];
+            if (::isfinite(v)) w = ::exp(-(v - rho_b) / a.lambda);
+        }
+        eta += w;
+        w2 = ::fma(w, w, w2);
+        sW[tid] = w;
+        __syncthreads();
+        const int nrow = k1 - kt < MPPI_NT ? (int)(k1 - kt) : MPPI_NT;
+        if (active) {
+            for (int jb = r; jb < nrow; jb += MPPI_CHUNK * R) {
+                double uv[MPPI_CHUNK][QC];
+#pragma unroll
+                for (int t = 0; t < MPPI_CHUNK; ++t) {
+                    const int j = jb + t * R;
+#pragma unroll
+                    for (int q = 0; q < QC; ++q) {
+                        const int c = c0 + q * MPPI_NT;
+                        uv[t][q] = (j < nrow && c < C3) ? (double)U[(kt + j) * C3 + c] : 0.0;
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < MPPI_CHUNK; ++t) {
+                    const int j = jb + t * R;
+                    const double wj = j < nrow ? sW[j] : 0.0;
+                    if (wj == 0.0) continue;              // not finite (or underflowed): contributes nothing
+#pragma unroll
+                    for (int q = 0; q < QC; ++q) S[q] = ::fma(wj, uv[t][q], S[q]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    eta = wave_sum(eta);
+    w2 = wave_sum(w2);
+    if (lane == 0) { sEta[wv] = eta; sW2[wv] = w2; }
+    if (C3 <= MPPI_NT) {
+        if (active) sS[r * C3 + c0] = S[0];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (c0 + q * MPPI_NT < C3) sS[c0 + q * MPPI_NT] = S[q];
+    }
+    __syncthreads();
+
+    // (3) wave 0 sums the row-lanes in order, stores the slab row write-through and takes the ticket
+    if (wv == 0) {
+        double *slab = a.slab + (size_t)blockIdx.x * (3 + C3);
+        for (int c = lane; c < C3; c += 64) {
+            double s = sS[c];
+            for (int q = 1; q < R; ++q) s += sS[q * C3 + c];
+            st_agent(slab + 3 + c, s);
+        }
+        if (lane == 0) {
+            st_agent(slab, rho_b);
+            st_agent(slab + 1, ((sEta[0] + sEta[1]) + sEta[2]) + sEta[3]);
+            st_agent(slab + 2, ((sW2[0] + sW2[1]) + sW2[2]) + sW2[3]);
+        }
+        // write-through stores acknowledged before the ticket that announces them (no L2 write-back fence needed)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) sLast = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(G - 1);
+    }
+    __syncthreads();
+    if (!sLast) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (no instruction: keeps the slab loads below the ticket)
+
+    // (4) combine (last workgroup)
+    if (tid == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double rb = inf, eb = 0.0, wb = 0.0;
+    if (tid < G) {
+        const double *s = a.slab + (size_t)tid * (3 + C3);
+        rb = ld_agent(s); eb = ld_agent(s + 1); wb = ld_agent(s + 2);
+    }
+    m = wave_min(rb);
+    if (lane == 0) sRed[4 + wv] = m;
+    __syncthreads();
+    const double rho = ::fmin(::fmin(sRed[4], sRed[5]), ::fmin(sRed[6], sRed[7]));
+    const double J0 = (double)J[0];
+    double st0, st1, st2;
+    if (!(rho < inf)) {
+        // no finite cost: the nominal stays as it is, bit for bit
+        for (int c = tid; c < C3; c += MPPI_NT) sNu[c] = a.nu_in[c];
+        st0 = __builtin_nan(""); st1 = 0.0; st2 = 0.0;
+    } else {
+        const double sc = (tid < G && rb < inf) ? ::exp(-(rb - rho) / a.lambda) : 0.0;
+        sScale[tid] = sc;
+        const double e = wave_sum(sc * eb), w = wave_sum(sc * sc * wb);
+        if (lane == 0) { sRed[8 + wv] = e; sRed[12 + wv] = w; }
+        __syncthreads();
+        const double eta_all = ((sRed[8] + sRed[9]) + sRed[10]) + sRed[11];
+        const double w2_all = ((sRed[12] + sRed[13]) + sRed[14]) + sRed[15];
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        if (active) {
+            for (int bb = r; bb < G; bb += MPPI_CHUNK * R) {
+                double sv[MPPI_CHUNK][QC];
+#pragma unroll
+                for (int t = 0; t < MPPI_CHUNK; ++t) {
+                    const int b = bb + t * R;
+                    const double *row = a.slab + (size_t)b * (3 + C3) + 3;
+#pragma unroll
+                    for (int q = 0; q < QC; ++q) {
+                        const int c = c0 + q * MPPI_NT;
+                        sv[t][q] = (b < G && c < C3) ? ld_agent(row + c) : 0.0;
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < MPPI_CHUNK; ++t) {
+                    const int b = bb + t * R;
+                    const double s = b < G ? sScale[b] : 0.0;
+                    if (s == 0.0) continue;
+#pragma unroll
+                    for (int q = 0; q < QC; ++q) acc[q] = ::fma(s, sv[t][q], acc[q]);
+                }
+            }
+        }
+        if (C3 <= MPPI_NT) {
+            if (active) sS[r * C3 + c0] = acc[0];
+            __syncthreads();
+            if (tid < C3) {
+                double s = sS[tid];
+                for (int q = 1; q < R; ++q) s += sS[q * C3 + tid];
+                sNu[tid] = s / eta_all;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (c0 + q * MPPI_NT < C3) sNu[c0 + q * MPPI_NT] = acc[q] / eta_all;
+        }
+        st0 = rho; st1 = eta_all; st2 = eta_all * eta_all / w2_all;
+    }
+    __syncthreads();
+    for (int c = tid; c < C3; c += MPPI_NT) a.nu_out[c] = sNu[a.shift && c + 3 < C3 ? c + 3 : c];
+    if (a.stats && tid == 0) { a.stats[0] = st0; a.stats[1] = st1; a.stats[2] = st2; a.stats[3] = J0; }
+    if (a.record && wv == 0) {
+        // the control to apply is nu*[0]; the rest of the record is the rollout's
+        if (lane < 3) a.record[2 + lane] = sNu[lane];
+        double *o = a.host_out;
+        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? sNu[i - 2] : a.record[i];
+        for (int c = lane; c < C3; c += 64) o[a.R + c] = sNu[c];
+        if (lane == 0) { o[a.R + C3] = st0; o[a.R + C3 + 1] = st1; o[a.R + C3 + 2] = st2; o[a.R + C3 + 3] = J0; }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        if (lane == 0) __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // model.predict(X) on n already-scaled rows: one lane per row, operand stack in LDS.
 __global__ void __launch_bounds__(256)
 predict_kernel(const double *__restrict__ Xs, long long n, int F, const int32_t *code, int ncode,

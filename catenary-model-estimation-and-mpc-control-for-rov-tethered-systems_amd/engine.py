@@ -9,7 +9,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import Config, State, RovmpcError, check, load_library
+from ._lib import Config, State, MPPIParams, RovmpcError, check, load_library
 from .model import DynamicsModel, default_model
 
 
@@ -235,6 +235,37 @@ class Engine:
         if rc:
             self._check(rc)
         return sp["rec"]
+
+    # -- MPPI (rovmpc_mppi_*) -----------------------------------------------------------------
+    def mppi_reset(self, nominal):
+        """Set the handle's MPPI nominal plan (N, 3); allocates the MPPI buffers on first use."""
+        nu = np.ascontiguousarray(nominal, dtype=np.float64)
+        if nu.shape != (self.cfg.N, 3):
+            raise ValueError(f"nominal must have shape ({self.cfg.N}, 3), got {nu.shape}")
+        self._check(self.lib.rovmpc_mppi_reset(self._h, _ptr(nu)))
+
+    def mppi_step(self, state, seed: int, step: int, params: MPPIParams):
+        """One MPPI control step: returns (record [J*, k*, u(3), traj], nu* (N, 3), stats (rho, eta, ESS, J_0))."""
+        if not isinstance(params, MPPIParams):
+            raise TypeError("params must be an MPPIParams (MPPIParams.make(...))")
+        s = _c_state(state_array(state))
+        rec = np.empty(self.result_len); nu = np.empty((self.cfg.N, 3)); stats = np.empty(4)
+        self._check(self.lib.rovmpc_mppi_step(self._h, C.byref(s), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                              C.byref(params), _ptr(rec), _ptr(nu), _ptr(stats)))
+        return rec, nu, stats
+
+    def mppi_last(self):
+        """Host copies of the last MPPI iteration's candidates U (K, N, 3) and costs J (K,)."""
+        U = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)
+        J = np.empty(self.cfg.K, dtype=self.cfg.np_dtype)
+        self._check(self.lib.rovmpc_mppi_last(self._h, _ptr(U), _ptr(J)))
+        return U, J
+
+    def mppi_update_device(self, d_J: int, d_U: int, lam: float, d_nominal_in: int, d_nominal_out: int, d_stats: int = 0,
+                           stream: int = 0):
+        """The weighted update alone on device buffers (raw pointers), asynchronous on `stream`."""
+        self._check(self.lib.rovmpc_mppi_update_device(self._h, d_J, d_U, float(lam), d_nominal_in, d_nominal_out,
+                                                       d_stats or None, stream))
 
     def sampled_candidates(self) -> np.ndarray:
         """Host copy of the candidate tensor of the last ``mpc_step_sampled`` (tests / inspection)."""

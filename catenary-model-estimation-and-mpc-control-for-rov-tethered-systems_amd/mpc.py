@@ -10,6 +10,7 @@ from typing import Optional
 
 import numpy as np
 
+from . import _lib
 from .engine import Engine, MPCConfig, MPCState, StepResult, state_array
 from .model import DynamicsModel, default_model
 
@@ -89,6 +90,56 @@ class MPC:
 
     def rollout_costs(self, state, U, return_traj: bool = False):
         return self.engine.rollout_costs(state, U, return_traj)
+
+    def close(self):
+        self.engine.close()
+
+
+class MPPI:
+    """``mppi = MPPI(N=20, K=4096, lam=1.0); u = mppi.step(state)``: model-predictive path integral control.
+
+    The handle keeps a nominal plan (N, 3); each step samples K candidates around it on the GPU (candidate 0 = the nominal),
+    rolls them out, moves the nominal to the exp(-J/lam)-weighted mean of all candidates (``n_iter`` times, without a
+    host round trip) and returns its first control.  The law is stated in include/rovmpc.h (rovmpc_mppi_step).
+    Defaults: nominal = the scaler mean of x3..x5 on every node, std = its scale.  After ``step``: ``last`` (the record of
+    the last rollout, with u = nominal*[0]), ``last_stats`` (rho, eta, ess, J0), ``nominal`` (the plan the step returned).
+    """
+
+    def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, lam: float = 1.0, std=None,
+                 n_iter: int = 1, seed: int = 20250523, nominal=None, **overrides):
+        m = default_model()
+        self.std = np.asarray(std if std is not None else m.scale[3:6], dtype=np.float64)
+        self.params = _lib.MPPIParams.make(n_iter, lam, self.std)        # ValueError before the library is called
+        self.lam, self.n_iter = float(lam), int(n_iter)
+        self.seed = int(seed)
+        self.engine = Engine(cfg, model, **overrides)
+        self.cfg = self.engine.cfg
+        self._default_mean = np.asarray(m.mean[3:6], dtype=np.float64)
+        self.step_count = 0
+        self.last: Optional[StepResult] = None
+        self.last_stats: Optional[dict] = None
+        self.nominal: Optional[np.ndarray] = None
+        self.reset(nominal)
+
+    def reset(self, nominal=None):
+        """Set the nominal plan ((N, 3), or (3,) repeated on every node; default: the scaler mean of x3..x5)."""
+        N = self.cfg.N
+        nu = self._default_mean if nominal is None else np.asarray(nominal, dtype=np.float64)
+        if nu.shape == (3,):
+            nu = np.tile(nu, (N, 1))
+        if nu.shape != (N, 3):
+            raise ValueError(f"nominal must have shape ({N}, 3) or (3,), got {nu.shape}")
+        self.engine.mppi_reset(nu)
+        self.nominal = nu.copy()
+
+    def step(self, state) -> np.ndarray:
+        rec, nu, stats = self.engine.mppi_step(state, self.seed, self.step_count, self.params)
+        self.step_count += 1
+        N = self.cfg.N
+        self.last = StepResult(rec[2:5].copy(), rec[5:].reshape(N + 1, 2).copy(), float(rec[0]), int(rec[1]))
+        self.last_stats = {"rho": float(stats[0]), "eta": float(stats[1]), "ess": float(stats[2]), "J0": float(stats[3])}
+        self.nominal = nu
+        return self.last.u
 
     def close(self):
         self.engine.close()

@@ -194,6 +194,52 @@ int rovmpc_sampled_candidates(rovmpc_handle *h, void *U_out);
 int rovmpc_sample_candidates_device(rovmpc_handle *h, uint64_t seed, uint64_t step, const double *mean3,
                                     const double *std3, void *d_U, void *stream);
 
+/* ---- MPPI: model-predictive path integral control around a warm-started nominal plan -----------------------------
+ * (Williams et al., ICRA 2016 / 2017.)  The handle holds a nominal nu[N][3], always in double, set by rovmpc_mppi_reset.
+ * Control step `step` with `seed`, state x; for i = 0 .. n_iter - 1:
+ *   1. counter c = step * n_iter + i (uint64, wraps); z = the sampler's standard normals of rovmpc_mpc_step_sampled keyed by
+ *      (seed, c), element order e = (k N + n) 3 + ch;
+ *   2. candidates U[0] = (T) nu_i (the nominal itself, no noise), U[k][n][ch] = (T) fma(std[ch], z_e, nu_i[n][ch]) for k >= 1;
+ *   3. the rollout of rovmpc_step on (x, U): same kernel, costs and record, for every model path, dtype, vt mode and feature map;
+ *   4. in double whatever T is, with F = {k : J_k finite} (NaN, +inf and -inf alike are not):
+ *      F empty: nu_{i+1} = nu_i bit for bit, stats = (NaN, 0, 0, J_0);
+ *      else rho = min_F J, w_k = exp(-(J_k - rho) / lambda) on F and 0 elsewhere, eta = sum w,
+ *      nu_{i+1}[n][ch] = sum_k w_k (double) U[k][n][ch] / eta, ESS = eta^2 / sum w^2.
+ * Results: nu* = nu_{n_iter}; record_out [rovmpc_result_len] keeps the layout [J*, k*, u[3], traj] with J*, k*, traj the last
+ * rollout's (its cheapest candidate) and u = nu*[0], the control to apply; stats_out = (rho, eta, ESS, J_0) of the last
+ * iteration, J_0 the nominal's own cost; nominal_out = nu*.  The handle then keeps nu[n] = nu*[min(n + 1, N - 1)].
+ * The host waits once per control step (the last update publishes record, nu* and stats into mapped memory), never between
+ * iterations.  Notes:
+ *  - with n_iter >= 2, nu* itself is never rolled out;
+ *  - there is no control-noise cross term: the path cost is the rollout's J, which already holds w_u |U - U_ref|^2;
+ *  - where costs diverge (the chosen rows reach about 1e30 at dt = 0.05) the weights collapse to the arg-min unless lambda is
+ *    scaled to them.
+ * MPPI has buffers of its own (candidate tensor, costs, record, nominal, slab), allocated at the first reset: steps of
+ * rovmpc_step / rovmpc_mpc_step_sampled on the same handle give the same bits with or without MPPI steps in between.
+ * Errors: ROVMPC_ERR_INVALID for bad parameters, a struct_size mismatch or a step before the first reset;
+ * ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
+ * Not provided: sharded MPPI (it needs an all-reduce of the 3 N + 3 partials), batched and closed-loop device entries,
+ * sampling folded into the fused sampled rollout kernel, control bounds. */
+typedef struct rovmpc_mppi_params {
+    int32_t struct_size;        /* = sizeof(rovmpc_mppi_params), ABI check                  */
+    int32_t n_iter;             /* iterations per control step, 1..64                       */
+    double lambda;              /* temperature, finite and > 0                              */
+    double std[3];              /* sampling standard deviation per channel, finite, >= 0    */
+} rovmpc_mppi_params;
+
+/* nominal[N][3] (host, double); allocates the MPPI buffers on first use. */
+int rovmpc_mppi_reset(rovmpc_handle *h, const double *nominal);
+/* One control step (blocking); nominal_out[N][3] and stats_out[4] may be NULL. */
+int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step,
+                     const rovmpc_mppi_params *p, double *record_out, double *nominal_out, double *stats_out);
+/* Host copies of the last iteration's candidates U[K][N][3] and costs J[K] (reals of cfg.dtype); either may be NULL. */
+int rovmpc_mppi_last(rovmpc_handle *h, void *U_out, void *J_out);
+/* Step 4 alone on caller device buffers, asynchronously on `stream`: d_J[K], d_U[K][N][3] (K = cfg.K, reals of cfg.dtype),
+ * d_nominal_in / d_nominal_out [N][3] double (no shift), d_stats[4] double or NULL.  For candidate pipelines of one's own.
+ * Calls on one handle must not overlap in time (they share one slab). */
+int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda,
+                              const double *d_nominal_in, double *d_nominal_out, double *d_stats, void *stream);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
