@@ -2235,11 +2235,14 @@ select_kernel(const long long *slots, int world, int R, double *result, unsigned
     for (int i = threadIdx.x; i < R; i += blockDim.x) result[i] = (bad && i == 0) ? __builtin_nan("") : ordered_val(slots[(size_t)rb * R + i]);
     // Sharded closed loop with the state handed over on the GPU: the rollout of step `step_next` is already launched and its
     // theta waves wait for this -- (theta, gamma) of its start = first predicted node of the GLOBAL winner, its delay slots =
-    // what this step started from (record: [J, k, u(3), th0, ga0, th1, ga1, ...]); then the sequence word.
+    // what this step started from (record: [J, k, u(3), th0, ga0, th1, ga1, ...]); then the sequence word.  After a hand-off
+    // that timed out the row is another step's: hand over NaN, so that every later record says so (theta NaN -> costs +inf)
+    // instead of continuing, finite and wrong, from a stale state.
     if (ring && threadIdx.x == 0) {
         double *r4 = ring + (int)(step_next & 3) * 4;
-        st_agent(&r4[0], ordered_val(slots[(size_t)rb * R + 7])); st_agent(&r4[1], ordered_val(slots[(size_t)rb * R + 8]));
-        st_agent(&r4[2], ordered_val(slots[(size_t)rb * R + 5])); st_agent(&r4[3], ordered_val(slots[(size_t)rb * R + 6]));
+        const double q = __builtin_nan("");
+        st_agent(&r4[0], bad ? q : ordered_val(slots[(size_t)rb * R + 7])); st_agent(&r4[1], bad ? q : ordered_val(slots[(size_t)rb * R + 8]));
+        st_agent(&r4[2], bad ? q : ordered_val(slots[(size_t)rb * R + 5])); st_agent(&r4[3], bad ? q : ordered_val(slots[(size_t)rb * R + 6]));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         st_agent(seq_theta, (unsigned long long)step_next);
     }

@@ -44,6 +44,7 @@ struct rovmpc_handle {
     unsigned long long *d_step_seq = nullptr;
     unsigned long long *d_cl_granules = nullptr;
     double *d_cl_blk_traj = nullptr;
+    int cl_form = 0;                 // form of the last closed-loop call (rovmpc_closed_loop_form)
     int n_feat = 0;
     double mean[ROVMPC_MAX_FEATURES], scale[ROVMPC_MAX_FEATURES];
     int n_th = 0, n_ga = 0, n_consts = 0;
@@ -837,6 +838,7 @@ extern "C" int rovmpc_set_model(rovmpc_handle *h, int32_t n_features, const doub
 
 extern "C" int32_t rovmpc_model_path(const rovmpc_handle *h) { return h ? h->model_kind : -1; }
 extern "C" int32_t rovmpc_model_structure(const rovmpc_handle *h) { return (h && h->model_kind == MODEL_JIT) ? (h->jit_gi | (h->jit_ts << 1)) : 0; }
+extern "C" int32_t rovmpc_closed_loop_form(const rovmpc_handle *h) { return h ? h->cl_form : -1; }
 
 extern "C" int rovmpc_set_rotation_table(rovmpc_handle *h, const double *R) {
     if (!h) return ROVMPC_ERR_INVALID;
@@ -2318,7 +2320,9 @@ static int closed_loop_workspace(rovmpc_handle *h, HandoffArgs &p, hipStream_t s
         HIPCHK(h, hipMemset(h->d_cl_granules, 0, 2 * GRAN * max_blocks * sizeof(unsigned long long)));
         HIPCHK(h, hipMalloc((void **)&h->d_cl_blk_traj, 2 * max_blocks * (size_t)(c.N + 1) * 2 * sizeof(double)));
     }
-    HIPCHK(h, hipMemsetAsync(h->d_step_seq, 0, 256, s));
+    HIPCHK(h, hipMemsetAsync(h->d_step_seq, 0, 128, s));
+    // the ring holds NaN until a step writes it: a wait that gives up before its state arrives reads NaN, not a state
+    HIPCHK(h, hipMemsetAsync(h->d_step_seq + 16, 0xff, 128, s));
     p.seq_theta = h->d_step_seq; p.seq_gamma = h->d_step_seq + 8;             // separate 64-byte lines
     p.ring = reinterpret_cast<double *>(h->d_step_seq + 16);                   // [4][4] doubles
     p.granules2 = h->d_cl_granules; p.blk_traj2 = h->d_cl_blk_traj;
@@ -2402,6 +2406,7 @@ static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_
     if (2 * g.nblocks > capacity)
         FAIL(h, ROVMPC_ERR_UNSUPPORTED, "pipelined closed loop needs two grids resident at once: 2 x %d workgroups exceed the device's capacity %d "
                                         "(use rovmpc_closed_loop_device)", g.nblocks, capacity);
+    h->cl_form = 2;
     hipLaunchKernelGGL(plant_update_kernel, dim3(1), dim3(64), 0, s, d_state, d_exo, (const double *)nullptr);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->pipe_ev[2], s));
@@ -2434,6 +2439,31 @@ static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_
     return ROVMPC_OK;
 }
 
+// Workgroups of the closed-loop step kernel (the instance launch_step / jit_fn_step would run, with its dynamic LDS) the
+// device holds at once: resident workgroups per CU x CUs; 0 if the model has no step kernel or the query fails.  Sets the
+// kernel's dynamic-LDS attribute on the way, as the launches need.
+template <typename T>
+static int step_kernel_capacity(rovmpc_handle *h, const Geo &g) {
+    const int vt = h->cfg.vt_mode;
+    int capacity = 0;
+    if (h->model_kind == MODEL_BUILTIN) {
+        RolloutArgs<T> a;
+        const HandoffArgs p{};
+        fill_args<T>(h, a, nullptr, nullptr, nullptr, g, 1);
+        --*h->epoch_ctr;                                         // (the probe takes no epoch)
+        hipError_t e = vt == 0 ? launch_step<T, 0>(h, a, p, nullptr, true, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, nullptr, true, &capacity)
+                                                                                              : launch_step<T, 2>(h, a, p, nullptr, true, &capacity);
+        if (e != hipSuccess) capacity = 0;
+    } else if (h->model_kind == MODEL_JIT && h->jit_fn_step) {
+        const size_t lds = rollout_lds_elems<T>(h->cfg.N, g.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
+        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        int per_cu = 0;
+        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_step, g.NT, lds) != hipSuccess) per_cu = 0;
+        capacity = per_cu * h->n_cu;
+    }
+    return capacity;
+}
+
 // ---- sharded closed loop with the state handed over on the GPU ----------------------------------------------------------
 // BASELINE config 5 as it is asked (every step the candidate-sharded one), model feedback: step g + 1's rollout is launched
 // right behind step g's on the caller's stream -- no join, no plant-update kernel, no event on that stream -- and waits ON THE
@@ -2441,7 +2471,8 @@ static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_
 // rank), theta from the select kernel that follows step g's all-reduce on the collective stream (the GLOBAL winner's first
 // node).  Its controls load, positions, gamma table and first velocity-transform half run meanwhile, so a step costs
 // rollout + max(0, all-reduce + select - prologue) instead of rollout + all-reduce + select + join + update
-// (world 1: 47.5 -> ~20 us).  Compiled-in and hiprtc models; records are the join-based loop's bit for bit.
+// (world 1: 47.5 -> ~20 us).  Compiled-in and hiprtc models whose step-kernel grid is resident in one round (the caller,
+// rovmpc_closed_loop_device, checks that); records are the join-based loop's bit for bit.
 template <typename T>
 static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const double *d_exo, int64_t T_steps, double *d_state, const void *d_pools,
                                          int32_t n_pools, int64_t k_offset, double *d_results, hipStream_t s) {
@@ -2481,7 +2512,7 @@ static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const double *d_exo, 
         a.result = h->d_result; a.k_offset = k_offset; a.slots = h->d_slots[sp]; a.rank = h->comm_rank; a.world = h->comm_world;
         p.step = i;
         hipError_t e;
-        int capacity = 0;
+        int capacity = 0;     // (not probed here: the caller's step_kernel_capacity has set the LDS attribute)
         if (h->model_kind == MODEL_JIT) {
             const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
             if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2490,11 +2521,6 @@ static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const double *d_exo, 
             void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &both, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
             e = hipModuleLaunchKernel(h->jit_fn_step, a.nblocks, 1, 1, a.NT, 1, 1, (unsigned)lds, s, nullptr, extra);
         } else {
-            if (i == 0) {      // (dynamic LDS attribute of the step kernel)
-                e = vt == 0 ? launch_step<T, 0>(h, a, p, s, true, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, s, true, &capacity)
-                                                                              : launch_step<T, 2>(h, a, p, s, true, &capacity);
-                if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
-            }
             e = vt == 0 ? launch_step<T, 0>(h, a, p, s, false, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, s, false, &capacity)
                                                                           : launch_step<T, 2>(h, a, p, s, false, &capacity);
         }
@@ -2518,6 +2544,7 @@ extern "C" int rovmpc_closed_loop_pipelined_device(rovmpc_handle *h, const doubl
                                                    const void *d_pools, int32_t n_pools, int32_t feedback, double *d_results,
                                                    void *stream) {
     if (!h) return ROVMPC_ERR_INVALID;
+    h->cl_form = 0;
     if (T < 1 || n_pools < 1 || !d_exo || !d_state || !d_pools || !d_results)
         FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_closed_loop_pipelined_device: bad argument");
     int rc = check_ready(h);
@@ -2534,6 +2561,7 @@ extern "C" int rovmpc_closed_loop_pipelined_device(rovmpc_handle *h, const doubl
 extern "C" int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, double *d_state, const void *d_pools,
                                          int32_t n_pools, int64_t k_offset, int32_t feedback, double *d_results, void *stream) {
     if (!h) return ROVMPC_ERR_INVALID;
+    h->cl_form = 0;
     if (T < 1 || n_pools < 1 || !d_exo || !d_state || !d_pools || !d_results)
         FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_closed_loop_device: bad argument");
     int rc = check_ready(h);
@@ -2547,6 +2575,7 @@ extern "C" int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, 
     if (!h->comm) {
         // one GPU: the plant update of step i + 1 rides on the epilogue of step i (sweeping workgroup), so the
         // loop is back-to-back rollout kernels; only step 0 needs the stand-alone update
+        h->cl_form = 1;
         hipLaunchKernelGGL(plant_update_kernel, dim3(1), dim3(64), 0, s, d_state, d_exo, (const double *)nullptr);
         HIPCHK(h, hipGetLastError());
         for (int64_t i = 0; i < T; ++i) {
@@ -2560,13 +2589,25 @@ extern "C" int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, 
         return ROVMPC_OK;
     }
     // model feedback over the sharded step: the GPU-side hand-off (closed_loop_sharded_handoff_t) unless the model runs on the
-    // interpreter (no step kernel) or ROVMPC_CL_JOIN asks for the join-based form below
+    // interpreter (no step kernel), ROVMPC_CL_JOIN asks for the join-based form below, or the step kernel's grid is not
+    // resident in one round: step g + 1's workgroups spin on their CU slots until step g's select has run, so a grid of
+    // several rounds would leave the all-reduce and select of step g nowhere to run (every step a hand-off time-out)
     if (feedback && T > 1 && !getenv("ROVMPC_CL_JOIN") &&
         (h->model_kind == MODEL_BUILTIN || (h->model_kind == MODEL_JIT && h->jit_fn_step))) {
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        return h->cfg.dtype == ROVMPC_F64 ? closed_loop_sharded_handoff_t<double>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s)
-                                          : closed_loop_sharded_handoff_t<float>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s);
+        const Geo g = launch_geometry(h, 1);
+        const int capacity = h->cfg.dtype == ROVMPC_F64 ? step_kernel_capacity<double>(h, g) : step_kernel_capacity<float>(h, g);
+        const bool one_round = capacity > 0 && g.nblocks <= capacity;
+        if (getenv("ROVMPC_CL_VERBOSE"))
+            fprintf(stderr, "[rovmpc] sharded closed loop: %d workgroups, %d resident at once -> %s\n", g.nblocks, capacity,
+                    one_round ? "GPU-side hand-off" : "join per step");
+        if (one_round) {
+            h->cl_form = 4;
+            return h->cfg.dtype == ROVMPC_F64 ? closed_loop_sharded_handoff_t<double>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s)
+                                              : closed_loop_sharded_handoff_t<float>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s);
+        }
     }
+    h->cl_form = 3;
     for (int64_t i = 0; i < T; ++i) {
         const double *prev = (feedback && i > 0) ? d_results + (size_t)(i - 1) * R : nullptr;
         if (prev) {

@@ -370,6 +370,12 @@ class Engine:
         self._check(self.lib.rovmpc_closed_loop_device(self._h, d_exo, T, d_state, d_pools, n_pools, k_offset,
                                                        int(feedback), d_results, stream))
 
+    @property
+    def closed_loop_form(self) -> str:
+        """Form the last ``closed_loop_device`` call took: "none" (none yet, or refused), "per_step" (single GPU, one launch
+        per step), "pipelined", "sharded_join" (a join per step) or "sharded_handoff" (state handed over on the GPU)."""
+        return ("none", "per_step", "pipelined", "sharded_join", "sharded_handoff")[int(self.lib.rovmpc_closed_loop_form(self._h))]
+
     def timing_enable(self, max_launches: int):
         self._check(self.lib.rovmpc_timing_enable(self._h, max_launches))
 

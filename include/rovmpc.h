@@ -327,8 +327,14 @@ const char *rovmpc_comm_placement(const rovmpc_handle *h);
  * from the second step on, theta/gamma_prev = theta/gamma and (theta, gamma) = the first predicted
  * node of the previous step's winner instead of the measured values -- and (2) one MPC step on
  * candidate batch pools[i % n_pools], record into results[i][result_len].  If rovmpc_comm_init
- * was called the step is the sharded one (all-reduce(min) per step; with feedback the plant
- * update then waits for the global record). */
+ * was called the step is the sharded one (all-reduce(min) per step).  With feedback the sharded
+ * loop hands the global winner's first node to the next rollout on the GPU (that rollout is
+ * launched behind the previous one and waits for the select kernel that follows the all-reduce)
+ * when the model has a step kernel (compiled-in or hiprtc-specialised) and the step kernel's
+ * whole grid is resident at once -- nblocks <= resident workgroups per CU x CUs, one round of
+ * workgroups; otherwise (interpreter models, grids of several rounds, environment
+ * ROVMPC_CL_JOIN=1) the plant update of each step waits for the global record (join per step).
+ * Both forms give the same records. */
 int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, double *d_state,
                               const void *d_pools, int32_t n_pools, int64_t k_offset,
                               int32_t feedback, double *d_results, void *stream);
@@ -341,6 +347,10 @@ int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, 
 int rovmpc_closed_loop_pipelined_device(rovmpc_handle *h, const double *d_exo, int64_t T, double *d_state,
                                         const void *d_pools, int32_t n_pools, int32_t feedback, double *d_results,
                                         void *stream);
+/* Form the last rovmpc_closed_loop_device / rovmpc_closed_loop_pipelined_device call on this handle took: 0 none yet (or
+ * the call was refused before it chose one), 1 single-GPU launch per step, 2 pipelined, 3 sharded with a join per step,
+ * 4 sharded with the GPU-side hand-off. */
+int32_t rovmpc_closed_loop_form(const rovmpc_handle *h);
 
 /* Per-launch timing of the rollout kernel with HIP events on the launch stream. */
 int rovmpc_timing_enable(rovmpc_handle *h, int32_t max_launches);

@@ -1179,10 +1179,12 @@ def test_closed_loop_equals_the_oracle(rv, orc, feedback, steps):
 @pytest.mark.parametrize("feedback", [True, False])
 def test_sharded_closed_loop_equals_the_unsharded_loop(rv, feedback):
     """BASELINE configs[4] as it is asked (the sharded step inside the loop), on a one-rank RCCL communicator:
-    rovmpc_closed_loop_device's communicator branch -- plant update, rollout into the slot row, ncclAllReduce, select, join per
-    step -- must give the un-sharded loop's records bit for bit over 250 steps, also for a shard that does not start at
-    candidate 0 (global indices = local + k_offset).  A hand-off that times out inside the loop is an error of the call,
-    never a silently wrong record, and the handle recovers."""
+    rovmpc_closed_loop_device's communicator branch -- rollout into the slot row, ncclAllReduce, select per step; with
+    feedback the GPU-side hand-off (the next rollout launched behind this one, its theta handed over by the select kernel),
+    with measured rows a plant update per step -- must give the un-sharded loop's records bit for bit over 250 steps, also
+    for a shard that does not start at candidate 0 (global indices = local + k_offset).  A hand-off that times out inside
+    the loop is an error of the call, never a silently wrong record, and the handle recovers.  (Other models, fp32, the
+    join-based form and big grids: test_sharded_handoff_closed_loop_across_paths.)"""
     from rovmpc.closed_loop import run_closed_loop, closed_loop_pools
     from rovmpc.sharded import NativeShardedMPC
     T = 250
@@ -1200,8 +1202,9 @@ def test_sharded_closed_loop_equals_the_unsharded_loop(rv, feedback):
         # one rollout of the loop never publishes its row: the collective of that step gives up after the hand-off time-out
         e.set_option("handoff_timeout_ms", 150.0)
         e.set_option("inject_skip_rolled", 1)
-        # (with feedback the loop joins every step and stops at the collective's give-up; without, the rollouts queued behind
-        # it give up on their slot rows first -- either way the call fails with the hand-off's reason)
+        # (with feedback the rollouts behind it wait on the GPU for the state its select hands over, which then is NaN --
+        # test_failed_handoff_poisons_every_later_record; without, the rollouts queued behind it give up on their slot rows
+        # first -- either way the call fails with the hand-off's reason)
         with pytest.raises(rv.RovmpcError, match="GPU-side hand-off gave up"):
             run_closed_loop(e, 12, 40, feedback=feedback, pools=pools)
         e.set_option("handoff_timeout_ms", 10000.0)
@@ -1211,6 +1214,166 @@ def test_sharded_closed_loop_equals_the_unsharded_loop(rv, feedback):
         assert not e.has_comm
         after = run_closed_loop(e, 12, 20, feedback=feedback, pools=pools)           # the handle is a plain one again
         assert np.array_equal(after.cost, plain20.cost) and np.array_equal(after.index, plain20.index)
+
+
+# Sharded closed loop with model feedback, one-rank native communicator.  (config, model, environment, model_path,
+# model_structure, form of rovmpc_closed_loop_device, steps, checked against the oracle).  K "multi": 256 x CUs with
+# 16-candidate, 4-wave workgroups -- a grid of several rounds, which must take the join-based form.
+_GI1 = {"gamma_invariant", "theta_stage_free"}
+_HANDOFF_CASES = [
+    pytest.param(dict(N=20, K=4096), None, {}, "builtin", set(), "sharded_handoff", 60, False, id="builtin-f64-C5"),
+    pytest.param(dict(N=20, K=1024, dtype="f32"), None, {}, "builtin", set(), "sharded_handoff", 60, False, id="builtin-f32"),
+    pytest.param(dict(K=512, no_builtin=True), None, {}, "jit", _GI1, "sharded_handoff", 60, True, id="jit-gi1-literal-N"),
+    pytest.param(dict(K=512, no_builtin=True), None, {"ROVMPC_JIT_NO_NC": "1"}, "jit", _GI1, "sharded_handoff", 60, True,
+                 id="jit-gi1-runtime-N"),
+    pytest.param(dict(K=512), (5, 9), {}, "jit", set(), "sharded_handoff", 60, True, id="jit-gi0"),
+    pytest.param(dict(K=512, dtype="f32", feature_map="gen2"), "gen2", {}, "jit", set(), "sharded_handoff", 60, False, id="gen2-f32"),
+    pytest.param(dict(N=12, K=256, force_interpreter=True), None, {}, "interpreter", set(), "sharded_join", 60, False,
+                 id="interpreter"),
+    pytest.param(dict(K="multi", candidates_per_block=16, threads_per_block=256), None, {}, "builtin", set(), "sharded_join", 12,
+                 False, id="multi-round-builtin"),
+    pytest.param(dict(K="multi", candidates_per_block=16, threads_per_block=256, no_builtin=True), None, {}, "jit", _GI1,
+                 "sharded_join", 12, False, id="multi-round-jit"),
+]
+
+
+@pytest.mark.parametrize("kw,rows,env,path,structure,form,steps,oracle", _HANDOFF_CASES)
+def test_sharded_handoff_closed_loop_across_paths(rv, orc, monkeypatch, kw, rows, env, path, structure, form, steps, oracle):
+    """rovmpc_closed_loop_device with a communicator and model feedback, in every model form it serves: the GPU-side hand-off
+    (rollout g + 1 behind rollout g, theta from the select kernel behind the all-reduce) must give the join-based form's
+    records (ROVMPC_CL_JOIN=1) bit for bit in fp64, the pipelined single-GPU loop's (same step-kernel instance) bit for bit
+    in fp32, and the un-sharded loop's for a shard at k_offset 0 and 3 K.  Interpreter models and grids the device cannot
+    hold in one round of workgroups take the join-based form (a multi-round grid on the hand-off would leave step g's
+    all-reduce and select no CU to run on while step g + 1's workgroups spin).  Loaded fp64 models are checked against the
+    oracle's closed loop too."""
+    import torch
+    from rovmpc.closed_loop import run_closed_loop, closed_loop_inputs, closed_loop_pools
+    from rovmpc.sharded import NativeShardedMPC
+    kw = dict(kw)
+    if kw["K"] == "multi":
+        n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+        kw["K"] = 256 * n_cu
+        nblocks = kw["K"] // kw["candidates_per_block"]
+        # 4-wave workgroups: at most 8 per CU (32 waves per CU), so the grid is at least two rounds on any geometry
+        assert kw["threads_per_block"] == 4 * 64 and nblocks > 8 * n_cu
+    if kw.get("feature_map") == "gen2":
+        kw["feature_map"] = rv.FEATURES_GEN2
+    model = rv.generation2_model() if rows == "gen2" else rv.default_model(*rows) if rows else None
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)                     # (read when the engine builds its model)
+    monkeypatch.delenv("ROVMPC_CL_JOIN", raising=False)
+    cfg = rv.MPCConfig(**kw)
+    f32 = cfg.dtype == "f32"
+    T = steps
+    with rv.Engine(cfg, model) as e:
+        assert e.model_path == path
+        if structure is not None:
+            assert e.model_structure == structure
+        e.set_option("handoff_timeout_ms", 2000.0)          # a regression fails in seconds, not in 10 s per step
+        pools = closed_loop_pools(e, 8, 3)
+        plain = run_closed_loop(e, 12, T, feedback=True, pools=pools)
+        assert e.closed_loop_form == "per_step"
+        e.device_status()
+        pipe = None
+        if f32:
+            try:
+                pipe = run_closed_loop(e, 12, T, feedback=True, mode="pipelined", pools=pools)
+            except rv.RovmpcError as exc:                   # (two grids do not fit the chip at once)
+                assert "resident" in str(exc)
+            else:
+                assert e.closed_loop_form == "pipelined"
+                e.device_status()
+        smpc = NativeShardedMPC(e, rank=0, world=1)
+        try:
+            sharded = {}
+            for k_offset in (0, 3 * cfg.K):
+                sharded[k_offset] = run_closed_loop(e, 12, T, feedback=True, pools=pools, k_offset=k_offset)
+                assert e.closed_loop_form == form
+                e.device_status()
+            monkeypatch.setenv("ROVMPC_CL_JOIN", "1")       # (read per call)
+            join = run_closed_loop(e, 12, T, feedback=True, pools=pools)
+            assert e.closed_loop_form == "sharded_join"
+            e.device_status()
+            monkeypatch.delenv("ROVMPC_CL_JOIN")
+        finally:
+            smpc.close()
+        rows_np, _ = closed_loop_inputs(e, 12, T)
+        pools_np = pools.cpu().numpy()
+
+    def same(a, b, dk=0):
+        assert np.array_equal(a.cost, b.cost) and np.array_equal(a.u, b.u) and np.array_equal(a.theta_gamma, b.theta_gamma)
+        assert np.array_equal(a.index, b.index + dk)
+
+    def close32(a, b):
+        # two instantiations of the fp32 body (test_pipelined_closed_loop_equals_launch_per_step, feedback)
+        np.testing.assert_allclose(a.cost, b.cost, rtol=1e-4)
+        np.testing.assert_allclose(a.theta_gamma, b.theta_gamma, rtol=1e-4, atol=1e-7)
+
+    assert np.isfinite(plain.cost).all()
+    hand = sharded[0]
+    same(sharded[3 * cfg.K], hand, 3 * cfg.K)
+    if not f32:
+        same(hand, join)
+        for k_offset, rep in sharded.items():
+            same(rep, plain, k_offset)
+    else:
+        close32(hand, join)
+        for k_offset, rep in sharded.items():
+            close32(rep, plain)
+            if pipe is not None:
+                same(rep, pipe, k_offset)
+    if oracle:
+        want = orc.closed_loop(oracle_cfg(orc, cfg), oracle_model(orc, model or rv.default_model()), rows_np, pools_np, True)
+        assert np.abs(want["theta_gamma"]).max() < 10.0 and np.abs(hand.theta_gamma).max() < 10.0     # the span is tame
+        for name, rep in (("handoff", hand), ("join", join)):
+            assert np.array_equal(rep.index, want["index"]), name
+            assert np.array_equal(rep.u, want["u"]), name
+            np.testing.assert_allclose(rep.cost, want["cost"], rtol=1e-9, err_msg=name)
+            np.testing.assert_allclose(rep.theta_gamma, want["theta_gamma"], rtol=1e-9, atol=1e-12, err_msg=name)
+
+
+@pytest.mark.parametrize("kw,rows", [(dict(N=20, K=512), None), (dict(K=512), (5, 9))], ids=["builtin-f64", "jit-gi0"])
+def test_failed_handoff_poisons_every_later_record(rv, kw, rows):
+    """A hand-off that times out in the sharded closed loop (here: step 0's rollout never publishes its row) leaves the
+    select kernel of that step with another step's row.  The state it hands over must be NaN, so that every later record
+    says so -- theta NaN, costs +inf by the kernel's rule -- instead of a loop that goes on, finite and wrong, from a stale
+    (theta, gamma).  The records are read although rovmpc_comm_sync failed (a C caller may do that); the next clean call
+    gives the plain loop's records bit for bit."""
+    import torch
+    from rovmpc.closed_loop import run_closed_loop, closed_loop_inputs, closed_loop_pools
+    from rovmpc.sharded import NativeShardedMPC
+    T = 30
+    dev = torch.device("cuda", 0)
+    with rv.Engine(rv.MPCConfig(**kw), rv.default_model(*rows) if rows else None) as e:
+        assert e.model_path == ("jit" if rows else "builtin")
+        pools = closed_loop_pools(e, 8, 3)
+        plain = run_closed_loop(e, 12, T, feedback=True, pools=pools)
+        smpc = NativeShardedMPC(e, rank=0, world=1)
+        exo_np, state_np = closed_loop_inputs(e, 12, T)
+        exo = torch.tensor(exo_np, device=dev)
+        state = torch.tensor(state_np, device=dev)
+        results = torch.zeros((T, e.result_len), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream()
+        torch.cuda.synchronize()
+        e.set_option("handoff_timeout_ms", 150.0)
+        e.set_option("inject_skip_rolled", 1)
+        e.closed_loop_device(exo.data_ptr(), T, state.data_ptr(), pools.data_ptr(), int(pools.shape[0]), results.data_ptr(),
+                             0, True, stream.cuda_stream)
+        assert e.closed_loop_form == "sharded_handoff"
+        with pytest.raises(rv.RovmpcError, match="GPU-side hand-off gave up"):
+            e.comm_sync(stream.cuda_stream)
+        torch.cuda.synchronize()
+        res = results.cpu().numpy()
+        assert np.isnan(res[0, 0])
+        assert not np.isfinite(res[1:, 0]).any(), res[:, 0]
+        assert np.isnan(res[1:, 7]).all(), res[:, 7]
+        e.set_option("handoff_timeout_ms", 2000.0)
+        again = run_closed_loop(e, 12, T, feedback=True, pools=pools)
+        assert e.closed_loop_form == "sharded_handoff"
+        e.device_status()
+        assert np.array_equal(again.cost, plain.cost) and np.array_equal(again.index, plain.index)
+        assert np.array_equal(again.u, plain.u) and np.array_equal(again.theta_gamma, plain.theta_gamma)
+        smpc.close()
 
 
 @pytest.mark.parametrize("feedback", [False, True])

@@ -34,6 +34,17 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.rovmpc_version()
 
 
+def test_closed_loop_form_query():
+    """rovmpc_closed_loop_form reads the handle only (-1 without one); Engine.closed_loop_form names the header's five values."""
+    import types
+    lib = rovmpc.load_library()
+    assert lib.rovmpc_closed_loop_form.restype is ctypes.c_int32
+    assert lib.rovmpc_closed_loop_form(None) == -1
+    names = [rovmpc.Engine.closed_loop_form.fget(types.SimpleNamespace(lib=types.SimpleNamespace(rovmpc_closed_loop_form=lambda h, v=v: v), _h=None))
+             for v in range(5)]
+    assert names == ["none", "per_step", "pipelined", "sharded_join", "sharded_handoff"]
+
+
 def test_config_struct_matches_c_layout():
     lib = rovmpc.load_library()
     from rovmpc._lib import Config
