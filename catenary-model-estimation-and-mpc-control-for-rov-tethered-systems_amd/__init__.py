@@ -20,7 +20,7 @@ from .integrate import (SymbolicRegressor, rk4_integration, integrate_theta_gamm
 from .features import extract_features, extract_features_arrays, features_dd, features_dd_arrays, preprocess_signals, compute_derivatives
 from .lagrangian import euler_lagrange, el_residuals, lagrangian_rollout, differentiate, EulerLagrange
 from .trajgen import generate_rov_trajectories, trajectory_csv
-from ._lib import MPPIParams
-from .mpc import MPC, MPPI, GaussianSampler, DeviceGaussianSampler, synthetic_problem
+from ._lib import MPPIParams, CEMParams
+from .mpc import MPC, MPPI, CEM, GaussianSampler, DeviceGaussianSampler, synthetic_problem
 
 __version__ = "0.1.0"

@@ -3,6 +3,7 @@ is missing or no GPU is present every compute entry point raises ``RovmpcError``
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -70,6 +71,47 @@ class MPPIParams(C.Structure):
         return p
 
 
+class CEMParams(C.Structure):
+    """Mirror of ``rovmpc_cem_params``.  ``make`` checks the values before the library sees them (n_elite <= K is checked by
+    the library and by ``rovmpc.CEM``, which know K)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_iter", C.c_int32), ("n_elite", C.c_int32), ("reserved", C.c_int32),
+                ("alpha", C.c_double), ("std", C.c_double * 3), ("std_min", C.c_double * 3),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
+
+    @classmethod
+    def make(cls, n_iter: int = 1, n_elite: int = 1, alpha: float = 0.0, std=(0.0, 0.0, 0.0), std_min=(0.0, 0.0, 0.0),
+             lo=(-math.inf,) * 3, hi=(math.inf,) * 3, reserved: int = 0) -> "CEMParams":
+        def integer(name, v, lo_, hi_):
+            if isinstance(v, bool) or int(v) != v or not lo_ <= int(v) <= hi_:
+                raise ValueError(f"{name} must be an integer in {lo_}..{hi_} (got {v!r})")
+            return int(v)
+
+        def triple(name, v, ok, what):
+            t = [float(x) for x in v]
+            if len(t) != 3 or not all(ok(x) for x in t):
+                raise ValueError(f"{name} must be 3 values, {what} (got {v!r})")
+            return t
+        n_iter = integer("n_iter", n_iter, 1, 64)
+        n_elite = integer("n_elite", n_elite, 1, 1024)
+        if reserved != 0:
+            raise ValueError(f"reserved must be 0 (got {reserved!r})")
+        alpha = float(alpha)
+        if not (math.isfinite(alpha) and 0.0 <= alpha < 1.0):
+            raise ValueError(f"alpha must be finite and 0 <= alpha < 1 (got {alpha!r})")
+        sd = triple("std", std, lambda x: math.isfinite(x) and x >= 0, "finite and >= 0")
+        sm = triple("std_min", std_min, lambda x: math.isfinite(x) and x >= 0, "finite and >= 0")
+        lo = triple("lo", lo, lambda x: not math.isnan(x), "not NaN")
+        hi = triple("hi", hi, lambda x: not math.isnan(x), "not NaN")
+        if not all(a <= b for a, b in zip(lo, hi)):
+            raise ValueError(f"lo must be <= hi on every channel (got {lo!r}, {hi!r})")
+        p = cls()
+        p.struct_size = C.sizeof(cls)
+        p.n_iter, p.n_elite, p.reserved, p.alpha = n_iter, n_elite, 0, alpha
+        p.std, p.std_min = (C.c_double * 3)(*sd), (C.c_double * 3)(*sm)
+        p.lo, p.hi = (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)
+        return p
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -87,6 +129,10 @@ _SIGNATURES = {
     "rovmpc_mppi_step": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P, _P, _P]),
     "rovmpc_mppi_last": (C.c_int, [_P, _P, _P]),
     "rovmpc_mppi_update_device": (C.c_int, [_P, _P, _P, C.c_double, _P, _P, _P, _P]),
+    "rovmpc_cem_reset": (C.c_int, [_P, _P]),
+    "rovmpc_cem_step": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, C.POINTER(CEMParams), _P, _P, _P, _P, _P]),
+    "rovmpc_cem_last": (C.c_int, [_P, _P, _P]),
+    "rovmpc_cem_update_device": (C.c_int, [_P, _P, _P, C.POINTER(CEMParams), _P, _P, _P, _P, _P, _P, _P]),
     "rovmpc_mpc_step_sampled": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, _P, _P, C.c_int32, _P]),
     "rovmpc_sampled_candidates": (C.c_int, [_P, _P]),
     "rovmpc_sample_candidates_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),

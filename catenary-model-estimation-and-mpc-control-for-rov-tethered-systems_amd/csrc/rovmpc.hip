@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "util_kernels.h"
+#include "cem_kernels.h"
 #include "embedded_sources.inc"
 
 using namespace rovmpc;
@@ -98,6 +99,17 @@ struct rovmpc_handle {
     double *h_mppi_out = nullptr, *d_mppi_out = nullptr;
     unsigned long long *h_mppi_done = nullptr, *d_mppi_done = nullptr;
     unsigned long long mppi_seq = 0, mppi_steps = 0;
+    // CEM (rovmpc_cem_*), allocated at the first rovmpc_cem_reset, as for MPPI: candidate tensor, costs, state and record of its
+    // own, mean and spread double-buffered by iteration, the update's slab and ticket, and the mapped host block
+    // [record, mu*, sigma*, stats] + elite list + sequence word the host spins on
+    void *d_cem_U = nullptr, *d_cem_J = nullptr;
+    double *d_cem_state = nullptr, *d_cem_record = nullptr, *d_cem_mu = nullptr, *d_cem_sig = nullptr;
+    int cem_cur = 0;                             // half of d_cem_mu holding the handle's mean
+    unsigned long long *d_cem_slab = nullptr; unsigned *d_cem_ticket = nullptr;
+    unsigned long long *d_cem_slab_x = nullptr; unsigned *d_cem_ticket_x = nullptr;   // rovmpc_cem_update_device's own
+    double *h_cem_out = nullptr, *d_cem_out = nullptr;
+    unsigned long long *h_cem_done = nullptr, *d_cem_done = nullptr;
+    unsigned long long cem_seq = 0, cem_steps = 0;
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -425,7 +437,9 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
                     h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
                     h->d_mppi_U, h->d_mppi_J, h->d_mppi_state, h->d_mppi_record, h->d_mppi_nu, h->d_mppi_slab, h->d_mppi_ticket,
-                    h->d_mppi_slab_x, h->d_mppi_ticket_x};
+                    h->d_mppi_slab_x, h->d_mppi_ticket_x,
+                    h->d_cem_U, h->d_cem_J, h->d_cem_state, h->d_cem_record, h->d_cem_mu, h->d_cem_sig, h->d_cem_slab,
+                    h->d_cem_ticket, h->d_cem_slab_x, h->d_cem_ticket_x};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     if (h->h_record) (void)hipHostFree(h->h_record);
@@ -433,6 +447,8 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     if (h->h_err) (void)hipHostFree(h->h_err);
     if (h->h_mppi_out) (void)hipHostFree(h->h_mppi_out);
     if (h->h_mppi_done) (void)hipHostFree(h->h_mppi_done);
+    if (h->h_cem_out) (void)hipHostFree(h->h_cem_out);
+    if (h->h_cem_done) (void)hipHostFree(h->h_cem_done);
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete h->epoch_ctr;
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1433,6 +1449,197 @@ extern "C" int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, cons
     }
     return launch_mppi_update(h, d_J, d_U, lambda, d_nominal_in, d_nominal_out, 0, d_stats, h->d_mppi_slab_x, h->d_mppi_ticket_x,
                               nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+// ---- CEM: clamped sampling around a per-node mean and spread, exact elite selection and refit on the GPU ---------------
+struct CemGeo { int G; long long slice; int Lcap; };
+static CemGeo cem_geometry(long long K) {
+    const long long G = (K + CEM_SLICE - 1) / CEM_SLICE, slice = (K + G - 1) / G;
+    return {(int)((K + slice - 1) / slice), slice, (int)(slice < CEM_MAX_ELITE ? slice : CEM_MAX_ELITE)};
+}
+
+static int cem_check_params(rovmpc_handle *h, const rovmpc_cem_params *p) {
+    if (!p) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem: null params");
+    if (p->struct_size != (int32_t)sizeof(rovmpc_cem_params))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_params.struct_size %d != %d (ABI mismatch)", p->struct_size, (int)sizeof(rovmpc_cem_params));
+    if (p->n_iter < 1 || p->n_iter > 64) FAIL(h, ROVMPC_ERR_INVALID, "n_iter must be in 1..64 (got %d)", p->n_iter);
+    const int emax = h->cfg.K < CEM_MAX_ELITE ? h->cfg.K : CEM_MAX_ELITE;
+    if (p->n_elite < 1 || p->n_elite > emax) FAIL(h, ROVMPC_ERR_INVALID, "n_elite must be in 1..%d = min(K, %d) (got %d)", emax, CEM_MAX_ELITE, p->n_elite);
+    if (p->reserved != 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_params.reserved must be 0 (got %d)", p->reserved);
+    if (!(isfinite(p->alpha) && p->alpha >= 0 && p->alpha < 1)) FAIL(h, ROVMPC_ERR_INVALID, "alpha must be finite, 0 <= alpha < 1 (got %g)", p->alpha);
+    for (int i = 0; i < 3; ++i) {
+        if (!(isfinite(p->std[i]) && p->std[i] >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "std[%d] must be finite and >= 0 (got %g)", i, p->std[i]);
+        if (!(isfinite(p->std_min[i]) && p->std_min[i] >= 0))
+            FAIL(h, ROVMPC_ERR_INVALID, "std_min[%d] must be finite and >= 0 (got %g)", i, p->std_min[i]);
+        if (isnan(p->lo[i]) || isnan(p->hi[i]) || !(p->lo[i] <= p->hi[i]))
+            FAIL(h, ROVMPC_ERR_INVALID, "bounds of channel %d must not be NaN and lo <= hi (got %g, %g)", i, p->lo[i], p->hi[i]);
+    }
+    return ROVMPC_OK;
+}
+
+// slab [G][2 + 2 Lcap] (only when the update has several workgroups) and its ticket word (zeroed once: the last workgroup of
+// every launch re-arms it)
+static int cem_alloc_slab(rovmpc_handle *h, unsigned long long **slab, unsigned **ticket) {
+    const CemGeo g = cem_geometry(h->cfg.K);
+    if (g.G > 1) HIPCHK(h, hipMalloc((void **)slab, (size_t)g.G * (2 + 2 * (size_t)g.Lcap) * sizeof(unsigned long long)));
+    HIPCHK(h, hipMalloc((void **)ticket, 16));
+    HIPCHK(h, hipMemset(*ticket, 0, 16));
+    return ROVMPC_OK;
+}
+
+static int launch_cem_update(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p, const double *mu_in,
+                             const double *sigma_in, double *mu_out, double *sigma_out, int shift, long long *elite, double *stats,
+                             unsigned long long *slab, unsigned *ticket, double *record, double *host_out, long long *host_elite,
+                             unsigned long long *done_flag, unsigned long long done_seq, hipStream_t s) {
+    const CemGeo g = cem_geometry(h->cfg.K);
+    CemUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.E = p->n_elite; a.Lcap = g.Lcap;
+    a.alpha = p->alpha;
+    for (int i = 0; i < 3; ++i) { a.std[i] = p->std[i]; a.std_min[i] = p->std_min[i]; a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
+    a.mu_in = mu_in; a.sigma_in = sigma_in; a.mu_out = mu_out; a.sigma_out = sigma_out; a.shift = shift;
+    a.elite = elite; a.stats = stats; a.slab = slab; a.ticket = ticket;
+    a.record = record; a.R = rovmpc_result_len(h); a.host_out = host_out; a.host_elite = host_elite;
+    a.done_flag = done_flag; a.done_seq = done_seq;
+    const bool wide = a.C3 > CEM_NT;
+    if (h->cfg.dtype == ROVMPC_F64) {
+        if (wide) hipLaunchKernelGGL((cem_update_kernel<double, 4>), dim3(g.G), dim3(CEM_NT), 0, s, a);
+        else hipLaunchKernelGGL((cem_update_kernel<double, 1>), dim3(g.G), dim3(CEM_NT), 0, s, a);
+    } else {
+        if (wide) hipLaunchKernelGGL((cem_update_kernel<float, 4>), dim3(g.G), dim3(CEM_NT), 0, s, a);
+        else hipLaunchKernelGGL((cem_update_kernel<float, 1>), dim3(g.G), dim3(CEM_NT), 0, s, a);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "CEM update launch failed: %s", hipGetErrorString(e));
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_cem_reset(rovmpc_handle *h, const double *mean) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!mean) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_reset: null mean");
+    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "CEM is single-GPU: not available once rovmpc_comm_init has run");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const rovmpc_config &c = h->cfg;
+    const size_t C3 = 3 * (size_t)c.N;
+    if (!h->d_cem_mu) {
+        const size_t R = (size_t)rovmpc_result_len(h);
+        HIPCHK(h, hipMalloc(&h->d_cem_U, (size_t)c.K * C3 * h->esz));
+        HIPCHK(h, hipMalloc(&h->d_cem_J, (size_t)c.K * h->esz));
+        HIPCHK(h, hipMalloc((void **)&h->d_cem_state, ROVMPC_STATE_LEN * sizeof(double)));
+        HIPCHK(h, hipMalloc((void **)&h->d_cem_record, R * sizeof(double)));
+        int rc = cem_alloc_slab(h, &h->d_cem_slab, &h->d_cem_ticket);
+        if (rc) return rc;
+        // [record (R), mu* (3N), sigma* (3N), stats (4)] then the elite list (int64 [CEM_MAX_ELITE])
+        HIPCHK(h, hipHostMalloc((void **)&h->h_cem_out, (R + 2 * C3 + 4 + CEM_MAX_ELITE) * sizeof(double), hipHostMallocMapped));
+        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_cem_out, h->h_cem_out, 0));
+        HIPCHK(h, hipHostMalloc((void **)&h->h_cem_done, 64, hipHostMallocMapped));
+        *h->h_cem_done = 0;
+        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_cem_done, h->h_cem_done, 0));
+        HIPCHK(h, hipMalloc((void **)&h->d_cem_sig, 2 * C3 * sizeof(double)));
+        HIPCHK(h, hipMalloc((void **)&h->d_cem_mu, 2 * C3 * sizeof(double)));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_cem_mu, mean, C3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->cem_cur = 0;
+    return ROVMPC_OK;
+}
+
+template <typename T>
+static int launch_cem_sample(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t counter, const rovmpc_cem_params *p,
+                             const double *mu, const double *sigma) {
+    CemSampleArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    if (state) { sa.state = *state; sa.d_state = h->d_cem_state; }
+    sa.seed = seed; sa.counter = counter;
+    for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
+    sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.mu = mu; sa.sigma = sigma;
+    const int bs = 256;
+    const int grid = (int)(((sa.total + 3) / 4 + bs - 1) / bs);
+    hipLaunchKernelGGL(cem_sample_kernel<T>, dim3(grid), dim3(bs), 0, h->stream, sa, (T *)h->d_cem_U);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "CEM sampler launch failed: %s", hipGetErrorString(e));
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const rovmpc_cem_params *p,
+                               double *record_out, double *mean_out, double *std_out, int64_t *elite_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_step: null pointer");
+    int rc = cem_check_params(h, p);
+    if (rc) return rc;
+    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "CEM is single-GPU: not available once rovmpc_comm_init has run");
+    if (!h->d_cem_mu) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_step before rovmpc_cem_reset");
+    if ((rc = check_ready(h))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    const unsigned long long seq = ++h->cem_seq;
+    int cur = h->cem_cur;
+    for (int i = 0; i < p->n_iter; ++i) {
+        const bool last = i + 1 == p->n_iter;
+        const uint64_t counter = step * (uint64_t)p->n_iter + (uint64_t)i;        // wraps
+        const double *mu_in = h->d_cem_mu + cur * C3, *sig_in = i == 0 ? nullptr : h->d_cem_sig + cur * C3;   // sigma_0 = std
+        double *mu_out = h->d_cem_mu + (cur ^ 1) * C3, *sig_out = h->d_cem_sig + (cur ^ 1) * C3;
+        rc = h->cfg.dtype == ROVMPC_F64 ? launch_cem_sample<double>(h, i == 0 ? state : nullptr, seed, counter, p, mu_in, sig_in)
+                                        : launch_cem_sample<float>(h, i == 0 ? state : nullptr, seed, counter, p, mu_in, sig_in);
+        if (rc) return rc;
+        // the rollout of rovmpc_step on this tensor, costs into CEM's own buffer
+        h->arg_J = h->d_cem_J;
+        rc = enqueue_step(h, h->d_cem_state, h->d_cem_U, nullptr, h->d_cem_record, 0, nullptr, 0, 1, h->stream);
+        h->arg_J = nullptr;
+        if (rc) return rc;
+        rc = launch_cem_update(h, h->d_cem_J, h->d_cem_U, p, mu_in, sig_in, mu_out, sig_out, last ? 1 : 0, nullptr, nullptr,
+                               h->d_cem_slab, h->d_cem_ticket, last ? h->d_cem_record : nullptr, last ? h->d_cem_out : nullptr,
+                               last ? (long long *)(h->d_cem_out + R + 2 * C3 + 4) : nullptr, last ? h->d_cem_done : nullptr,
+                               seq, h->stream);
+        if (rc) return rc;
+        cur ^= 1;
+    }
+    h->cem_cur = cur;
+    ++h->cem_steps;
+    // the last update releases `seq` behind the record in mapped host memory: spin on it, as rovmpc_mppi_step does
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; ++spins) {
+        if (__atomic_load_n(h->h_cem_done, __ATOMIC_ACQUIRE) == seq) break;
+        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (__atomic_load_n(h->h_cem_done, __ATOMIC_ACQUIRE) != seq) FAIL(h, ROVMPC_ERR_HIP, "the CEM step finished without publishing its record");
+            break;
+        }
+    }
+    const double *o = h->h_cem_out;
+    memcpy(record_out, o, R * sizeof(double));
+    if (mean_out) memcpy(mean_out, o + R, C3 * sizeof(double));
+    if (std_out) memcpy(std_out, o + R + C3, C3 * sizeof(double));
+    if (stats_out) memcpy(stats_out, o + R + 2 * C3, 4 * sizeof(double));
+    if (elite_out) memcpy(elite_out, o + R + 2 * C3 + 4, (size_t)p->n_elite * sizeof(int64_t));
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_cem_last(rovmpc_handle *h, void *U_out, void *J_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (h->cem_steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_last: no CEM step yet");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (U_out) HIPCHK(h, hipMemcpy(U_out, h->d_cem_U, (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
+    if (J_out) HIPCHK(h, hipMemcpy(J_out, h->d_cem_J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost));
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p,
+                                        const double *d_mean_in, const double *d_std_in, double *d_mean_out, double *d_std_out,
+                                        int64_t *d_elite_out, double *d_stats, void *stream) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!d_J || !d_U || !d_mean_in || !d_std_in || !d_mean_out || !d_std_out)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_update_device: null pointer");
+    int rc = cem_check_params(h, p);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->d_cem_ticket_x) {
+        rc = cem_alloc_slab(h, &h->d_cem_slab_x, &h->d_cem_ticket_x);
+        if (rc) return rc;
+    }
+    return launch_cem_update(h, d_J, d_U, p, d_mean_in, d_std_in, d_mean_out, d_std_out, 0, (long long *)d_elite_out, d_stats,
+                             h->d_cem_slab_x, h->d_cem_ticket_x, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // ---- timing ---------------------------------------------------------------------------------

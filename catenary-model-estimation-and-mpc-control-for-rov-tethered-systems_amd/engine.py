@@ -9,7 +9,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import Config, State, MPPIParams, RovmpcError, check, load_library
+from ._lib import Config, State, MPPIParams, CEMParams, RovmpcError, check, load_library
 from .model import DynamicsModel, default_model
 
 
@@ -266,6 +266,41 @@ class Engine:
         """The weighted update alone on device buffers (raw pointers), asynchronous on `stream`."""
         self._check(self.lib.rovmpc_mppi_update_device(self._h, d_J, d_U, float(lam), d_nominal_in, d_nominal_out,
                                                        d_stats or None, stream))
+
+    # -- CEM (rovmpc_cem_*) ------------------------------------------------------------------
+    def cem_reset(self, mean):
+        """Set the handle's CEM mean (N, 3); allocates the CEM buffers on first use."""
+        mu = np.ascontiguousarray(mean, dtype=np.float64)
+        if mu.shape != (self.cfg.N, 3):
+            raise ValueError(f"mean must have shape ({self.cfg.N}, 3), got {mu.shape}")
+        self._check(self.lib.rovmpc_cem_reset(self._h, _ptr(mu)))
+
+    def cem_step(self, state, seed: int, step: int, params: CEMParams):
+        """One CEM control step: returns (record [J*, k*, u(3), traj], mu* (N, 3), sigma* (N, 3), elites (n_elite,) int64,
+        stats (J rank 0, J rank E'-1, |F|, J_0))."""
+        if not isinstance(params, CEMParams):
+            raise TypeError("params must be a CEMParams (CEMParams.make(...))")
+        s = _c_state(state_array(state))
+        rec = np.empty(self.result_len); mu = np.empty((self.cfg.N, 3)); sg = np.empty((self.cfg.N, 3))
+        el = np.empty(params.n_elite, dtype=np.int64); stats = np.empty(4)
+        self._check(self.lib.rovmpc_cem_step(self._h, C.byref(s), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                             C.byref(params), _ptr(rec), _ptr(mu), _ptr(sg), _ptr(el), _ptr(stats)))
+        return rec, mu, sg, el, stats
+
+    def cem_last(self):
+        """Host copies of the last CEM iteration's candidates U (K, N, 3) and costs J (K,)."""
+        U = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)
+        J = np.empty(self.cfg.K, dtype=self.cfg.np_dtype)
+        self._check(self.lib.rovmpc_cem_last(self._h, _ptr(U), _ptr(J)))
+        return U, J
+
+    def cem_update_device(self, d_J: int, d_U: int, params: CEMParams, d_mean_in: int, d_std_in: int, d_mean_out: int,
+                          d_std_out: int, d_elite_out: int = 0, d_stats: int = 0, stream: int = 0):
+        """The elite selection and refit alone on device buffers (raw pointers), asynchronous on `stream`."""
+        if not isinstance(params, CEMParams):
+            raise TypeError("params must be a CEMParams (CEMParams.make(...))")
+        self._check(self.lib.rovmpc_cem_update_device(self._h, d_J, d_U, C.byref(params), d_mean_in, d_std_in, d_mean_out,
+                                                      d_std_out, d_elite_out or None, d_stats or None, stream))
 
     def sampled_candidates(self) -> np.ndarray:
         """Host copy of the candidate tensor of the last ``mpc_step_sampled`` (tests / inspection)."""

@@ -145,6 +145,68 @@ class MPPI:
         self.engine.close()
 
 
+class CEM:
+    """``cem = CEM(N=20, K=4096, n_elite=64); u = cem.step(state)``: the cross-entropy method.
+
+    The handle keeps a mean plan (N, 3); each step samples K candidates on the GPU around it with a per-node spread, clamped
+    to the box [lo, hi] (candidate 0 = the clamped mean), rolls them out, keeps the ``n_elite`` cheapest (by rank only, ties to
+    the lower index) and refits mean and spread from them (``n_iter`` times, without a host round trip); it returns the
+    clamped first control of the mean.  The law is stated in include/rovmpc.h (rovmpc_cem_step).
+    Defaults: mean = the scaler mean of x3..x5 on every node, std = its scale, std_min = 0, bounds +-inf, alpha = 0,
+    n_elite = K / 64 (at least 1).  After ``step``: ``last`` (the record of the last rollout, with u = clamp(mean*[0])),
+    ``last_stats`` (J_best, J_worst_elite, n_finite, J0), ``mean`` and ``std`` (the plan and spread the step returned) and
+    ``elites`` (the last iteration's elite indices in rank order, -1 padded).
+    """
+
+    def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, n_elite: Optional[int] = None,
+                 n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0), lo=(-np.inf,) * 3, hi=(np.inf,) * 3,
+                 seed: int = 20250523, mean=None, reserved: int = 0, **overrides):
+        m = default_model()
+        K = int(overrides["K"]) if "K" in overrides else (cfg.K if cfg is not None else MPCConfig().K)
+        if n_elite is None:
+            n_elite = max(K // 64, 1)
+        if isinstance(n_elite, bool) or int(n_elite) != n_elite or int(n_elite) > K:
+            raise ValueError(f"n_elite must be an integer <= K = {K} (got {n_elite!r})")
+        std = np.asarray(std if std is not None else m.scale[3:6], dtype=np.float64)
+        self.params = _lib.CEMParams.make(n_iter, n_elite, alpha, std, std_min, lo, hi, reserved)   # ValueError before the library is called
+        self.n_iter, self.n_elite, self.alpha = int(n_iter), int(n_elite), float(alpha)
+        self.seed = int(seed)
+        self.engine = Engine(cfg, model, **overrides)
+        self.cfg = self.engine.cfg
+        self._default_mean = np.asarray(m.mean[3:6], dtype=np.float64)
+        self.step_count = 0
+        self.last: Optional[StepResult] = None
+        self.last_stats: Optional[dict] = None
+        self.mean: Optional[np.ndarray] = None
+        self.std: Optional[np.ndarray] = None
+        self.elites: Optional[np.ndarray] = None
+        self.reset(mean)
+
+    def reset(self, mean=None):
+        """Set the mean plan ((N, 3), or (3,) repeated on every node; default: the scaler mean of x3..x5)."""
+        N = self.cfg.N
+        mu = self._default_mean if mean is None else np.asarray(mean, dtype=np.float64)
+        if mu.shape == (3,):
+            mu = np.tile(mu, (N, 1))
+        if mu.shape != (N, 3):
+            raise ValueError(f"mean must have shape ({N}, 3) or (3,), got {mu.shape}")
+        self.engine.cem_reset(mu)
+        self.mean = mu.copy()
+
+    def step(self, state) -> np.ndarray:
+        rec, mu, sg, el, stats = self.engine.cem_step(state, self.seed, self.step_count, self.params)
+        self.step_count += 1
+        N = self.cfg.N
+        self.last = StepResult(rec[2:5].copy(), rec[5:].reshape(N + 1, 2).copy(), float(rec[0]), int(rec[1]))
+        self.last_stats = {"J_best": float(stats[0]), "J_worst_elite": float(stats[1]), "n_finite": int(stats[2]),
+                           "J0": float(stats[3])}
+        self.mean, self.std, self.elites = mu, sg, el
+        return self.last.u
+
+    def close(self):
+        self.engine.close()
+
+
 def synthetic_problem(K: int, N: int, seed: int = 20250523, dtype=np.float64):
     """The synthetic MPC step of SURVEY section 8(d) / BASELINE.md section 3: state at the scaler means,
     candidates drawn from the scaler statistics of x3..x5.  Returns (state(16,), U(K,N,3))."""

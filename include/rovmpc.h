@@ -240,6 +240,59 @@ int rovmpc_mppi_last(rovmpc_handle *h, void *U_out, void *J_out);
 int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda,
                               const double *d_nominal_in, double *d_nominal_out, double *d_stats, void *stream);
 
+/* ---- CEM: the cross-entropy method, elite selection and refit of a per-node mean and spread --------------------------
+ * (Rubinstein 1999; de Boer et al. 2005.)  The handle holds a mean mu[N][3], always in double, set by rovmpc_cem_reset.
+ * clamp(v) = fmin(fmax(v, lo[ch]), hi[ch]) in double (infinite bounds make it the identity, bit for bit).
+ * Control step `step` with `seed`, state x; sigma_0[n][ch] = std[ch] on every node; for i = 0 .. n_iter - 1:
+ *   1. counter c = step * n_iter + i (uint64, wraps); z = the sampler's standard normals of rovmpc_mpc_step_sampled keyed by
+ *      (seed, c), element order e = (k N + n) 3 + ch;
+ *   2. candidates U[0][n][ch] = (T) clamp(mu_i[n][ch]), U[k][n][ch] = (T) clamp(fma(sigma_i[n][ch], z_e, mu_i[n][ch])) for k >= 1;
+ *   3. the rollout of rovmpc_step on (x, U): same kernel, costs and record, for every model path, dtype, vt mode and feature map;
+ *   4. F = {k : J_k finite} (NaN, +inf and -inf alike are not); F ordered by the pair (J_k, k) ascending (ties go to the
+ *      lower index); E' = min(n_elite, |F|) and the elites are the first E' of that order.
+ *      E' = 0: mu_{i+1} = mu_i and sigma_{i+1} = sigma_i, bit for bit;
+ *      else, in double whatever T is, per node and channel: m = (1/E') sum_elite U[k], v = (1/E') sum_elite (U[k] - m)^2
+ *      (two passes), mu_{i+1} = alpha mu_i + (1 - alpha) m, sigma_{i+1} = max(std_min[ch], alpha sigma_i + (1 - alpha) sqrt(v)).
+ *      The sums are taken in a fixed order (rank order, in row-lanes added in order), with no float atomics: results are
+ *      bitwise reproducible.  Only the rank of the costs matters: a strictly increasing map of J gives the same plan.
+ * Results: mu* = mu_{n_iter}, sigma* = sigma_{n_iter}; record_out [rovmpc_result_len] keeps the layout [J*, k*, u[3], traj] with
+ * J*, k*, traj the last rollout's (its cheapest candidate) and u = clamp(mu*[0]), the control to apply; elite_out[n_elite]
+ * (int64) = the last iteration's elite indices in rank order, padded with -1; stats_out = (J of rank 0, J of rank E' - 1,
+ * |F|, J_0) of the last iteration (the first two NaN when E' = 0; J_0 the clamped mean's own cost); mean_out = mu*,
+ * std_out = sigma*.  The handle then keeps mu[n] = mu*[min(n + 1, N - 1)]; sigma starts from std again at the next step.
+ * The host waits once per control step (the last update publishes into mapped memory), never between iterations.
+ * CEM has buffers of its own (candidate tensor, costs, state, record, mean and spread, elite list, slab), allocated at the
+ * first reset: steps of rovmpc_step / rovmpc_mpc_step_sampled / rovmpc_mppi_step on the same handle give the same bits with
+ * or without CEM steps in between.
+ * Errors: ROVMPC_ERR_INVALID for parameters outside the ranges below (n_elite > cfg.K included), a struct_size mismatch or a
+ * step before the first reset, before anything is launched; ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
+ * Not provided: sharded CEM, batched and closed-loop device entries. */
+typedef struct rovmpc_cem_params {
+    int32_t struct_size;        /* = sizeof(rovmpc_cem_params), ABI check                   */
+    int32_t n_iter;             /* iterations per control step, 1..64                       */
+    int32_t n_elite;            /* elites per iteration, 1..min(cfg.K, 1024)                */
+    int32_t reserved;           /* 0                                                        */
+    double alpha;               /* smoothing, finite, 0 <= alpha < 1                        */
+    double std[3];              /* initial spread per channel, finite, >= 0                 */
+    double std_min[3];          /* spread floor per channel, finite, >= 0                   */
+    double lo[3], hi[3];        /* box per channel, not NaN, lo <= hi, +-inf allowed        */
+} rovmpc_cem_params;            /* 120 bytes */
+
+/* mean[N][3] (host, double); allocates the CEM buffers on first use. */
+int rovmpc_cem_reset(rovmpc_handle *h, const double *mean);
+/* One control step (blocking); mean_out[N][3], std_out[N][3], elite_out[n_elite] and stats_out[4] may be NULL. */
+int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const rovmpc_cem_params *p,
+                    double *record_out, double *mean_out, double *std_out, int64_t *elite_out, double *stats_out);
+/* Host copies of the last iteration's candidates U[K][N][3] and costs J[K] (reals of cfg.dtype); either may be NULL. */
+int rovmpc_cem_last(rovmpc_handle *h, void *U_out, void *J_out);
+/* Step 4 alone on caller device buffers, asynchronously on `stream` (no shift): d_J[K], d_U[K][N][3] (K = cfg.K, reals of
+ * cfg.dtype), d_mean_in / d_std_in / d_mean_out / d_std_out [N][3] double, d_elite_out[n_elite] int64 or NULL, d_stats[4]
+ * double or NULL.  p->n_iter, std, lo and hi are checked but not used.  Calls on one handle must not overlap in time (they
+ * share one slab). */
+int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p,
+                             const double *d_mean_in, const double *d_std_in, double *d_mean_out, double *d_std_out,
+                             int64_t *d_elite_out, double *d_stats, void *stream);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
