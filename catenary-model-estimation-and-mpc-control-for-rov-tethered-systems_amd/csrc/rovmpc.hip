@@ -25,6 +25,32 @@ using namespace rovmpc;
 
 static thread_local std::string g_create_error;
 
+// Where the kernel that ends a step leaves its results for the host: a block of doubles in mapped host memory and, behind
+// it, the sequence word that kernel releases at system scope and the host spins on (mailbox_wait).
+struct Mailbox {
+    double *h_out = nullptr, *d_out = nullptr;
+    unsigned long long *h_done = nullptr, *d_done = nullptr;
+    unsigned long long seq = 0;                  // last sequence number handed out
+};
+
+// Partial results of an update kernel's workgroups and the ticket word its last workgroup re-arms (zeroed once).
+struct Slab { void *rows = nullptr; unsigned *ticket = nullptr; };
+
+// What a controller that iterates on a plan (MPPI: the nominal; CEM: mean and spread) owns, allocated at its first reset: a
+// candidate tensor, costs, state and record of its own (the other entry points' buffers are never touched), the plan
+// double-buffered by iteration, the update's slab and the mailbox [record, plan*, ..., stats] of its step.
+struct PlanCtl {
+    const char *name, *abi, *step_name;          // "MPPI", "mppi", "MPPI step": for the messages
+    bool allocated = false;
+    void *U = nullptr, *J = nullptr;             // T [K][N][3], T [K]
+    double *state = nullptr, *record = nullptr;
+    double *plan = nullptr, *spread = nullptr;   // [2][3N] each; spread: CEM only
+    int cur = 0;                                 // half of plan (and spread) holding the handle's
+    Slab slab, slab_x;                           // of *_step; of *_update_device (allocated at its first call)
+    Mailbox box;
+    unsigned long long steps = 0;
+};
+
 struct rovmpc_handle {
     rovmpc_config cfg;
     hipStream_t stream = nullptr;
@@ -77,10 +103,9 @@ struct rovmpc_handle {
     double handoff_timeout_ms = 10000.0;      // give-up time of the GPU-side hand-off waits (rovmpc_set_option)
     int inject_skip_rolled = 0, inject_skip_consumed = 0;   // test hooks: the next N steps lose that publication
     // rovmpc_mpc_step_sampled: two candidate tensors (the sampler of step s+1 reads the winner of step s for the warm
-    // start), the record mirrored into mapped host memory, and the sequence word the host spins on
+    // start) and the mailbox of the record (its sequence numbers are samp_steps)
     void *d_Us[2] = {nullptr, nullptr};
-    double *h_record = nullptr, *d_record_host = nullptr;
-    unsigned long long *h_done = nullptr, *d_done = nullptr;
+    Mailbox samp_box;
     unsigned long long samp_steps = 0;
     double *d_best = nullptr;                    // [2][N][3]: winner's sequence of the last fused-sampling steps, by step parity
     double *d_blk_u = nullptr;                   // [max_blocks][3 N]: per-workgroup best controls of a fused-sampling step
@@ -88,28 +113,8 @@ struct rovmpc_handle {
     unsigned long long last_seed = 0, last_step = 0; double last_mean[3] = {}, last_std[3] = {}; int last_warm = 0; bool last_fused = false;
     double *arg_result_host = nullptr; unsigned long long *arg_done_flag = nullptr; unsigned long long arg_done_seq = 0;
     void *arg_J = nullptr;                       // costs of the launch being enqueued go here instead of d_J (null: d_J)
-    // MPPI (rovmpc_mppi_*), allocated at the first rovmpc_mppi_reset: candidate tensor, costs, state and record of its own
-    // (the other entry points' buffers are never touched), the nominal double-buffered by iteration, the update's slab and
-    // ticket, and the mapped host block [record, nu*, stats] + sequence word the host spins on
-    void *d_mppi_U = nullptr, *d_mppi_J = nullptr;
-    double *d_mppi_state = nullptr, *d_mppi_record = nullptr, *d_mppi_nu = nullptr;
-    int mppi_cur = 0;                            // half of d_mppi_nu holding the handle's nominal
-    double *d_mppi_slab = nullptr; unsigned *d_mppi_ticket = nullptr;
-    double *d_mppi_slab_x = nullptr; unsigned *d_mppi_ticket_x = nullptr;   // rovmpc_mppi_update_device's own
-    double *h_mppi_out = nullptr, *d_mppi_out = nullptr;
-    unsigned long long *h_mppi_done = nullptr, *d_mppi_done = nullptr;
-    unsigned long long mppi_seq = 0, mppi_steps = 0;
-    // CEM (rovmpc_cem_*), allocated at the first rovmpc_cem_reset, as for MPPI: candidate tensor, costs, state and record of its
-    // own, mean and spread double-buffered by iteration, the update's slab and ticket, and the mapped host block
-    // [record, mu*, sigma*, stats] + elite list + sequence word the host spins on
-    void *d_cem_U = nullptr, *d_cem_J = nullptr;
-    double *d_cem_state = nullptr, *d_cem_record = nullptr, *d_cem_mu = nullptr, *d_cem_sig = nullptr;
-    int cem_cur = 0;                             // half of d_cem_mu holding the handle's mean
-    unsigned long long *d_cem_slab = nullptr; unsigned *d_cem_ticket = nullptr;
-    unsigned long long *d_cem_slab_x = nullptr; unsigned *d_cem_ticket_x = nullptr;   // rovmpc_cem_update_device's own
-    double *h_cem_out = nullptr, *d_cem_out = nullptr;
-    unsigned long long *h_cem_done = nullptr, *d_cem_done = nullptr;
-    unsigned long long cem_seq = 0, cem_steps = 0;
+    // MPPI (rovmpc_mppi_*): mailbox [record, nu*, stats]; CEM (rovmpc_cem_*): [record, mu*, sigma*, stats, elite list]
+    PlanCtl mppi{"MPPI", "mppi", "MPPI step"}, cem{"CEM", "cem", "CEM step"};
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -195,6 +200,63 @@ extern "C" const char *rovmpc_last_error(const rovmpc_handle *h) {
 }
 
 extern "C" int32_t rovmpc_result_len(const rovmpc_handle *h) { return h ? 5 + 2 * (h->cfg.N + 1) : 0; }
+
+// ---- allocation shared by the sampled step, MPPI and CEM: all or nothing, so a call repeated after a failure leaks nothing ----
+template <typename P> static void dev_free(P *&p) { if (p) (void)hipFree(p); p = nullptr; }
+
+static void mailbox_free(Mailbox &m) {
+    for (void *p : {(void *)m.h_out, (void *)m.h_done}) if (p) (void)hipHostFree(p);
+    m = Mailbox();
+}
+
+static int mailbox_alloc(rovmpc_handle *h, Mailbox &m, size_t n_doubles) {
+    hipError_t e = hipHostMalloc((void **)&m.h_out, n_doubles * sizeof(double), hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&m.d_out, m.h_out, 0);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&m.h_done, 64, hipHostMallocMapped);
+    if (e == hipSuccess) { *m.h_done = 0; e = hipHostGetDevicePointer((void **)&m.d_done, m.h_done, 0); }
+    if (e == hipSuccess) return ROVMPC_OK;
+    mailbox_free(m);
+    FAIL(h, ROVMPC_ERR_HIP, "mapped host memory for a step's results: %s", hipGetErrorString(e));
+}
+
+static void slab_free(Slab &s) { dev_free(s.rows); dev_free(s.ticket); }
+
+// bytes = 0: an update of one workgroup needs the ticket only.  Nothing to do when the slab is there.
+static int slab_alloc(rovmpc_handle *h, Slab &s, size_t bytes) {
+    if (s.ticket) return ROVMPC_OK;
+    hipError_t e = bytes ? hipMalloc(&s.rows, bytes) : hipSuccess;
+    if (e == hipSuccess) e = hipMalloc((void **)&s.ticket, 16);
+    if (e == hipSuccess) e = hipMemset(s.ticket, 0, 16);
+    if (e == hipSuccess) return ROVMPC_OK;
+    slab_free(s);
+    FAIL(h, ROVMPC_ERR_HIP, "update slab: %s", hipGetErrorString(e));
+}
+
+static void plan_free(PlanCtl &c) {
+    dev_free(c.U); dev_free(c.J); dev_free(c.state); dev_free(c.record); dev_free(c.plan); dev_free(c.spread);
+    slab_free(c.slab); slab_free(c.slab_x);
+    mailbox_free(c.box);
+    c.allocated = false;
+}
+
+// The controller's sizes: bytes of its update's slab, doubles behind the record in its mailbox, a spread next to the plan.
+static int plan_alloc(rovmpc_handle *h, PlanCtl &c, size_t slab_bytes, size_t extra_doubles, bool with_spread) {
+    if (c.allocated) return ROVMPC_OK;
+    const size_t K = (size_t)h->cfg.K, C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    hipError_t e = hipSuccess;
+    auto dev = [&e](auto **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void **)p, bytes); };
+    dev(&c.U, K * C3 * h->esz); dev(&c.J, K * h->esz);
+    dev(&c.state, ROVMPC_STATE_LEN * sizeof(double)); dev(&c.record, R * sizeof(double));
+    dev(&c.plan, 2 * C3 * sizeof(double));
+    if (with_spread) dev(&c.spread, 2 * C3 * sizeof(double));
+    int rc = ROVMPC_OK;
+    if (e != hipSuccess) { h->err = std::string(c.name) + " buffers: " + hipGetErrorString(e); rc = ROVMPC_ERR_HIP; }
+    if (!rc) rc = slab_alloc(h, c.slab, slab_bytes);
+    if (!rc) rc = mailbox_alloc(h, c.box, R + extra_doubles);
+    if (rc) plan_free(c);
+    c.allocated = !rc;
+    return rc;
+}
 
 static size_t lds_need(const rovmpc_config *c, int ck, int model, unsigned used = 0xffffffffu, int jit_gi = 0) {
     return c->dtype == ROVMPC_F64 ? rollout_lds_elems<double>(c->N, ck, model, c->vt_mode, used, jit_gi) * sizeof(double)
@@ -435,20 +497,13 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     void *ptrs[] = {h->d_U, h->d_J, h->d_traj_all, h->d_state, h->d_blk_traj,
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
-                    h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
-                    h->d_mppi_U, h->d_mppi_J, h->d_mppi_state, h->d_mppi_record, h->d_mppi_nu, h->d_mppi_slab, h->d_mppi_ticket,
-                    h->d_mppi_slab_x, h->d_mppi_ticket_x,
-                    h->d_cem_U, h->d_cem_J, h->d_cem_state, h->d_cem_record, h->d_cem_mu, h->d_cem_sig, h->d_cem_slab,
-                    h->d_cem_ticket, h->d_cem_slab_x, h->d_cem_ticket_x};
+                    h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
-    if (h->h_record) (void)hipHostFree(h->h_record);
-    if (h->h_done) (void)hipHostFree(h->h_done);
+    mailbox_free(h->samp_box);
     if (h->h_err) (void)hipHostFree(h->h_err);
-    if (h->h_mppi_out) (void)hipHostFree(h->h_mppi_out);
-    if (h->h_mppi_done) (void)hipHostFree(h->h_mppi_done);
-    if (h->h_cem_out) (void)hipHostFree(h->h_cem_out);
-    if (h->h_cem_done) (void)hipHostFree(h->h_cem_done);
+    plan_free(h->mppi);
+    plan_free(h->cem);
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete h->epoch_ctr;
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1048,17 +1103,42 @@ static int take_device_errors(rovmpc_handle *h);
 
 // ---- MPC.step with the candidates drawn on the GPU: one call, no copies on the step path ---------------------------
 static int ensure_sampler(rovmpc_handle *h) {
-    if (h->d_Us[0]) return ROVMPC_OK;
-    const size_t ub = (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, R = (size_t)rovmpc_result_len(h);
-    HIPCHK(h, hipMalloc(&h->d_Us[0], ub));
-    HIPCHK(h, hipMalloc(&h->d_Us[1], ub));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_record, R * sizeof(double), hipHostMallocMapped));
-    HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_record_host, h->h_record, 0));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_done, 64, hipHostMallocMapped));
-    *h->h_done = 0;
-    HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_done, h->h_done, 0));
+    const size_t ub = (size_t)h->cfg.K * h->cfg.N * 3 * h->esz;
+    for (void *&d_U : h->d_Us)
+        if (!d_U) HIPCHK(h, hipMalloc(&d_U, ub));
+    return h->samp_box.d_done ? ROVMPC_OK : mailbox_alloc(h, h->samp_box, (size_t)rovmpc_result_len(h));
+}
+
+// The kernel that ends a step releases `seq` into the mailbox behind its results: spin on the word (a stream synchronise
+// costs several microseconds of wake-up latency); after ~2 s fall back to the blocking call so a failed launch is reported.
+static int mailbox_wait(rovmpc_handle *h, const Mailbox &m, unsigned long long seq, const char *what) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; ++spins) {
+        if (__atomic_load_n(m.h_done, __ATOMIC_ACQUIRE) == seq) return ROVMPC_OK;
+        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (__atomic_load_n(m.h_done, __ATOMIC_ACQUIRE) != seq) FAIL(h, ROVMPC_ERR_HIP, "the %s finished without publishing its record", what);
+            return ROVMPC_OK;
+        }
+    }
+}
+
+static int launched(rovmpc_handle *h, const char *what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
     return ROVMPC_OK;
 }
+
+// kern<T, QC> of an update: T by the handle's dtype, QC = 4 columns per thread where a row is wider than the workgroup
+#define LAUNCH_T_QC(kern, h, wide, ...)                                                                                       \
+    do {                                                                                                                      \
+        if ((h)->cfg.dtype == ROVMPC_F64) { if (wide) hipLaunchKernelGGL((kern<double, 4>), __VA_ARGS__); else hipLaunchKernelGGL((kern<double, 1>), __VA_ARGS__); } \
+        else { if (wide) hipLaunchKernelGGL((kern<float, 4>), __VA_ARGS__); else hipLaunchKernelGGL((kern<float, 1>), __VA_ARGS__); } \
+    } while (0)
+
+// grid of the samplers: 256 threads, four elements of the tensor each
+static const int SAMPLER_NT = 256;
+static int sampler_grid(long long total) { return (int)(((total + 3) / 4 + SAMPLER_NT - 1) / SAMPLER_NT); }
 
 static int launch_sampler(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const double *mean3,
                           const double *std3, int warm, void *d_U, const void *d_Uprev, hipStream_t s, const double *warm_seq = nullptr) {
@@ -1069,13 +1149,10 @@ static int launch_sampler(rovmpc_handle *h, const rovmpc_state *state, uint64_t 
     for (int i = 0; i < 3; ++i) { sa.mean[i] = mean3[i]; sa.std[i] = std3[i]; }
     sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N;
     sa.warm = warm; sa.Uprev = d_Uprev; sa.prev_record = h->d_result; sa.warm_seq = warm_seq;
-    const int bs = 256;
-    const int grid = (int)(((sa.total + 3) / 4 + bs - 1) / bs);
-    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(sample_candidates_kernel<double>, dim3(grid), dim3(bs), 0, s, sa, (double *)d_U);
-    else hipLaunchKernelGGL(sample_candidates_kernel<float>, dim3(grid), dim3(bs), 0, s, sa, (float *)d_U);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "sampler launch failed: %s", hipGetErrorString(e));
-    return ROVMPC_OK;
+    const dim3 grid(sampler_grid(sa.total)), bs(SAMPLER_NT);
+    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(sample_candidates_kernel<double>, grid, bs, 0, s, sa, (double *)d_U);
+    else hipLaunchKernelGGL(sample_candidates_kernel<float>, grid, bs, 0, s, sa, (float *)d_U);
+    return launched(h, "sampler");
 }
 
 extern "C" int rovmpc_sample_candidates_device(rovmpc_handle *h, uint64_t seed, uint64_t step, const double *mean3,
@@ -1109,7 +1186,7 @@ static int fused_sampled_step_t(rovmpc_handle *h, const rovmpc_state *state, uin
     const Geo g = launch_geometry(h, 1);
     fill_args<T>(h, a, h->d_state, nullptr, nullptr, g, 1);
     a.result = h->d_result; a.k_offset = 0; a.slots = nullptr; a.rank = 0; a.world = 1;
-    a.result_host = h->d_record_host; a.done_flag = h->d_done; a.done_seq = seq;
+    a.result_host = h->samp_box.d_out; a.done_flag = h->samp_box.d_done; a.done_seq = seq;
     a.samp_seed = seed; a.samp_step = step;
     for (int i = 0; i < 3; ++i) { a.samp_mean[i] = mean3[i]; a.samp_std[i] = std3[i]; }
     a.samp_warm = warm ? h->d_best + (size_t)(cur ^ 1) * row : nullptr;
@@ -1153,23 +1230,13 @@ extern "C" int rovmpc_mpc_step_sampled(rovmpc_handle *h, const rovmpc_state *sta
     const double *warm_seq = (warm && prev_fused) ? h->d_best + (size_t)(cur ^ 1) * h->cfg.N * 3 : nullptr;
     if ((rc = launch_sampler(h, state, seed, step, mean3, std3, warm, h->d_Us[cur], h->d_Us[cur ^ 1], h->stream, warm_seq))) return rc;
     seq = ++h->samp_steps;
-    h->arg_result_host = h->d_record_host; h->arg_done_flag = h->d_done; h->arg_done_seq = seq;
+    h->arg_result_host = h->samp_box.d_out; h->arg_done_flag = h->samp_box.d_done; h->arg_done_seq = seq;
     rc = enqueue_step(h, h->d_state, h->d_Us[cur], nullptr, h->d_result, 0, nullptr, 0, 1, h->stream);
     h->arg_result_host = nullptr; h->arg_done_flag = nullptr;
     if (rc) return rc;
     }
-    // the sweeper releases `seq` into mapped host memory behind the record: spin on it (a stream synchronise costs
-    // several microseconds of wake-up latency); after ~2 s fall back to the blocking call so a failed launch is reported
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        if (__atomic_load_n(h->h_done, __ATOMIC_ACQUIRE) == seq) break;
-        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (__atomic_load_n(h->h_done, __ATOMIC_ACQUIRE) != seq) FAIL(h, ROVMPC_ERR_HIP, "the step finished without publishing its record");
-            break;
-        }
-    }
-    memcpy(record_out, h->h_record, (size_t)rovmpc_result_len(h) * sizeof(double));
+    if ((rc = mailbox_wait(h, h->samp_box, seq, "step"))) return rc;
+    memcpy(record_out, h->samp_box.h_out, (size_t)rovmpc_result_len(h) * sizeof(double));
     return take_device_errors(h);
 }
 
@@ -1281,6 +1348,92 @@ extern "C" int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state,
     return ROVMPC_OK;
 }
 
+// ---- controllers that iterate on a plan (MPPI, CEM): what their entry points share ----------------------------------------
+// A controller supplies two launches (its sampler and its update) and two sizes (plan_alloc); everything else is here.
+static int check_n_iter(rovmpc_handle *h, int n_iter) {
+    if (n_iter < 1 || n_iter > 64) FAIL(h, ROVMPC_ERR_INVALID, "n_iter must be in 1..64 (got %d)", n_iter);
+    return ROVMPC_OK;
+}
+
+static int check_std3(rovmpc_handle *h, const char *name, const double *v) {
+    for (int i = 0; i < 3; ++i)
+        if (!(isfinite(v[i]) && v[i] >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "%s[%d] must be finite and >= 0 (got %g)", name, i, v[i]);
+    return ROVMPC_OK;
+}
+
+static int check_single_gpu(rovmpc_handle *h, const char *name) {
+    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "%s is single-GPU: not available once rovmpc_comm_init has run", name);
+    return ROVMPC_OK;
+}
+
+// rovmpc_*_reset: the plan goes into half 0 (the spread, where there is one, restarts from std at every step)
+static int plan_reset(rovmpc_handle *h, PlanCtl &c, const double *plan, size_t slab_bytes, size_t extra_doubles, bool with_spread) {
+    int rc;
+    if ((rc = check_single_gpu(h, c.name))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = plan_alloc(h, c, slab_bytes, extra_doubles, with_spread))) return rc;
+    HIPCHK(h, hipMemcpyAsync(c.plan, plan, 3 * (size_t)h->cfg.N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    c.cur = 0;
+    return ROVMPC_OK;
+}
+
+// rovmpc_*_last: host copies of the last iteration's candidates and costs
+static int plan_last(rovmpc_handle *h, PlanCtl &c, void *U_out, void *J_out) {
+    if (c.steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_last: no %s yet", c.abi, c.step_name);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (U_out) HIPCHK(h, hipMemcpy(U_out, c.U, (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
+    if (J_out) HIPCHK(h, hipMemcpy(J_out, c.J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost));
+    return ROVMPC_OK;
+}
+
+// the rollout of rovmpc_step on the controller's tensor, costs into its own buffer
+static int plan_rollout(rovmpc_handle *h, PlanCtl &c) {
+    h->arg_J = c.J;
+    const int rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream);
+    h->arg_J = nullptr;
+    return rc;
+}
+
+// What the loop hands the two launches of iteration i.  The last group is set in the last iteration only (the update then
+// also shifts the plan by one node, passes the rollout's record on and fills the mailbox); *_update_device passes PlanIter{}.
+struct PlanIter {
+    const rovmpc_state *state = nullptr;   // iteration 0 only (the sampler stores it for the step's rollouts)
+    uint64_t counter = 0;                  // of the draw: step * n_iter + i (wraps)
+    size_t in = 0, out = 0;                // offsets of the halves of plan (and spread) the iteration reads and writes
+    int shift = 0;
+    double *record = nullptr, *host_out = nullptr;
+    unsigned long long *done_flag = nullptr, done_seq = 0;
+};
+
+// rovmpc_*_step: n_iter x (sample, rollout, update) on the handle's stream without a host round trip, then one wait for the
+// mailbox.  sample(it) and update(it) launch the controller's kernels.
+template <typename Sample, typename Update>
+static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *state, uint64_t step, int n_iter, Sample sample, Update update) {
+    int rc;
+    if ((rc = check_single_gpu(h, c.name))) return rc;
+    if (!c.allocated) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_step before rovmpc_%s_reset", c.abi, c.abi);
+    if ((rc = check_ready(h))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t C3 = 3 * (size_t)h->cfg.N;
+    const unsigned long long seq = ++c.box.seq;
+    int cur = c.cur;
+    for (int i = 0; i < n_iter; ++i) {
+        PlanIter it;
+        it.state = i == 0 ? state : nullptr; it.counter = step * (uint64_t)n_iter + (uint64_t)i;
+        it.in = cur * C3; it.out = (cur ^ 1) * C3; it.done_seq = seq;
+        if (i + 1 == n_iter) { it.shift = 1; it.record = c.record; it.host_out = c.box.d_out; it.done_flag = c.box.d_done; }
+        if ((rc = sample(it))) return rc;
+        if ((rc = plan_rollout(h, c))) return rc;
+        if ((rc = update(it))) return rc;
+        cur ^= 1;
+    }
+    c.cur = cur;
+    ++c.steps;
+    return mailbox_wait(h, c.box, seq, c.step_name);
+}
+
 // ---- MPPI: sampling around a warm-started nominal, exp(-J/lambda)-weighted update on the GPU -------------------------
 struct MppiGeo { int G; long long slice; };
 static MppiGeo mppi_geometry(long long K) {
@@ -1294,87 +1447,47 @@ static int mppi_check_params(rovmpc_handle *h, const rovmpc_mppi_params *p) {
     if (!p) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step: null params");
     if (p->struct_size != (int32_t)sizeof(rovmpc_mppi_params))
         FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_params.struct_size %d != %d (ABI mismatch)", p->struct_size, (int)sizeof(rovmpc_mppi_params));
-    if (p->n_iter < 1 || p->n_iter > 64) FAIL(h, ROVMPC_ERR_INVALID, "n_iter must be in 1..64 (got %d)", p->n_iter);
+    int rc = check_n_iter(h, p->n_iter);
+    if (rc) return rc;
     if (!(isfinite(p->lambda) && p->lambda > 0)) FAIL(h, ROVMPC_ERR_INVALID, "lambda must be finite and > 0 (got %g)", p->lambda);
-    for (int i = 0; i < 3; ++i)
-        if (!(isfinite(p->std[i]) && p->std[i] >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "std[%d] must be finite and >= 0 (got %g)", i, p->std[i]);
-    return ROVMPC_OK;
+    return check_std3(h, "std", p->std);
 }
 
-// slab [G][3 + 3N] and its ticket word (zeroed once: the last workgroup of every launch re-arms it)
-static int mppi_alloc_slab(rovmpc_handle *h, double **slab, unsigned **ticket) {
-    const MppiGeo g = mppi_geometry(h->cfg.K);
-    HIPCHK(h, hipMalloc((void **)slab, (size_t)g.G * (3 + 3 * (size_t)h->cfg.N) * sizeof(double)));
-    HIPCHK(h, hipMalloc((void **)ticket, 16));
-    HIPCHK(h, hipMemset(*ticket, 0, 16));
-    return ROVMPC_OK;
+// slab [G][3 + 3N]
+static size_t mppi_slab_bytes(const rovmpc_handle *h) {
+    return (size_t)mppi_geometry(h->cfg.K).G * (3 + 3 * (size_t)h->cfg.N) * sizeof(double);
 }
 
 static int launch_mppi_update(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda, const double *nu_in, double *nu_out,
-                              int shift, double *stats, double *slab, unsigned *ticket, double *record, double *host_out,
-                              unsigned long long *done_flag, unsigned long long done_seq, hipStream_t s) {
+                              double *stats, const Slab &slab, const PlanIter &pub, hipStream_t s) {
     const MppiGeo g = mppi_geometry(h->cfg.K);
     MppiUpdateArgs a;
     memset(&a, 0, sizeof(a));
     a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.lambda = lambda;
-    a.nu_in = nu_in; a.nu_out = nu_out; a.shift = shift; a.stats = stats; a.slab = slab; a.ticket = ticket;
-    a.record = record; a.R = rovmpc_result_len(h); a.host_out = host_out; a.done_flag = done_flag; a.done_seq = done_seq;
-    const bool wide = a.C3 > MPPI_NT;
-    if (h->cfg.dtype == ROVMPC_F64) {
-        if (wide) hipLaunchKernelGGL((mppi_update_kernel<double, 4>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
-        else hipLaunchKernelGGL((mppi_update_kernel<double, 1>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
-    } else {
-        if (wide) hipLaunchKernelGGL((mppi_update_kernel<float, 4>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
-        else hipLaunchKernelGGL((mppi_update_kernel<float, 1>), dim3(g.G), dim3(MPPI_NT), 0, s, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "MPPI update launch failed: %s", hipGetErrorString(e));
-    return ROVMPC_OK;
+    a.nu_in = nu_in; a.nu_out = nu_out; a.shift = pub.shift; a.stats = stats; a.slab = (double *)slab.rows; a.ticket = slab.ticket;
+    a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
+    LAUNCH_T_QC(mppi_update_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
+    return launched(h, "MPPI update");
 }
 
 extern "C" int rovmpc_mppi_reset(rovmpc_handle *h, const double *nominal) {
     if (!h) return ROVMPC_ERR_INVALID;
     if (!nominal) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_reset: null nominal");
-    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "MPPI is single-GPU: not available once rovmpc_comm_init has run");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const rovmpc_config &c = h->cfg;
-    const size_t C3 = 3 * (size_t)c.N;
-    if (!h->d_mppi_nu) {
-        const size_t R = (size_t)rovmpc_result_len(h);
-        HIPCHK(h, hipMalloc(&h->d_mppi_U, (size_t)c.K * C3 * h->esz));
-        HIPCHK(h, hipMalloc(&h->d_mppi_J, (size_t)c.K * h->esz));
-        HIPCHK(h, hipMalloc((void **)&h->d_mppi_state, ROVMPC_STATE_LEN * sizeof(double)));
-        HIPCHK(h, hipMalloc((void **)&h->d_mppi_record, R * sizeof(double)));
-        int rc = mppi_alloc_slab(h, &h->d_mppi_slab, &h->d_mppi_ticket);
-        if (rc) return rc;
-        HIPCHK(h, hipHostMalloc((void **)&h->h_mppi_out, (R + C3 + 4) * sizeof(double), hipHostMallocMapped));
-        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_mppi_out, h->h_mppi_out, 0));
-        HIPCHK(h, hipHostMalloc((void **)&h->h_mppi_done, 64, hipHostMallocMapped));
-        *h->h_mppi_done = 0;
-        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_mppi_done, h->h_mppi_done, 0));
-        HIPCHK(h, hipMalloc((void **)&h->d_mppi_nu, 2 * C3 * sizeof(double)));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_mppi_nu, nominal, C3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->mppi_cur = 0;
-    return ROVMPC_OK;
+    return plan_reset(h, h->mppi, nominal, mppi_slab_bytes(h), 3 * (size_t)h->cfg.N + 4, false);   // mailbox: record, nu*, stats
 }
 
-template <typename T>
 static int launch_mppi_sample(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t counter, const double *std3,
                               const double *nu) {
     MppiSampleArgs sa;
     memset(&sa, 0, sizeof(sa));
-    if (state) { sa.state = *state; sa.d_state = h->d_mppi_state; }
+    if (state) { sa.state = *state; sa.d_state = h->mppi.state; }
     sa.seed = seed; sa.counter = counter;
     for (int i = 0; i < 3; ++i) sa.std[i] = std3[i];
     sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.nu = nu;
-    const int bs = 256;
-    const int grid = (int)(((sa.total + 3) / 4 + bs - 1) / bs);
-    hipLaunchKernelGGL(mppi_sample_kernel<T>, dim3(grid), dim3(bs), 0, h->stream, sa, (T *)h->d_mppi_U);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "MPPI sampler launch failed: %s", hipGetErrorString(e));
-    return ROVMPC_OK;
+    const dim3 grid(sampler_grid(sa.total)), bs(SAMPLER_NT);
+    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(mppi_sample_kernel<double>, grid, bs, 0, h->stream, sa, (double *)h->mppi.U);
+    else hipLaunchKernelGGL(mppi_sample_kernel<float>, grid, bs, 0, h->stream, sa, (float *)h->mppi.U);
+    return launched(h, "MPPI sampler");
 }
 
 extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step,
@@ -1383,58 +1496,23 @@ extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uin
     if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step: null pointer");
     int rc = mppi_check_params(h, p);
     if (rc) return rc;
-    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "MPPI is single-GPU: not available once rovmpc_comm_init has run");
-    if (!h->d_mppi_nu) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step before rovmpc_mppi_reset");
-    if ((rc = check_ready(h))) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
+    PlanCtl &c = h->mppi;
+    rc = plan_step(h, c, state, step, p->n_iter,
+                   [&](const PlanIter &it) { return launch_mppi_sample(h, it.state, seed, it.counter, p->std, c.plan + it.in); },
+                   [&](const PlanIter &it) {
+                       return launch_mppi_update(h, c.J, c.U, p->lambda, c.plan + it.in, c.plan + it.out, nullptr, c.slab, it, h->stream);
+                   });
+    if (rc) return rc;
     const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    const unsigned long long seq = ++h->mppi_seq;
-    int cur = h->mppi_cur;
-    for (int i = 0; i < p->n_iter; ++i) {
-        const bool last = i + 1 == p->n_iter;
-        const uint64_t counter = step * (uint64_t)p->n_iter + (uint64_t)i;        // wraps
-        const double *nu_in = h->d_mppi_nu + cur * C3;
-        double *nu_out = h->d_mppi_nu + (cur ^ 1) * C3;
-        rc = h->cfg.dtype == ROVMPC_F64 ? launch_mppi_sample<double>(h, i == 0 ? state : nullptr, seed, counter, p->std, nu_in)
-                                        : launch_mppi_sample<float>(h, i == 0 ? state : nullptr, seed, counter, p->std, nu_in);
-        if (rc) return rc;
-        // the rollout of rovmpc_step on this tensor, costs into MPPI's own buffer
-        h->arg_J = h->d_mppi_J;
-        rc = enqueue_step(h, h->d_mppi_state, h->d_mppi_U, nullptr, h->d_mppi_record, 0, nullptr, 0, 1, h->stream);
-        h->arg_J = nullptr;
-        if (rc) return rc;
-        rc = launch_mppi_update(h, h->d_mppi_J, h->d_mppi_U, p->lambda, nu_in, nu_out, last ? 1 : 0, nullptr, h->d_mppi_slab,
-                                h->d_mppi_ticket, last ? h->d_mppi_record : nullptr, last ? h->d_mppi_out : nullptr,
-                                last ? h->d_mppi_done : nullptr, seq, h->stream);
-        if (rc) return rc;
-        cur ^= 1;
-    }
-    h->mppi_cur = cur;
-    ++h->mppi_steps;
-    // the last update releases `seq` behind the record in mapped host memory: spin on it, as rovmpc_mpc_step_sampled does
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        if (__atomic_load_n(h->h_mppi_done, __ATOMIC_ACQUIRE) == seq) break;
-        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (__atomic_load_n(h->h_mppi_done, __ATOMIC_ACQUIRE) != seq) FAIL(h, ROVMPC_ERR_HIP, "the MPPI step finished without publishing its record");
-            break;
-        }
-    }
-    memcpy(record_out, h->h_mppi_out, R * sizeof(double));
-    if (nominal_out) memcpy(nominal_out, h->h_mppi_out + R, C3 * sizeof(double));
-    if (stats_out) memcpy(stats_out, h->h_mppi_out + R + C3, 4 * sizeof(double));
+    const double *o = c.box.h_out;
+    memcpy(record_out, o, R * sizeof(double));
+    if (nominal_out) memcpy(nominal_out, o + R, C3 * sizeof(double));
+    if (stats_out) memcpy(stats_out, o + R + C3, 4 * sizeof(double));
     return take_device_errors(h);
 }
 
 extern "C" int rovmpc_mppi_last(rovmpc_handle *h, void *U_out, void *J_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (h->mppi_steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_last: no MPPI step yet");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (U_out) HIPCHK(h, hipMemcpy(U_out, h->d_mppi_U, (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
-    if (J_out) HIPCHK(h, hipMemcpy(J_out, h->d_mppi_J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost));
-    return ROVMPC_OK;
+    return h ? plan_last(h, h->mppi, U_out, J_out) : ROVMPC_ERR_INVALID;
 }
 
 extern "C" int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda,
@@ -1443,12 +1521,9 @@ extern "C" int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, cons
     if (!d_J || !d_U || !d_nominal_in || !d_nominal_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_update_device: null pointer");
     if (!(isfinite(lambda) && lambda > 0)) FAIL(h, ROVMPC_ERR_INVALID, "lambda must be finite and > 0 (got %g)", lambda);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->d_mppi_slab_x) {
-        int rc = mppi_alloc_slab(h, &h->d_mppi_slab_x, &h->d_mppi_ticket_x);
-        if (rc) return rc;
-    }
-    return launch_mppi_update(h, d_J, d_U, lambda, d_nominal_in, d_nominal_out, 0, d_stats, h->d_mppi_slab_x, h->d_mppi_ticket_x,
-                              nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+    int rc = slab_alloc(h, h->mppi.slab_x, mppi_slab_bytes(h));
+    if (rc) return rc;
+    return launch_mppi_update(h, d_J, d_U, lambda, d_nominal_in, d_nominal_out, d_stats, h->mppi.slab_x, PlanIter{}, (hipStream_t)stream);
 }
 
 // ---- CEM: clamped sampling around a per-node mean and spread, exact elite selection and refit on the GPU ---------------
@@ -1462,103 +1537,61 @@ static int cem_check_params(rovmpc_handle *h, const rovmpc_cem_params *p) {
     if (!p) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem: null params");
     if (p->struct_size != (int32_t)sizeof(rovmpc_cem_params))
         FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_params.struct_size %d != %d (ABI mismatch)", p->struct_size, (int)sizeof(rovmpc_cem_params));
-    if (p->n_iter < 1 || p->n_iter > 64) FAIL(h, ROVMPC_ERR_INVALID, "n_iter must be in 1..64 (got %d)", p->n_iter);
+    int rc = check_n_iter(h, p->n_iter);
+    if (rc) return rc;
     const int emax = h->cfg.K < CEM_MAX_ELITE ? h->cfg.K : CEM_MAX_ELITE;
     if (p->n_elite < 1 || p->n_elite > emax) FAIL(h, ROVMPC_ERR_INVALID, "n_elite must be in 1..%d = min(K, %d) (got %d)", emax, CEM_MAX_ELITE, p->n_elite);
     if (p->reserved != 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_params.reserved must be 0 (got %d)", p->reserved);
     if (!(isfinite(p->alpha) && p->alpha >= 0 && p->alpha < 1)) FAIL(h, ROVMPC_ERR_INVALID, "alpha must be finite, 0 <= alpha < 1 (got %g)", p->alpha);
-    for (int i = 0; i < 3; ++i) {
-        if (!(isfinite(p->std[i]) && p->std[i] >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "std[%d] must be finite and >= 0 (got %g)", i, p->std[i]);
-        if (!(isfinite(p->std_min[i]) && p->std_min[i] >= 0))
-            FAIL(h, ROVMPC_ERR_INVALID, "std_min[%d] must be finite and >= 0 (got %g)", i, p->std_min[i]);
+    if ((rc = check_std3(h, "std", p->std)) || (rc = check_std3(h, "std_min", p->std_min))) return rc;
+    for (int i = 0; i < 3; ++i)
         if (isnan(p->lo[i]) || isnan(p->hi[i]) || !(p->lo[i] <= p->hi[i]))
             FAIL(h, ROVMPC_ERR_INVALID, "bounds of channel %d must not be NaN and lo <= hi (got %g, %g)", i, p->lo[i], p->hi[i]);
-    }
     return ROVMPC_OK;
 }
 
-// slab [G][2 + 2 Lcap] (only when the update has several workgroups) and its ticket word (zeroed once: the last workgroup of
-// every launch re-arms it)
-static int cem_alloc_slab(rovmpc_handle *h, unsigned long long **slab, unsigned **ticket) {
+// slab [G][2 + 2 Lcap], only when the update has several workgroups
+static size_t cem_slab_bytes(const rovmpc_handle *h) {
     const CemGeo g = cem_geometry(h->cfg.K);
-    if (g.G > 1) HIPCHK(h, hipMalloc((void **)slab, (size_t)g.G * (2 + 2 * (size_t)g.Lcap) * sizeof(unsigned long long)));
-    HIPCHK(h, hipMalloc((void **)ticket, 16));
-    HIPCHK(h, hipMemset(*ticket, 0, 16));
-    return ROVMPC_OK;
+    return g.G > 1 ? (size_t)g.G * (2 + 2 * (size_t)g.Lcap) * sizeof(unsigned long long) : 0;
 }
 
 static int launch_cem_update(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p, const double *mu_in,
-                             const double *sigma_in, double *mu_out, double *sigma_out, int shift, long long *elite, double *stats,
-                             unsigned long long *slab, unsigned *ticket, double *record, double *host_out, long long *host_elite,
-                             unsigned long long *done_flag, unsigned long long done_seq, hipStream_t s) {
+                             const double *sigma_in, double *mu_out, double *sigma_out, long long *elite, double *stats,
+                             const Slab &slab, const PlanIter &pub, long long *host_elite, hipStream_t s) {
     const CemGeo g = cem_geometry(h->cfg.K);
     CemUpdateArgs a;
     memset(&a, 0, sizeof(a));
     a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.E = p->n_elite; a.Lcap = g.Lcap;
     a.alpha = p->alpha;
     for (int i = 0; i < 3; ++i) { a.std[i] = p->std[i]; a.std_min[i] = p->std_min[i]; a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
-    a.mu_in = mu_in; a.sigma_in = sigma_in; a.mu_out = mu_out; a.sigma_out = sigma_out; a.shift = shift;
-    a.elite = elite; a.stats = stats; a.slab = slab; a.ticket = ticket;
-    a.record = record; a.R = rovmpc_result_len(h); a.host_out = host_out; a.host_elite = host_elite;
-    a.done_flag = done_flag; a.done_seq = done_seq;
-    const bool wide = a.C3 > CEM_NT;
-    if (h->cfg.dtype == ROVMPC_F64) {
-        if (wide) hipLaunchKernelGGL((cem_update_kernel<double, 4>), dim3(g.G), dim3(CEM_NT), 0, s, a);
-        else hipLaunchKernelGGL((cem_update_kernel<double, 1>), dim3(g.G), dim3(CEM_NT), 0, s, a);
-    } else {
-        if (wide) hipLaunchKernelGGL((cem_update_kernel<float, 4>), dim3(g.G), dim3(CEM_NT), 0, s, a);
-        else hipLaunchKernelGGL((cem_update_kernel<float, 1>), dim3(g.G), dim3(CEM_NT), 0, s, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "CEM update launch failed: %s", hipGetErrorString(e));
-    return ROVMPC_OK;
+    a.mu_in = mu_in; a.sigma_in = sigma_in; a.mu_out = mu_out; a.sigma_out = sigma_out; a.shift = pub.shift;
+    a.elite = elite; a.stats = stats; a.slab = (unsigned long long *)slab.rows; a.ticket = slab.ticket;
+    a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.host_elite = host_elite;
+    a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
+    LAUNCH_T_QC(cem_update_kernel, h, a.C3 > CEM_NT, dim3(g.G), dim3(CEM_NT), 0, s, a);
+    return launched(h, "CEM update");
 }
 
 extern "C" int rovmpc_cem_reset(rovmpc_handle *h, const double *mean) {
     if (!h) return ROVMPC_ERR_INVALID;
     if (!mean) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_reset: null mean");
-    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "CEM is single-GPU: not available once rovmpc_comm_init has run");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const rovmpc_config &c = h->cfg;
-    const size_t C3 = 3 * (size_t)c.N;
-    if (!h->d_cem_mu) {
-        const size_t R = (size_t)rovmpc_result_len(h);
-        HIPCHK(h, hipMalloc(&h->d_cem_U, (size_t)c.K * C3 * h->esz));
-        HIPCHK(h, hipMalloc(&h->d_cem_J, (size_t)c.K * h->esz));
-        HIPCHK(h, hipMalloc((void **)&h->d_cem_state, ROVMPC_STATE_LEN * sizeof(double)));
-        HIPCHK(h, hipMalloc((void **)&h->d_cem_record, R * sizeof(double)));
-        int rc = cem_alloc_slab(h, &h->d_cem_slab, &h->d_cem_ticket);
-        if (rc) return rc;
-        // [record (R), mu* (3N), sigma* (3N), stats (4)] then the elite list (int64 [CEM_MAX_ELITE])
-        HIPCHK(h, hipHostMalloc((void **)&h->h_cem_out, (R + 2 * C3 + 4 + CEM_MAX_ELITE) * sizeof(double), hipHostMallocMapped));
-        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_cem_out, h->h_cem_out, 0));
-        HIPCHK(h, hipHostMalloc((void **)&h->h_cem_done, 64, hipHostMallocMapped));
-        *h->h_cem_done = 0;
-        HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_cem_done, h->h_cem_done, 0));
-        HIPCHK(h, hipMalloc((void **)&h->d_cem_sig, 2 * C3 * sizeof(double)));
-        HIPCHK(h, hipMalloc((void **)&h->d_cem_mu, 2 * C3 * sizeof(double)));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_cem_mu, mean, C3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->cem_cur = 0;
-    return ROVMPC_OK;
+    // mailbox: record, mu* (3N), sigma* (3N), stats (4), then the elite list (int64 [CEM_MAX_ELITE])
+    return plan_reset(h, h->cem, mean, cem_slab_bytes(h), 6 * (size_t)h->cfg.N + 4 + CEM_MAX_ELITE, true);
 }
 
-template <typename T>
 static int launch_cem_sample(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t counter, const rovmpc_cem_params *p,
                              const double *mu, const double *sigma) {
     CemSampleArgs sa;
     memset(&sa, 0, sizeof(sa));
-    if (state) { sa.state = *state; sa.d_state = h->d_cem_state; }
+    if (state) { sa.state = *state; sa.d_state = h->cem.state; }
     sa.seed = seed; sa.counter = counter;
     for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
     sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.mu = mu; sa.sigma = sigma;
-    const int bs = 256;
-    const int grid = (int)(((sa.total + 3) / 4 + bs - 1) / bs);
-    hipLaunchKernelGGL(cem_sample_kernel<T>, dim3(grid), dim3(bs), 0, h->stream, sa, (T *)h->d_cem_U);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "CEM sampler launch failed: %s", hipGetErrorString(e));
-    return ROVMPC_OK;
+    const dim3 grid(sampler_grid(sa.total)), bs(SAMPLER_NT);
+    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(cem_sample_kernel<double>, grid, bs, 0, h->stream, sa, (double *)h->cem.U);
+    else hipLaunchKernelGGL(cem_sample_kernel<float>, grid, bs, 0, h->stream, sa, (float *)h->cem.U);
+    return launched(h, "CEM sampler");
 }
 
 extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const rovmpc_cem_params *p,
@@ -1567,46 +1600,19 @@ extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint
     if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_step: null pointer");
     int rc = cem_check_params(h, p);
     if (rc) return rc;
-    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "CEM is single-GPU: not available once rovmpc_comm_init has run");
-    if (!h->d_cem_mu) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_step before rovmpc_cem_reset");
-    if ((rc = check_ready(h))) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
+    PlanCtl &c = h->cem;
     const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    const unsigned long long seq = ++h->cem_seq;
-    int cur = h->cem_cur;
-    for (int i = 0; i < p->n_iter; ++i) {
-        const bool last = i + 1 == p->n_iter;
-        const uint64_t counter = step * (uint64_t)p->n_iter + (uint64_t)i;        // wraps
-        const double *mu_in = h->d_cem_mu + cur * C3, *sig_in = i == 0 ? nullptr : h->d_cem_sig + cur * C3;   // sigma_0 = std
-        double *mu_out = h->d_cem_mu + (cur ^ 1) * C3, *sig_out = h->d_cem_sig + (cur ^ 1) * C3;
-        rc = h->cfg.dtype == ROVMPC_F64 ? launch_cem_sample<double>(h, i == 0 ? state : nullptr, seed, counter, p, mu_in, sig_in)
-                                        : launch_cem_sample<float>(h, i == 0 ? state : nullptr, seed, counter, p, mu_in, sig_in);
-        if (rc) return rc;
-        // the rollout of rovmpc_step on this tensor, costs into CEM's own buffer
-        h->arg_J = h->d_cem_J;
-        rc = enqueue_step(h, h->d_cem_state, h->d_cem_U, nullptr, h->d_cem_record, 0, nullptr, 0, 1, h->stream);
-        h->arg_J = nullptr;
-        if (rc) return rc;
-        rc = launch_cem_update(h, h->d_cem_J, h->d_cem_U, p, mu_in, sig_in, mu_out, sig_out, last ? 1 : 0, nullptr, nullptr,
-                               h->d_cem_slab, h->d_cem_ticket, last ? h->d_cem_record : nullptr, last ? h->d_cem_out : nullptr,
-                               last ? (long long *)(h->d_cem_out + R + 2 * C3 + 4) : nullptr, last ? h->d_cem_done : nullptr,
-                               seq, h->stream);
-        if (rc) return rc;
-        cur ^= 1;
-    }
-    h->cem_cur = cur;
-    ++h->cem_steps;
-    // the last update releases `seq` behind the record in mapped host memory: spin on it, as rovmpc_mppi_step does
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        if (__atomic_load_n(h->h_cem_done, __ATOMIC_ACQUIRE) == seq) break;
-        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (__atomic_load_n(h->h_cem_done, __ATOMIC_ACQUIRE) != seq) FAIL(h, ROVMPC_ERR_HIP, "the CEM step finished without publishing its record");
-            break;
-        }
-    }
-    const double *o = h->h_cem_out;
+    rc = plan_step(h, c, state, step, p->n_iter,
+                   [&](const PlanIter &it) {                                   // sigma_0 = std
+                       return launch_cem_sample(h, it.state, seed, it.counter, p, c.plan + it.in, it.state ? nullptr : c.spread + it.in);
+                   },
+                   [&](const PlanIter &it) {
+                       return launch_cem_update(h, c.J, c.U, p, c.plan + it.in, it.state ? nullptr : c.spread + it.in, c.plan + it.out,
+                                                c.spread + it.out, nullptr, nullptr, c.slab, it,
+                                                it.host_out ? (long long *)(it.host_out + R + 2 * C3 + 4) : nullptr, h->stream);
+                   });
+    if (rc) return rc;
+    const double *o = c.box.h_out;
     memcpy(record_out, o, R * sizeof(double));
     if (mean_out) memcpy(mean_out, o + R, C3 * sizeof(double));
     if (std_out) memcpy(std_out, o + R + C3, C3 * sizeof(double));
@@ -1616,13 +1622,7 @@ extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint
 }
 
 extern "C" int rovmpc_cem_last(rovmpc_handle *h, void *U_out, void *J_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (h->cem_steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_last: no CEM step yet");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (U_out) HIPCHK(h, hipMemcpy(U_out, h->d_cem_U, (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
-    if (J_out) HIPCHK(h, hipMemcpy(J_out, h->d_cem_J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost));
-    return ROVMPC_OK;
+    return h ? plan_last(h, h->cem, U_out, J_out) : ROVMPC_ERR_INVALID;
 }
 
 extern "C" int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p,
@@ -1634,12 +1634,9 @@ extern "C" int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const
     int rc = cem_check_params(h, p);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->d_cem_ticket_x) {
-        rc = cem_alloc_slab(h, &h->d_cem_slab_x, &h->d_cem_ticket_x);
-        if (rc) return rc;
-    }
-    return launch_cem_update(h, d_J, d_U, p, d_mean_in, d_std_in, d_mean_out, d_std_out, 0, (long long *)d_elite_out, d_stats,
-                             h->d_cem_slab_x, h->d_cem_ticket_x, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+    if ((rc = slab_alloc(h, h->cem.slab_x, cem_slab_bytes(h)))) return rc;
+    return launch_cem_update(h, d_J, d_U, p, d_mean_in, d_std_in, d_mean_out, d_std_out, (long long *)d_elite_out, d_stats,
+                             h->cem.slab_x, PlanIter{}, nullptr, (hipStream_t)stream);
 }
 
 // ---- timing ---------------------------------------------------------------------------------

@@ -134,6 +134,10 @@ class StepResult:
     cost: float
     index: int
 
+    @classmethod
+    def from_record(cls, rec: np.ndarray, N: int) -> "StepResult":      # rec = [J*, k*, u(3), (theta, gamma)_0..N]
+        return cls(rec[2:5].copy(), rec[5:].reshape(N + 1, 2).copy(), float(rec[0]), int(rec[1]))
+
 
 class Engine:
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, **overrides):
@@ -236,13 +240,21 @@ class Engine:
             self._check(rc)
         return sp["rec"]
 
-    # -- MPPI (rovmpc_mppi_*) -----------------------------------------------------------------
+    # -- MPPI (rovmpc_mppi_*) and CEM (rovmpc_cem_*) -----------------------------------------------
+    def _plan_reset(self, fn, plan, name: str):
+        plan = np.ascontiguousarray(plan, dtype=np.float64)
+        if plan.shape != (self.cfg.N, 3):
+            raise ValueError(f"{name} must have shape ({self.cfg.N}, 3), got {plan.shape}")
+        self._check(fn(self._h, _ptr(plan)))
+
+    def _plan_last(self, fn):
+        U, J = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype), np.empty(self.cfg.K, dtype=self.cfg.np_dtype)
+        self._check(fn(self._h, _ptr(U), _ptr(J)))
+        return U, J
+
     def mppi_reset(self, nominal):
         """Set the handle's MPPI nominal plan (N, 3); allocates the MPPI buffers on first use."""
-        nu = np.ascontiguousarray(nominal, dtype=np.float64)
-        if nu.shape != (self.cfg.N, 3):
-            raise ValueError(f"nominal must have shape ({self.cfg.N}, 3), got {nu.shape}")
-        self._check(self.lib.rovmpc_mppi_reset(self._h, _ptr(nu)))
+        self._plan_reset(self.lib.rovmpc_mppi_reset, nominal, "nominal")
 
     def mppi_step(self, state, seed: int, step: int, params: MPPIParams):
         """One MPPI control step: returns (record [J*, k*, u(3), traj], nu* (N, 3), stats (rho, eta, ESS, J_0))."""
@@ -256,10 +268,7 @@ class Engine:
 
     def mppi_last(self):
         """Host copies of the last MPPI iteration's candidates U (K, N, 3) and costs J (K,)."""
-        U = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)
-        J = np.empty(self.cfg.K, dtype=self.cfg.np_dtype)
-        self._check(self.lib.rovmpc_mppi_last(self._h, _ptr(U), _ptr(J)))
-        return U, J
+        return self._plan_last(self.lib.rovmpc_mppi_last)
 
     def mppi_update_device(self, d_J: int, d_U: int, lam: float, d_nominal_in: int, d_nominal_out: int, d_stats: int = 0,
                            stream: int = 0):
@@ -267,13 +276,9 @@ class Engine:
         self._check(self.lib.rovmpc_mppi_update_device(self._h, d_J, d_U, float(lam), d_nominal_in, d_nominal_out,
                                                        d_stats or None, stream))
 
-    # -- CEM (rovmpc_cem_*) ------------------------------------------------------------------
     def cem_reset(self, mean):
         """Set the handle's CEM mean (N, 3); allocates the CEM buffers on first use."""
-        mu = np.ascontiguousarray(mean, dtype=np.float64)
-        if mu.shape != (self.cfg.N, 3):
-            raise ValueError(f"mean must have shape ({self.cfg.N}, 3), got {mu.shape}")
-        self._check(self.lib.rovmpc_cem_reset(self._h, _ptr(mu)))
+        self._plan_reset(self.lib.rovmpc_cem_reset, mean, "mean")
 
     def cem_step(self, state, seed: int, step: int, params: CEMParams):
         """One CEM control step: returns (record [J*, k*, u(3), traj], mu* (N, 3), sigma* (N, 3), elites (n_elite,) int64,
@@ -289,10 +294,7 @@ class Engine:
 
     def cem_last(self):
         """Host copies of the last CEM iteration's candidates U (K, N, 3) and costs J (K,)."""
-        U = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)
-        J = np.empty(self.cfg.K, dtype=self.cfg.np_dtype)
-        self._check(self.lib.rovmpc_cem_last(self._h, _ptr(U), _ptr(J)))
-        return U, J
+        return self._plan_last(self.lib.rovmpc_cem_last)
 
     def cem_update_device(self, d_J: int, d_U: int, params: CEMParams, d_mean_in: int, d_std_in: int, d_mean_out: int,
                           d_std_out: int, d_elite_out: int = 0, d_stats: int = 0, stream: int = 0):
@@ -512,7 +514,6 @@ class Engine:
         out = np.empty_like(v)
         self._check(self.lib.rovmpc_velocity_transform(self._h, _ptr(R), _ptr(v), v.shape[0], _ptr(out)))
         return out
-
 
     def extract_features(self, P0, P1, V1, time, theta, gamma, with_prev: bool = True) -> np.ndarray:
         c = lambda x, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), shape))

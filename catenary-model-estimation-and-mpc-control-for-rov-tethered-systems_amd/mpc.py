@@ -71,8 +71,7 @@ class MPC:
         d = self._dev
         rec = self.engine.mpc_step_sampled(state, d.seed, d.step, d.mean, d.std, self.warm_start)
         d.step += 1
-        N = self.cfg.N
-        self.last = StepResult(rec[2:5].copy(), rec[5:].reshape(N + 1, 2).copy(), float(rec[0]), int(rec[1]))
+        self.last = StepResult.from_record(rec, self.cfg.N)
         return self.last.u
 
     def step(self, state, U: Optional[np.ndarray] = None) -> np.ndarray:
@@ -95,7 +94,40 @@ class MPC:
         self.engine.close()
 
 
-class MPPI:
+class _PlanController:
+    """What MPPI and CEM share: an engine of their own, the seed and step counter of the draws, the plan's shape and the
+    result of the last step."""
+
+    def __init__(self, cfg, model, seed: int, overrides: dict):
+        self.seed = int(seed)
+        self.engine = Engine(cfg, model, **overrides)
+        self.cfg = self.engine.cfg
+        self._default_mean = np.asarray(default_model().mean[3:6], dtype=np.float64)
+        self.step_count = 0
+        self.last: Optional[StepResult] = None
+        self.last_stats: Optional[dict] = None
+
+    def _plan(self, value, name: str) -> np.ndarray:
+        """(N, 3) from (N, 3), from (3,) repeated on every node, or from None (the scaler mean of x3..x5)."""
+        N = self.cfg.N
+        plan = self._default_mean if value is None else np.asarray(value, dtype=np.float64)
+        if plan.shape == (3,):
+            plan = np.tile(plan, (N, 1))
+        if plan.shape != (N, 3):
+            raise ValueError(f"{name} must have shape ({N}, 3) or (3,), got {plan.shape}")
+        return plan
+
+    def _took_step(self, rec, stats: dict) -> np.ndarray:
+        self.step_count += 1
+        self.last = StepResult.from_record(rec, self.cfg.N)
+        self.last_stats = stats
+        return self.last.u
+
+    def close(self):
+        self.engine.close()
+
+
+class MPPI(_PlanController):
     """``mppi = MPPI(N=20, K=4096, lam=1.0); u = mppi.step(state)``: model-predictive path integral control.
 
     The handle keeps a nominal plan (N, 3); each step samples K candidates around it on the GPU (candidate 0 = the nominal),
@@ -107,45 +139,25 @@ class MPPI:
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, lam: float = 1.0, std=None,
                  n_iter: int = 1, seed: int = 20250523, nominal=None, **overrides):
-        m = default_model()
-        self.std = np.asarray(std if std is not None else m.scale[3:6], dtype=np.float64)
+        self.std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
         self.params = _lib.MPPIParams.make(n_iter, lam, self.std)        # ValueError before the library is called
         self.lam, self.n_iter = float(lam), int(n_iter)
-        self.seed = int(seed)
-        self.engine = Engine(cfg, model, **overrides)
-        self.cfg = self.engine.cfg
-        self._default_mean = np.asarray(m.mean[3:6], dtype=np.float64)
-        self.step_count = 0
-        self.last: Optional[StepResult] = None
-        self.last_stats: Optional[dict] = None
+        super().__init__(cfg, model, seed, overrides)
         self.nominal: Optional[np.ndarray] = None
         self.reset(nominal)
 
     def reset(self, nominal=None):
         """Set the nominal plan ((N, 3), or (3,) repeated on every node; default: the scaler mean of x3..x5)."""
-        N = self.cfg.N
-        nu = self._default_mean if nominal is None else np.asarray(nominal, dtype=np.float64)
-        if nu.shape == (3,):
-            nu = np.tile(nu, (N, 1))
-        if nu.shape != (N, 3):
-            raise ValueError(f"nominal must have shape ({N}, 3) or (3,), got {nu.shape}")
+        nu = self._plan(nominal, "nominal")
         self.engine.mppi_reset(nu)
         self.nominal = nu.copy()
 
     def step(self, state) -> np.ndarray:
-        rec, nu, stats = self.engine.mppi_step(state, self.seed, self.step_count, self.params)
-        self.step_count += 1
-        N = self.cfg.N
-        self.last = StepResult(rec[2:5].copy(), rec[5:].reshape(N + 1, 2).copy(), float(rec[0]), int(rec[1]))
-        self.last_stats = {"rho": float(stats[0]), "eta": float(stats[1]), "ess": float(stats[2]), "J0": float(stats[3])}
-        self.nominal = nu
-        return self.last.u
-
-    def close(self):
-        self.engine.close()
+        rec, self.nominal, stats = self.engine.mppi_step(state, self.seed, self.step_count, self.params)
+        return self._took_step(rec, {"rho": float(stats[0]), "eta": float(stats[1]), "ess": float(stats[2]), "J0": float(stats[3])})
 
 
-class CEM:
+class CEM(_PlanController):
     """``cem = CEM(N=20, K=4096, n_elite=64); u = cem.step(state)``: the cross-entropy method.
 
     The handle keeps a mean plan (N, 3); each step samples K candidates on the GPU around it with a per-node spread, clamped
@@ -161,22 +173,15 @@ class CEM:
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, n_elite: Optional[int] = None,
                  n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0), lo=(-np.inf,) * 3, hi=(np.inf,) * 3,
                  seed: int = 20250523, mean=None, reserved: int = 0, **overrides):
-        m = default_model()
         K = int(overrides["K"]) if "K" in overrides else (cfg.K if cfg is not None else MPCConfig().K)
         if n_elite is None:
             n_elite = max(K // 64, 1)
         if isinstance(n_elite, bool) or int(n_elite) != n_elite or int(n_elite) > K:
             raise ValueError(f"n_elite must be an integer <= K = {K} (got {n_elite!r})")
-        std = np.asarray(std if std is not None else m.scale[3:6], dtype=np.float64)
+        std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
         self.params = _lib.CEMParams.make(n_iter, n_elite, alpha, std, std_min, lo, hi, reserved)   # ValueError before the library is called
         self.n_iter, self.n_elite, self.alpha = int(n_iter), int(n_elite), float(alpha)
-        self.seed = int(seed)
-        self.engine = Engine(cfg, model, **overrides)
-        self.cfg = self.engine.cfg
-        self._default_mean = np.asarray(m.mean[3:6], dtype=np.float64)
-        self.step_count = 0
-        self.last: Optional[StepResult] = None
-        self.last_stats: Optional[dict] = None
+        super().__init__(cfg, model, seed, overrides)
         self.mean: Optional[np.ndarray] = None
         self.std: Optional[np.ndarray] = None
         self.elites: Optional[np.ndarray] = None
@@ -184,27 +189,14 @@ class CEM:
 
     def reset(self, mean=None):
         """Set the mean plan ((N, 3), or (3,) repeated on every node; default: the scaler mean of x3..x5)."""
-        N = self.cfg.N
-        mu = self._default_mean if mean is None else np.asarray(mean, dtype=np.float64)
-        if mu.shape == (3,):
-            mu = np.tile(mu, (N, 1))
-        if mu.shape != (N, 3):
-            raise ValueError(f"mean must have shape ({N}, 3) or (3,), got {mu.shape}")
+        mu = self._plan(mean, "mean")
         self.engine.cem_reset(mu)
         self.mean = mu.copy()
 
     def step(self, state) -> np.ndarray:
-        rec, mu, sg, el, stats = self.engine.cem_step(state, self.seed, self.step_count, self.params)
-        self.step_count += 1
-        N = self.cfg.N
-        self.last = StepResult(rec[2:5].copy(), rec[5:].reshape(N + 1, 2).copy(), float(rec[0]), int(rec[1]))
-        self.last_stats = {"J_best": float(stats[0]), "J_worst_elite": float(stats[1]), "n_finite": int(stats[2]),
-                           "J0": float(stats[3])}
-        self.mean, self.std, self.elites = mu, sg, el
-        return self.last.u
-
-    def close(self):
-        self.engine.close()
+        rec, self.mean, self.std, self.elites, stats = self.engine.cem_step(state, self.seed, self.step_count, self.params)
+        return self._took_step(rec, {"J_best": float(stats[0]), "J_worst_elite": float(stats[1]), "n_finite": int(stats[2]),
+                                     "J0": float(stats[3])})
 
 
 def synthetic_problem(K: int, N: int, seed: int = 20250523, dtype=np.float64):
