@@ -133,6 +133,12 @@ _SIGNATURES = {
     "rovmpc_cem_step": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, C.POINTER(CEMParams), _P, _P, _P, _P, _P]),
     "rovmpc_cem_last": (C.c_int, [_P, _P, _P]),
     "rovmpc_cem_update_device": (C.c_int, [_P, _P, _P, C.POINTER(CEMParams), _P, _P, _P, _P, _P, _P, _P]),
+    "rovmpc_mppi_reset_batch": (C.c_int, [_P, C.c_int32, _P]),
+    "rovmpc_mppi_step_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint64, C.POINTER(MPPIParams), _P, _P, _P]),
+    "rovmpc_mppi_last_batch": (C.c_int, [_P, _P, _P]),
+    "rovmpc_cem_reset_batch": (C.c_int, [_P, C.c_int32, _P]),
+    "rovmpc_cem_step_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint64, C.POINTER(CEMParams), _P, _P, _P, _P, _P]),
+    "rovmpc_cem_last_batch": (C.c_int, [_P, _P, _P]),
     "rovmpc_mpc_step_sampled": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, _P, _P, C.c_int32, _P]),
     "rovmpc_sampled_candidates": (C.c_int, [_P, _P]),
     "rovmpc_sample_candidates_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),

@@ -21,26 +21,54 @@ struct CemSampleArgs {
     const double *sigma;                // [N][3], or null: std[c] on every node
 };
 
+// the draw of one problem; the batched sampler runs the same body per problem, so the bits are the same
+template <typename T>
+RV_DEV void cem_sample_body(unsigned long long seed, unsigned long long counter, const double *std, const double *lo,
+                            const double *hi, long long total, int N, const double *mu, const double *sigma, T *__restrict__ U) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, e0 = 4 * j;
+    if (e0 >= total) return;
+    double z[4];
+    philox_normal4(seed, counter, j, z);
+    const int row3 = 3 * N;
+    int col = (int)(e0 % row3);                         // = 3 n + c
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long long e = e0 + i;
+        if (e >= total) break;
+        const int c = col % 3;
+        const double m = mu[col], s = sigma ? sigma[col] : std[c];
+        U[e] = (T)cem_clamp(e < row3 ? m : ::fma(s, z[i], m), lo[c], hi[c]);
+        if (++col == row3) col = 0;
+    }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 cem_sample_kernel(const CemSampleArgs a, T *__restrict__ U) {
     if (a.d_state && blockIdx.x == 0 && threadIdx.x < ROVMPC_STATE_LEN)
         a.d_state[threadIdx.x] = reinterpret_cast<const double *>(&a.state)[threadIdx.x];
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, e0 = 4 * j;
-    if (e0 >= a.total) return;
-    double z[4];
-    philox_normal4(a.seed, a.counter, j, z);
-    const int row3 = 3 * a.N;
-    int col = (int)(e0 % row3);                         // = 3 n + c
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long long e = e0 + i;
-        if (e >= a.total) break;
-        const int c = col % 3;
-        const double m = a.mu[col], s = a.sigma ? a.sigma[col] : a.std[c];
-        U[e] = (T)cem_clamp(e < row3 ? m : ::fma(s, z[i], m), a.lo[c], a.hi[c]);
-        if (++col == row3) col = 0;
-    }
+    cem_sample_body<T>(a.seed, a.counter, a.std, a.lo, a.hi, a.total, a.N, a.mu, a.sigma, U);
+}
+
+// Batched form (rovmpc_cem_step_batch): blockIdx.y = problem; states and seeds as for mppi_sample_batch_kernel.
+struct CemSampleBatchArgs {
+    PlanBatchIn in;
+    unsigned long long counter;
+    double std[3], lo[3], hi[3];
+    long long total;                    // K * N * 3 (a problem's share of U)
+    int N;
+    const double *mu;                   // [B][N][3]
+    const double *sigma;                // [B][N][3], or null: std[c] on every node
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+cem_sample_batch_kernel(const CemSampleBatchArgs a, T *__restrict__ U) {
+    const int b = blockIdx.y;
+    const unsigned long long seed = plan_batch_seed(a.in, b);
+    const size_t off = (size_t)b * 3 * a.N;
+    cem_sample_body<T>(seed, a.counter, a.std, a.lo, a.hi, a.total, a.N, a.mu + off, a.sigma ? a.sigma + off : nullptr,
+                       U + (size_t)b * a.total);
 }
 
 // ---- selection and refit ------------------------------------------------------------------------------------------------
@@ -199,16 +227,23 @@ RV_DEV int cem_select(const Ld &ld, long long M, int E, CemShared &s, unsigned &
     return (int)(tlt + (teq < cap ? teq : cap));
 }
 
-// QC = columns per thread: 1 when 3 N <= CEM_NT, else 4
+// The selection and refit of one problem by the workgroups blockIdx.x = 0 .. G - 1 (the kernels below: one problem, or
+// blockIdx.y = problem).  QC = columns per thread: 1 when 3 N <= CEM_NT, else 4
 template <typename T, int QC>
-__global__ void __launch_bounds__(CEM_NT)
-cem_update_kernel(const CemUpdateArgs a) {
+RV_DEV void cem_update_body(const CemUpdateArgs &a, const PlanBatchAt &at) {
     __shared__ CemShared s;
     __shared__ int sLast;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const T *__restrict__ J = static_cast<const T *>(a.J);
-    const T *__restrict__ U = static_cast<const T *>(a.U);
+    const T *__restrict__ J = static_cast<const T *>(a.J) + at.b * a.K;
+    const T *__restrict__ U = static_cast<const T *>(a.U) + at.b * a.K * a.C3;
     const int C3 = a.C3, G = a.G;
+    // the problem's other arrays, each taken from the arguments where it is used
+    auto mu_in = [&] { return a.mu_in + at.b * C3; };
+    auto sigma_in = [&] { return a.sigma_in + at.b * C3; };            // (a.sigma_in not null)
+    auto mu_out = [&] { return a.mu_out + at.b * C3; };
+    auto sigma_out = [&] { return a.sigma_out + at.b * C3; };
+    auto slab_p = [&] { return a.slab + at.b * at.slab_stride; };      // (G > 1)
+    auto ticket = [&] { return a.ticket + at.b; };
     const long long k0 = (long long)blockIdx.x * a.slice, k1 = k0 + a.slice < a.K ? k0 + a.slice : a.K;
 
     // (1) the workgroup's own selection, its keys in registers (thread t: candidates k0 + t C1 + i, all loads issued at once)
@@ -228,7 +263,7 @@ cem_update_kernel(const CemUpdateArgs a) {
         //     again over all the lists
         const long long W = 2 + 2 * (long long)a.Lcap;
         if (wv == 0) {
-            unsigned long long *row = a.slab + blockIdx.x * W;
+            unsigned long long *row = slab_p() + blockIdx.x * W;
             for (int i = lane; i < nE; i += 64) {
                 st_agent(row + 2 + i, s.key[i]);
                 st_agent(row + 2 + a.Lcap + i, (unsigned long long)s.idx[i]);
@@ -236,15 +271,15 @@ cem_update_kernel(const CemUpdateArgs a) {
             if (lane == 0) { st_agent(row, (unsigned long long)nE); st_agent(row + 1, (unsigned long long)nfin); }
             // write-through stores acknowledged before the ticket that announces them (no L2 write-back fence needed)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) sLast = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(G - 1);
+            if (lane == 0) sLast = __hip_atomic_fetch_add(ticket(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(G - 1);
         }
         __syncthreads();
         if (!sLast) return;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (no instruction: keeps the slab loads below the ticket)
-        if (tid == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) __hip_atomic_store(ticket(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // |F| = the sum of the workgroups' finite counts
         unsigned f = 0;
-        for (int b = tid; b < G; b += CEM_NT) f += (unsigned)ld_agent(a.slab + b * W + 1);
+        for (int b = tid; b < G; b += CEM_NT) f += (unsigned)ld_agent(slab_p() + b * W + 1);
         cem_block_scan(f, s.wsum, nfin);
         const int Lcap = a.Lcap;
         unsigned ncand;
@@ -252,7 +287,7 @@ cem_update_kernel(const CemUpdateArgs a) {
         nE = cem_select<0>([&](long long i, unsigned long long &key, int &idx) {
                             const long long p = tid * C2 + i, b = p / Lcap;
                             const int j = (int)(p - b * Lcap);
-                            const unsigned long long *row = a.slab + b * W;
+                            const unsigned long long *row = slab_p() + b * W;
                             key = CEM_NONE;
                             if ((unsigned long long)j < ld_agent(row)) {
                                 key = ld_agent(row + 2 + j);
@@ -330,7 +365,7 @@ cem_update_kernel(const CemUpdateArgs a) {
     }
     for (int c = tid; c < C3; c += CEM_NT) {
         const int ch = c % 3;
-        const double mi = a.mu_in[c], si = a.sigma_in ? a.sigma_in[c] : a.std[ch];
+        const double mi = mu_in()[c], si = a.sigma_in ? sigma_in()[c] : a.std[ch];
         if (nE == 0) {
             s.mu[c] = mi; s.sg[c] = si;             // no finite cost: mean and spread stay, bit for bit
         } else {
@@ -340,8 +375,8 @@ cem_update_kernel(const CemUpdateArgs a) {
     }
     __syncthreads();
     for (int c = tid; c < C3; c += CEM_NT) {
-        a.mu_out[c] = s.mu[a.shift && c + 3 < C3 ? c + 3 : c];
-        a.sigma_out[c] = s.sg[c];
+        mu_out()[c] = s.mu[a.shift && c + 3 < C3 ? c + 3 : c];
+        sigma_out()[c] = s.sg[c];
     }
     const double nan = __builtin_nan("");
     const double st0 = nE ? (double)J[s.ridx[0]] : nan, st1 = nE ? (double)J[s.ridx[nE - 1]] : nan;
@@ -352,15 +387,37 @@ cem_update_kernel(const CemUpdateArgs a) {
     if (a.record && wv == 0) {
         // the control to apply is clamp(mu*[0]); the rest of the record is the last rollout's
         auto u = [&](int c) { return cem_clamp(s.mu[c], a.lo[c], a.hi[c]); };
-        if (lane < 3) a.record[2 + lane] = u(lane);
-        double *o = a.host_out;
-        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? u(i - 2) : a.record[i];
+        double *record = a.record + at.b * a.R, *o = a.host_out + at.b * at.host_stride;
+        long long *host_elite = a.host_elite + at.b * at.host_stride;
+        if (lane < 3) record[2 + lane] = u(lane);
+        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? u(i - 2) : record[i];
         for (int c = lane; c < C3; c += 64) { o[a.R + c] = s.mu[c]; o[a.R + C3 + c] = s.sg[c]; }
-        for (int i = lane; i < a.E; i += 64) a.host_elite[i] = i < nE ? s.ridx[i] : -1;
+        for (int i = lane; i < a.E; i += 64) host_elite[i] = i < nE ? s.ridx[i] : -1;
         if (lane == 0) { o[a.R + 2 * C3] = st0; o[a.R + 2 * C3 + 1] = st1; o[a.R + 2 * C3 + 2] = st2; o[a.R + 2 * C3 + 3] = st3; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        if (lane == 0) __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        plan_publish(a.done_flag, a.done_seq, at.step_ticket, at.B);          // (see mppi_update_body)
     }
+}
+
+template <typename T, int QC>
+__global__ void __launch_bounds__(CEM_NT)
+cem_update_kernel(const CemUpdateArgs a) {
+    cem_update_body<T, QC>(a, PlanBatchAt{});
+}
+
+// Batched form: grid (G, B).  Problem b = blockIdx.y has its own J, U, mean and spread halves, slab rows, ticket, record and
+// mailbox row (the elite list inside it), each at the first problem's pointer + b * its stride (PlanBatchAt); within a problem
+// everything is cem_update_body, the cross-workgroup select at K > CEM_SLICE included.
+struct CemUpdateBatchArgs {
+    CemUpdateArgs a;                    // problem 0
+    size_t slab_stride, host_stride;    // 64-bit words per problem
+    unsigned *step_ticket;              // last iteration: 0 between steps
+    int B;
+};
+
+template <typename T, int QC>
+__global__ void __launch_bounds__(CEM_NT)
+cem_update_batch_kernel(const CemUpdateBatchArgs ba) {
+    cem_update_body<T, QC>(ba.a, PlanBatchAt{blockIdx.y, ba.slab_stride, ba.host_stride, ba.step_ticket, ba.B});
 }
 
 }  // namespace rovmpc

@@ -51,6 +51,24 @@ struct PlanCtl {
     unsigned long long steps = 0;
 };
 
+// The batched form of such a controller (rovmpc_*_step_batch): B problems side by side in buffers of its own, every
+// per-problem array the single-problem array repeated B times; allocated at rovmpc_*_reset_batch, again when B changes.
+struct PlanBatch {
+    const char *name, *abi;                      // "MPPI", "mppi"
+    int B = 0;                                   // 0: no reset yet
+    void *U = nullptr, *J = nullptr;             // T [B][K][N][3], T [B][K]
+    double *state = nullptr, *record = nullptr;  // [B][16], [B][result_len]
+    unsigned long long *seeds = nullptr;         // [B]: kept by the first sampler of a step for the later ones
+    double *plan = nullptr, *spread = nullptr;   // [2][B][3N] each; spread: CEM only
+    int cur = 0;
+    void *slab = nullptr;                        // [B] slabs of slab_stride 64-bit words
+    unsigned *tickets = nullptr;                 // [B] of the problems' updates, then the step's
+    size_t slab_stride = 0, row = 0;             // row: 64-bit words per problem of the mailbox
+    double *h_stage = nullptr, *d_stage = nullptr;   // mapped: states [B][16], seeds [B] of the step being enqueued
+    Mailbox box;                                 // [B][row]
+    unsigned long long steps = 0;
+};
+
 struct rovmpc_handle {
     rovmpc_config cfg;
     hipStream_t stream = nullptr;
@@ -115,6 +133,7 @@ struct rovmpc_handle {
     void *arg_J = nullptr;                       // costs of the launch being enqueued go here instead of d_J (null: d_J)
     // MPPI (rovmpc_mppi_*): mailbox [record, nu*, stats]; CEM (rovmpc_cem_*): [record, mu*, sigma*, stats, elite list]
     PlanCtl mppi{"MPPI", "mppi", "MPPI step"}, cem{"CEM", "cem", "CEM step"};
+    PlanBatch mppi_b{"MPPI", "mppi"}, cem_b{"CEM", "cem"};
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -256,6 +275,38 @@ static int plan_alloc(rovmpc_handle *h, PlanCtl &c, size_t slab_bytes, size_t ex
     if (rc) plan_free(c);
     c.allocated = !rc;
     return rc;
+}
+
+static void plan_batch_free(PlanBatch &c) {
+    dev_free(c.U); dev_free(c.J); dev_free(c.state); dev_free(c.record); dev_free(c.seeds); dev_free(c.plan); dev_free(c.spread);
+    dev_free(c.slab); dev_free(c.tickets);
+    if (c.h_stage) (void)hipHostFree(c.h_stage);
+    c.h_stage = c.d_stage = nullptr;
+    mailbox_free(c.box);
+    c.B = 0;
+}
+
+// Into a fresh PlanBatch, all or nothing: the caller swaps it in, so a failure leaves the previous batched state usable.
+static int plan_batch_alloc(rovmpc_handle *h, PlanBatch &c, int B, size_t slab_words, size_t row_words, bool with_spread) {
+    const size_t K = (size_t)h->cfg.K, C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h), nb = (size_t)B;
+    hipError_t e = hipSuccess;
+    auto dev = [&e](auto **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void **)p, bytes); };
+    dev(&c.U, nb * K * C3 * h->esz); dev(&c.J, nb * K * h->esz);
+    dev(&c.state, nb * ROVMPC_STATE_LEN * sizeof(double)); dev(&c.record, nb * R * sizeof(double));
+    dev(&c.seeds, nb * sizeof(unsigned long long));
+    dev(&c.plan, 2 * nb * C3 * sizeof(double));
+    if (with_spread) dev(&c.spread, 2 * nb * C3 * sizeof(double));
+    if (slab_words) dev(&c.slab, nb * slab_words * 8);
+    dev(&c.tickets, (nb + 1) * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(c.tickets, 0, (nb + 1) * sizeof(unsigned));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c.h_stage, nb * (ROVMPC_STATE_LEN + 1) * 8, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&c.d_stage, c.h_stage, 0);
+    int rc = ROVMPC_OK;
+    if (e != hipSuccess) { h->err = std::string("batched ") + c.name + " buffers: " + hipGetErrorString(e); rc = ROVMPC_ERR_HIP; }
+    if (!rc) rc = mailbox_alloc(h, c.box, nb * row_words);
+    if (rc) { plan_batch_free(c); return rc; }
+    c.B = B; c.slab_stride = slab_words; c.row = row_words;
+    return ROVMPC_OK;
 }
 
 static size_t lds_need(const rovmpc_config *c, int ck, int model, unsigned used = 0xffffffffu, int jit_gi = 0) {
@@ -504,6 +555,8 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     if (h->h_err) (void)hipHostFree(h->h_err);
     plan_free(h->mppi);
     plan_free(h->cem);
+    plan_batch_free(h->mppi_b);
+    plan_batch_free(h->cem_b);
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete h->epoch_ctr;
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -943,7 +996,7 @@ template <typename T> static void fill_args(const rovmpc_handle *h, RolloutArgs<
     while ((1 << a.ck_shift) < g.CK) ++a.ck_shift;
     a.magic_3n = (unsigned)(4294967296ULL / (unsigned long long)(3 * c.N)) + 1u;
     a.granules = B > 1 ? h->d_granulesb : h->d_granules;
-    if (B > 1) { a.J = (T *)h->d_Jb; a.blk_traj = h->d_blk_trajb; }
+    if (B > 1) { if (!h->arg_J) a.J = (T *)h->d_Jb; a.blk_traj = h->d_blk_trajb; }
     a.sweeper = (long long)B * g.nblocks <= h->n_cu ? 0 : g.nblocks - 1;
     if (++*h->epoch_ctr == 0) ++*h->epoch_ctr;      // never 0 (the granules start zeroed)
     a.epoch = *h->epoch_ctr;
@@ -1063,20 +1116,28 @@ extern "C" int rovmpc_step_device(rovmpc_handle *h, const double *d_state, const
     return enqueue_step(h, d_state, d_U, nullptr, d_result, 0, nullptr, 0, 1, (hipStream_t)stream);
 }
 
-// Workspace of a batched launch: costs, per-workgroup trajectories and hand-off granules for B problems.
+// Workspace of a batched launch: costs, per-workgroup trajectories and hand-off granules for B problems.  The larger set is
+// made before the old one is let go, so a failed allocation leaves the handle with the workspace and capacity it had.
 static int ensure_batch(rovmpc_handle *h, int B) {
     if (B <= h->batch_cap) return ROVMPC_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipDeviceSynchronize());               // nothing may still be using the old buffers
-    void *old[] = {h->d_Jb, h->d_blk_trajb, h->d_granulesb};
-    for (void *p : old) if (p) (void)hipFree(p);
-    h->d_Jb = nullptr; h->d_blk_trajb = nullptr; h->d_granulesb = nullptr; h->batch_cap = 0;
     const rovmpc_config &c = h->cfg;
     const size_t max_blocks = c.candidates_per_block > 0 ? (size_t)((c.K + c.candidates_per_block - 1) / c.candidates_per_block) : (size_t)c.K;
-    HIPCHK(h, hipMalloc(&h->d_Jb, (size_t)B * c.K * h->esz));
-    HIPCHK(h, hipMalloc((void **)&h->d_blk_trajb, (size_t)B * max_blocks * (c.N + 1) * 2 * sizeof(double)));
-    HIPCHK(h, hipMalloc((void **)&h->d_granulesb, (size_t)B * GRAN * max_blocks * sizeof(unsigned long long)));
-    HIPCHK(h, hipMemset(h->d_granulesb, 0, (size_t)B * GRAN * max_blocks * sizeof(unsigned long long)));
+    const size_t gran_bytes = (size_t)B * GRAN * max_blocks * sizeof(unsigned long long);
+    void *fresh[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipMalloc(&fresh[0], (size_t)B * c.K * h->esz);
+    if (e == hipSuccess) e = hipMalloc(&fresh[1], (size_t)B * max_blocks * (c.N + 1) * 2 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&fresh[2], gran_bytes);
+    if (e == hipSuccess) e = hipMemset(fresh[2], 0, gran_bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();  // nothing may still be using the old buffers
+    if (e != hipSuccess) {
+        for (void *p : fresh) if (p) (void)hipFree(p);
+        (void)hipGetLastError();                     // an allocation failure is not sticky: the handle stays usable
+        FAIL(h, ROVMPC_ERR_HIP, "batched workspace for %d problems: %s", B, hipGetErrorString(e));
+    }
+    void *old[] = {h->d_Jb, h->d_blk_trajb, h->d_granulesb};
+    for (void *p : old) if (p) (void)hipFree(p);
+    h->d_Jb = fresh[0]; h->d_blk_trajb = (double *)fresh[1]; h->d_granulesb = (unsigned long long *)fresh[2];
     h->batch_cap = B;
     return ROVMPC_OK;
 }
@@ -1637,6 +1698,228 @@ extern "C" int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const
     if ((rc = slab_alloc(h, h->cem.slab_x, cem_slab_bytes(h)))) return rc;
     return launch_cem_update(h, d_J, d_U, p, d_mean_in, d_std_in, d_mean_out, d_std_out, (long long *)d_elite_out, d_stats,
                              h->cem.slab_x, PlanIter{}, nullptr, (hipStream_t)stream);
+}
+
+// ---- batched MPPI and CEM: B independent plans advanced by one call, three launches per iteration for the whole batch ----
+static const int PLAN_BATCH_MAX = 1024;
+
+static int check_batch_size(rovmpc_handle *h, const char *fn, int B) {
+    if (B < 1 || B > PLAN_BATCH_MAX) FAIL(h, ROVMPC_ERR_INVALID, "%s: B must be in 1..%d (got %d)", fn, PLAN_BATCH_MAX, B);
+    return ROVMPC_OK;
+}
+
+// rovmpc_*_reset_batch: buffers for B problems (kept when B is the one they were made for), the plans into half 0
+static int plan_reset_batch(rovmpc_handle *h, PlanBatch &c, int B, const double *plans, size_t slab_words, size_t row_words,
+                            bool with_spread) {
+    int rc;
+    if ((rc = check_single_gpu(h, c.name))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (B != c.B) {
+        PlanBatch fresh{c.name, c.abi};
+        if ((rc = plan_batch_alloc(h, fresh, B, slab_words, row_words, with_spread))) return rc;
+        if (B > 1 && (rc = ensure_batch(h, B))) { plan_batch_free(fresh); return rc; }     // the batched rollout's workspace
+        HIPCHK(h, hipDeviceSynchronize());           // nothing may still be using the old buffers
+        plan_batch_free(c);
+        c = fresh;
+    }
+    HIPCHK(h, hipMemcpyAsync(c.plan, plans, (size_t)B * 3 * h->cfg.N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    c.cur = 0;
+    return ROVMPC_OK;
+}
+
+static int plan_last_batch(rovmpc_handle *h, PlanBatch &c, void *U_out, void *J_out) {
+    if (c.steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_last_batch: no batched %s step yet", c.abi, c.name);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (U_out) HIPCHK(h, hipMemcpy(U_out, c.U, (size_t)c.B * h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
+    if (J_out) HIPCHK(h, hipMemcpy(J_out, c.J, (size_t)c.B * h->cfg.K * h->esz, hipMemcpyDeviceToHost));
+    return ROVMPC_OK;
+}
+
+// What the loop hands the two launches of iteration i of a batched step (PlanIter's counterpart)
+struct PlanBatchIter {
+    PlanBatchIn in;                        // stage set in iteration 0 only
+    uint64_t counter = 0;
+    size_t in_off = 0, out_off = 0;        // offsets of the halves of plan (and spread): [B][3N] each
+    bool first = false, last = false;
+    unsigned long long done_seq = 0;
+};
+
+// The checks of a batched step that need no parameters, before anything is launched
+static int plan_batch_ready(rovmpc_handle *h, PlanBatch &c, const char *fn, int B, const rovmpc_state *states, const uint64_t *seeds,
+                            const double *records_out) {
+    int rc;
+    if ((rc = check_batch_size(h, fn, B))) return rc;
+    if (!states || !seeds || !records_out) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer", fn);
+    if ((rc = check_single_gpu(h, c.name))) return rc;
+    if (c.B == 0) FAIL(h, ROVMPC_ERR_INVALID, "%s before rovmpc_%s_reset_batch", fn, c.abi);
+    if (B != c.B) FAIL(h, ROVMPC_ERR_INVALID, "%s: B = %d but rovmpc_%s_reset_batch made %d problems", fn, B, c.abi, c.B);
+    return ROVMPC_OK;
+}
+
+// rovmpc_*_step_batch: states and seeds into the staging block, n_iter x (sample, batched rollout, update) on the handle's
+// stream without a host round trip, then one wait for the whole batch's mailbox.
+template <typename Sample, typename Update>
+static int plan_step_batch(rovmpc_handle *h, PlanBatch &c, const rovmpc_state *states, const uint64_t *seeds, uint64_t step, int n_iter,
+                           Sample sample, Update update) {
+    int rc;
+    if ((rc = check_ready(h))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
+    const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N;
+    memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
+    memcpy(c.h_stage + B * ROVMPC_STATE_LEN, seeds, B * sizeof(uint64_t));
+    const unsigned long long seq = ++c.box.seq;
+    int cur = c.cur;
+    for (int i = 0; i < n_iter; ++i) {
+        PlanBatchIter it;
+        it.in = PlanBatchIn{i == 0 ? c.d_stage : nullptr, c.state, c.seeds, c.B};
+        it.counter = step * (uint64_t)n_iter + (uint64_t)i;
+        it.in_off = cur * half; it.out_off = (cur ^ 1) * half; it.first = i == 0; it.last = i + 1 == n_iter; it.done_seq = seq;
+        if ((rc = sample(it))) return rc;
+        const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
+        h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
+        rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream, c.B);
+        h->arg_J = nullptr;
+        h->last_batch = last_batch;
+        if (rc) return rc;
+        if ((rc = update(it))) return rc;
+        cur ^= 1;
+    }
+    c.cur = cur;
+    ++c.steps;
+    return mailbox_wait(h, c.box, seq, c.name);
+}
+
+// mailbox row of a problem: record, nu* (3N), stats (4)
+static size_t mppi_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 3 * (size_t)h->cfg.N + 4; }
+
+extern "C" int rovmpc_mppi_reset_batch(rovmpc_handle *h, int32_t B, const double *nominals) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_batch_size(h, "rovmpc_mppi_reset_batch", B);
+    if (rc) return rc;
+    if (!nominals) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_reset_batch: null nominals");
+    return plan_reset_batch(h, h->mppi_b, B, nominals, mppi_slab_bytes(h) / 8, mppi_row_words(h), false);
+}
+
+extern "C" int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                                      const rovmpc_mppi_params *p, double *records_out, double *nominals_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    PlanBatch &c = h->mppi_b;
+    int rc = plan_batch_ready(h, c, "rovmpc_mppi_step_batch", B, states, seeds, records_out);
+    if (rc || (rc = mppi_check_params(h, p))) return rc;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    const long long total = (long long)h->cfg.K * h->cfg.N * 3;
+    rc = plan_step_batch(h, c, states, seeds, step, p->n_iter,
+                         [&](const PlanBatchIter &it) {
+                             MppiSampleBatchArgs sa;
+                             memset(&sa, 0, sizeof(sa));
+                             sa.in = it.in; sa.counter = it.counter;
+                             for (int i = 0; i < 3; ++i) sa.std[i] = p->std[i];
+                             sa.total = total; sa.N = h->cfg.N; sa.nu = c.plan + it.in_off;
+                             const dim3 grid(sampler_grid(total), B), bs(SAMPLER_NT);
+                             if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(mppi_sample_batch_kernel<double>, grid, bs, 0, h->stream, sa, (double *)c.U);
+                             else hipLaunchKernelGGL(mppi_sample_batch_kernel<float>, grid, bs, 0, h->stream, sa, (float *)c.U);
+                             return launched(h, "batched MPPI sampler");
+                         },
+                         [&](const PlanBatchIter &it) {
+                             const MppiGeo g = mppi_geometry(h->cfg.K);
+                             MppiUpdateBatchArgs ba;
+                             memset(&ba, 0, sizeof(ba));
+                             MppiUpdateArgs &a = ba.a;
+                             a.J = c.J; a.U = c.U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = (int)C3; a.G = g.G; a.lambda = p->lambda;
+                             a.nu_in = c.plan + it.in_off; a.nu_out = c.plan + it.out_off; a.slab = (double *)c.slab; a.ticket = c.tickets;
+                             a.R = (int)R;
+                             ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = B;
+                             if (it.last) {
+                                 a.shift = 1; a.record = c.record; a.host_out = c.box.d_out; a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
+                                 ba.step_ticket = c.tickets + B;
+                             }
+                             LAUNCH_T_QC(mppi_update_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, B), dim3(MPPI_NT), 0, h->stream, ba);
+                             return launched(h, "batched MPPI update");
+                         });
+    if (rc) return rc;
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        const double *o = c.box.h_out + b * c.row;
+        memcpy(records_out + b * R, o, R * sizeof(double));
+        if (nominals_out) memcpy(nominals_out + b * C3, o + R, C3 * sizeof(double));
+        if (stats_out) memcpy(stats_out + b * 4, o + R + C3, 4 * sizeof(double));
+    }
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_mppi_last_batch(rovmpc_handle *h, void *U_out, void *J_out) {
+    return h ? plan_last_batch(h, h->mppi_b, U_out, J_out) : ROVMPC_ERR_INVALID;
+}
+
+// mailbox row of a problem: record, mu* (3N), sigma* (3N), stats (4), then the elite list (int64 [CEM_MAX_ELITE])
+static size_t cem_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 6 * (size_t)h->cfg.N + 4 + CEM_MAX_ELITE; }
+
+extern "C" int rovmpc_cem_reset_batch(rovmpc_handle *h, int32_t B, const double *means) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_batch_size(h, "rovmpc_cem_reset_batch", B);
+    if (rc) return rc;
+    if (!means) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_reset_batch: null means");
+    return plan_reset_batch(h, h->cem_b, B, means, cem_slab_bytes(h) / 8, cem_row_words(h), true);
+}
+
+extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                                     const rovmpc_cem_params *p, double *records_out, double *means_out, double *stds_out,
+                                     int64_t *elites_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    PlanBatch &c = h->cem_b;
+    int rc = plan_batch_ready(h, c, "rovmpc_cem_step_batch", B, states, seeds, records_out);
+    if (rc || (rc = cem_check_params(h, p))) return rc;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    const long long total = (long long)h->cfg.K * h->cfg.N * 3;
+    rc = plan_step_batch(h, c, states, seeds, step, p->n_iter,
+                         [&](const PlanBatchIter &it) {                           // sigma_0 = std
+                             CemSampleBatchArgs sa;
+                             memset(&sa, 0, sizeof(sa));
+                             sa.in = it.in; sa.counter = it.counter;
+                             for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
+                             sa.total = total; sa.N = h->cfg.N; sa.mu = c.plan + it.in_off; sa.sigma = it.first ? nullptr : c.spread + it.in_off;
+                             const dim3 grid(sampler_grid(total), B), bs(SAMPLER_NT);
+                             if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(cem_sample_batch_kernel<double>, grid, bs, 0, h->stream, sa, (double *)c.U);
+                             else hipLaunchKernelGGL(cem_sample_batch_kernel<float>, grid, bs, 0, h->stream, sa, (float *)c.U);
+                             return launched(h, "batched CEM sampler");
+                         },
+                         [&](const PlanBatchIter &it) {
+                             const CemGeo g = cem_geometry(h->cfg.K);
+                             CemUpdateBatchArgs ba;
+                             memset(&ba, 0, sizeof(ba));
+                             CemUpdateArgs &a = ba.a;
+                             a.J = c.J; a.U = c.U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = (int)C3; a.G = g.G; a.E = p->n_elite; a.Lcap = g.Lcap;
+                             a.alpha = p->alpha;
+                             for (int i = 0; i < 3; ++i) { a.std[i] = p->std[i]; a.std_min[i] = p->std_min[i]; a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
+                             a.mu_in = c.plan + it.in_off; a.sigma_in = it.first ? nullptr : c.spread + it.in_off;
+                             a.mu_out = c.plan + it.out_off; a.sigma_out = c.spread + it.out_off;
+                             a.slab = (unsigned long long *)c.slab; a.ticket = c.tickets; a.R = (int)R;
+                             ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = B;
+                             if (it.last) {
+                                 a.shift = 1; a.record = c.record; a.host_out = c.box.d_out;
+                                 a.host_elite = (long long *)(c.box.d_out + R + 2 * C3 + 4);
+                                 a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
+                                 ba.step_ticket = c.tickets + B;
+                             }
+                             LAUNCH_T_QC(cem_update_batch_kernel, h, a.C3 > CEM_NT, dim3(g.G, B), dim3(CEM_NT), 0, h->stream, ba);
+                             return launched(h, "batched CEM update");
+                         });
+    if (rc) return rc;
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        const double *o = c.box.h_out + b * c.row;
+        memcpy(records_out + b * R, o, R * sizeof(double));
+        if (means_out) memcpy(means_out + b * C3, o + R, C3 * sizeof(double));
+        if (stds_out) memcpy(stds_out + b * C3, o + R + C3, C3 * sizeof(double));
+        if (stats_out) memcpy(stats_out + b * 4, o + R + 2 * C3, 4 * sizeof(double));
+        if (elites_out) memcpy(elites_out + b * (size_t)p->n_elite, o + R + 2 * C3 + 4, (size_t)p->n_elite * sizeof(int64_t));
+    }
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_cem_last_batch(rovmpc_handle *h, void *U_out, void *J_out) {
+    return h ? plan_last_batch(h, h->cem_b, U_out, J_out) : ROVMPC_ERR_INVALID;
 }
 
 // ---- timing ---------------------------------------------------------------------------------

@@ -65,25 +65,71 @@ struct MppiSampleArgs {
     const double *nu;                   // nominal [N][3]
 };
 
+// the draw of one problem; the batched sampler runs the same body per problem, so the bits are the same
+template <typename T>
+RV_DEV void mppi_sample_body(unsigned long long seed, unsigned long long counter, const double *std, long long total, int N,
+                             const double *nu, T *__restrict__ U) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, e0 = 4 * j;
+    if (e0 >= total) return;
+    double z[4];
+    philox_normal4(seed, counter, j, z);
+    const int row3 = 3 * N;
+    int col = (int)(e0 % row3);                         // = 3 n + c
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long long e = e0 + i;
+        if (e >= total) break;
+        const double m = nu[col];
+        U[e] = e < row3 ? (T)m : (T)::fma(std[col % 3], z[i], m);
+        if (++col == row3) col = 0;
+    }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 mppi_sample_kernel(const MppiSampleArgs a, T *__restrict__ U) {
     if (a.d_state && blockIdx.x == 0 && threadIdx.x < ROVMPC_STATE_LEN)
         a.d_state[threadIdx.x] = reinterpret_cast<const double *>(&a.state)[threadIdx.x];
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, e0 = 4 * j;
-    if (e0 >= a.total) return;
-    double z[4];
-    philox_normal4(a.seed, a.counter, j, z);
-    const int row3 = 3 * a.N;
-    int col = (int)(e0 % row3);                         // = 3 n + c
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long long e = e0 + i;
-        if (e >= a.total) break;
-        const double m = a.nu[col];
-        U[e] = e < row3 ? (T)m : (T)::fma(a.std[col % 3], z[i], m);
-        if (++col == row3) col = 0;
+    mppi_sample_body<T>(a.seed, a.counter, a.std, a.total, a.N, a.nu, U);
+}
+
+// Batched form (rovmpc_mppi_step_batch): blockIdx.y = problem.  B states do not fit in the kernel arguments, so the first
+// iteration of a control step reads states [B][16] and seeds [B] from one staging block in mapped host memory and block 0
+// of each problem keeps them in device memory (d_state, d_seeds) for the step's rollouts and later draws; the later
+// iterations read the seeds from there (stage null).
+struct PlanBatchIn {
+    const double *stage;                // mapped: states [B][16], then seeds [B]; null after the first iteration
+    double *d_state;                    // [B][16]
+    unsigned long long *d_seeds;        // [B]
+    int B;
+};
+
+RV_DEV unsigned long long plan_batch_seed(const PlanBatchIn &in, int b) {
+    if (!in.stage) return in.d_seeds[b];
+    const unsigned long long seed = reinterpret_cast<const unsigned long long *>(in.stage + (size_t)in.B * ROVMPC_STATE_LEN)[b];
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < ROVMPC_STATE_LEN)
+            in.d_state[(size_t)b * ROVMPC_STATE_LEN + threadIdx.x] = in.stage[(size_t)b * ROVMPC_STATE_LEN + threadIdx.x];
+        if (threadIdx.x == 0) in.d_seeds[b] = seed;
     }
+    return seed;
+}
+
+struct MppiSampleBatchArgs {
+    PlanBatchIn in;
+    unsigned long long counter;
+    double std[3];
+    long long total;                    // K * N * 3 (a problem's share of U)
+    int N;
+    const double *nu;                   // nominals [B][N][3]
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+mppi_sample_batch_kernel(const MppiSampleBatchArgs a, T *__restrict__ U) {
+    const int b = blockIdx.y;
+    const unsigned long long seed = plan_batch_seed(a.in, b);
+    mppi_sample_body<T>(seed, a.counter, a.std, a.total, a.N, a.nu + (size_t)b * 3 * a.N, U + (size_t)b * a.total);
 }
 
 // Update: one read of J[K] and U[K][3N].  Workgroup b takes candidates [b slice, (b + 1) slice) and writes to its slab row
@@ -127,19 +173,46 @@ RV_DEV double wave_sum(double v) {          // butterfly: every lane ends with t
 
 constexpr int MPPI_CHUNK = 8;             // rows (slab rows in the combine) whose loads are issued together
 
+// Publication of a control step's last update.  One problem: the finishing workgroup's wave 0 has written the mailbox and
+// releases done_seq at system scope.  A batch (step_ticket not null): each problem's finishing workgroup has written its own
+// mailbox row; it releases the row and takes the step's ticket, and the last of the B acquires the others' rows through
+// that ticket before it releases done_seq, so the host never reads a row that is not yet visible.  Called by whole wave 0.
+RV_DEV void plan_publish(unsigned long long *done_flag, unsigned long long done_seq, unsigned *step_ticket, int B) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    if ((threadIdx.x & 63) != 0) return;
+    if (step_ticket) {
+        if (__hip_atomic_fetch_add(step_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_SYSTEM) != (unsigned)(B - 1)) return;
+        __hip_atomic_store(step_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // re-armed for the next step
+    }
+    __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Where a workgroup's problem lies behind problem 0 of the arguments (all zero: a single-problem launch)
+struct PlanBatchAt {
+    size_t b = 0;                       // problem
+    size_t slab_stride = 0, host_stride = 0;   // 64-bit words per problem of the slab and of the mailbox
+    unsigned *step_ticket = nullptr;    // of the batch's last iteration (plan_publish)
+    int B = 0;
+};
+
+// The update of one problem by the workgroups blockIdx.x = 0 .. G - 1 (the kernels below: one problem, or blockIdx.y = problem).
 // QC = columns per thread: 1 when 3 N <= MPPI_NT, else 4
 template <typename T, int QC>
-__global__ void __launch_bounds__(MPPI_NT)
-mppi_update_kernel(const MppiUpdateArgs a) {
+RV_DEV void mppi_update_body(const MppiUpdateArgs &a, const PlanBatchAt &at) {
     __shared__ double sS[MPPI_MAX_COLS];                // row-lane partials [R][3N]
     __shared__ double sNu[MPPI_MAX_COLS];               // nu* (combine)
     __shared__ double sScale[MPPI_MAX_WG], sW[MPPI_NT], sEta[4], sW2[4];
     __shared__ double sRed[16];
     __shared__ int sLast;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const T *__restrict__ J = static_cast<const T *>(a.J);
-    const T *__restrict__ U = static_cast<const T *>(a.U);
+    const T *__restrict__ J = static_cast<const T *>(a.J) + at.b * a.K;
+    const T *__restrict__ U = static_cast<const T *>(a.U) + at.b * a.K * a.C3;
     const int C3 = a.C3, G = a.G;
+    // the problem's other arrays, each taken from the arguments where it is used
+    auto nu_in = [&] { return a.nu_in + at.b * C3; };
+    auto nu_out = [&] { return a.nu_out + at.b * C3; };
+    auto slab_p = [&] { return a.slab + at.b * at.slab_stride; };
+    auto ticket = [&] { return a.ticket + at.b; };
     // threads map to columns so that each candidate row is one coalesced read; R rows side by side when 3N <= 256,
     // otherwise one row with up to four columns per thread
     const int R = C3 <= MPPI_NT ? MPPI_NT / C3 : 1;
@@ -211,7 +284,7 @@ mppi_update_kernel(const MppiUpdateArgs a) {
 
     // (3) wave 0 sums the row-lanes in order, stores the slab row write-through and takes the ticket
     if (wv == 0) {
-        double *slab = a.slab + (size_t)blockIdx.x * (3 + C3);
+        double *slab = slab_p() + (size_t)blockIdx.x * (3 + C3);
         for (int c = lane; c < C3; c += 64) {
             double s = sS[c];
             for (int q = 1; q < R; ++q) s += sS[q * C3 + c];
@@ -224,17 +297,17 @@ mppi_update_kernel(const MppiUpdateArgs a) {
         }
         // write-through stores acknowledged before the ticket that announces them (no L2 write-back fence needed)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) sLast = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(G - 1);
+        if (lane == 0) sLast = __hip_atomic_fetch_add(ticket(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(G - 1);
     }
     __syncthreads();
     if (!sLast) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (no instruction: keeps the slab loads below the ticket)
 
     // (4) combine (last workgroup)
-    if (tid == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store(ticket(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     double rb = inf, eb = 0.0, wb = 0.0;
     if (tid < G) {
-        const double *s = a.slab + (size_t)tid * (3 + C3);
+        const double *s = slab_p() + (size_t)tid * (3 + C3);
         rb = ld_agent(s); eb = ld_agent(s + 1); wb = ld_agent(s + 2);
     }
     m = wave_min(rb);
@@ -245,7 +318,7 @@ mppi_update_kernel(const MppiUpdateArgs a) {
     double st0, st1, st2;
     if (!(rho < inf)) {
         // no finite cost: the nominal stays as it is, bit for bit
-        for (int c = tid; c < C3; c += MPPI_NT) sNu[c] = a.nu_in[c];
+        for (int c = tid; c < C3; c += MPPI_NT) sNu[c] = nu_in()[c];
         st0 = __builtin_nan(""); st1 = 0.0; st2 = 0.0;
     } else {
         const double sc = (tid < G && rb < inf) ? ::exp(-(rb - rho) / a.lambda) : 0.0;
@@ -262,7 +335,7 @@ mppi_update_kernel(const MppiUpdateArgs a) {
 #pragma unroll
                 for (int t = 0; t < MPPI_CHUNK; ++t) {
                     const int b = bb + t * R;
-                    const double *row = a.slab + (size_t)b * (3 + C3) + 3;
+                    const double *row = slab_p() + (size_t)b * (3 + C3) + 3;
 #pragma unroll
                     for (int q = 0; q < QC; ++q) {
                         const int c = c0 + q * MPPI_NT;
@@ -295,18 +368,38 @@ mppi_update_kernel(const MppiUpdateArgs a) {
         st0 = rho; st1 = eta_all; st2 = eta_all * eta_all / w2_all;
     }
     __syncthreads();
-    for (int c = tid; c < C3; c += MPPI_NT) a.nu_out[c] = sNu[a.shift && c + 3 < C3 ? c + 3 : c];
+    for (int c = tid; c < C3; c += MPPI_NT) nu_out()[c] = sNu[a.shift && c + 3 < C3 ? c + 3 : c];
     if (a.stats && tid == 0) { a.stats[0] = st0; a.stats[1] = st1; a.stats[2] = st2; a.stats[3] = J0; }
     if (a.record && wv == 0) {
         // the control to apply is nu*[0]; the rest of the record is the rollout's
-        if (lane < 3) a.record[2 + lane] = sNu[lane];
-        double *o = a.host_out;
-        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? sNu[i - 2] : a.record[i];
+        double *record = a.record + at.b * a.R, *o = a.host_out + at.b * at.host_stride;
+        if (lane < 3) record[2 + lane] = sNu[lane];
+        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? sNu[i - 2] : record[i];
         for (int c = lane; c < C3; c += 64) o[a.R + c] = sNu[c];
         if (lane == 0) { o[a.R + C3] = st0; o[a.R + C3 + 1] = st1; o[a.R + C3 + 2] = st2; o[a.R + C3 + 3] = J0; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        if (lane == 0) __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        plan_publish(a.done_flag, a.done_seq, at.step_ticket, at.B);
     }
+}
+
+template <typename T, int QC>
+__global__ void __launch_bounds__(MPPI_NT)
+mppi_update_kernel(const MppiUpdateArgs a) {
+    mppi_update_body<T, QC>(a, PlanBatchAt{});
+}
+
+// Batched form: grid (G, B).  Problem b = blockIdx.y has its own J, U, nominal halves, slab rows, ticket, record and mailbox
+// row, each at the first problem's pointer + b * its stride (PlanBatchAt); within a problem everything is mppi_update_body.
+struct MppiUpdateBatchArgs {
+    MppiUpdateArgs a;                   // problem 0
+    size_t slab_stride, host_stride;    // doubles per problem
+    unsigned *step_ticket;              // last iteration: 0 between steps
+    int B;
+};
+
+template <typename T, int QC>
+__global__ void __launch_bounds__(MPPI_NT)
+mppi_update_batch_kernel(const MppiUpdateBatchArgs ba) {
+    mppi_update_body<T, QC>(ba.a, PlanBatchAt{blockIdx.y, ba.slab_stride, ba.host_stride, ba.step_ticket, ba.B});
 }
 
 // model.predict(X) on n already-scaled rows: one lane per row, operand stack in LDS.

@@ -304,6 +304,79 @@ class Engine:
         self._check(self.lib.rovmpc_cem_update_device(self._h, d_J, d_U, C.byref(params), d_mean_in, d_std_in, d_mean_out,
                                                       d_std_out, d_elite_out or None, d_stats or None, stream))
 
+    # -- batched MPPI / CEM (rovmpc_*_batch): B plans advanced by one library call -----------------------
+    def _batch_inputs(self, B: int, states, seeds):
+        st = np.ascontiguousarray(states, dtype=np.float64)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if st.shape != (B, 16):
+            raise ValueError(f"states must have shape ({B}, 16), got {st.shape}")
+        if sd.shape != (B,):
+            raise ValueError(f"seeds must have shape ({B},), got {sd.shape}")
+        return st, sd
+
+    def _plan_reset_batch(self, fn, plans, name: str) -> int:
+        plans = np.ascontiguousarray(plans, dtype=np.float64)
+        if plans.ndim != 3 or plans.shape[1:] != (self.cfg.N, 3):
+            raise ValueError(f"{name} must have shape (B, {self.cfg.N}, 3), got {plans.shape}")
+        self._check(fn(self._h, plans.shape[0], _ptr(plans)))
+        return plans.shape[0]
+
+    def _plan_last_batch(self, fn, B: Optional[int], known: int, name: str):
+        # The library copies its own B problems whatever the caller believes: the arrays are sized from the B of this
+        # engine's last successful reset or step, and a caller that reset through the raw library says so with `B`.
+        if B is None:
+            B = known
+        if isinstance(B, bool) or int(B) != B or not 1 <= int(B) <= 1024 or (known and int(B) != known):
+            raise ValueError(f"{name}: B = {B!r}, but this engine's batch has {known} problems (0: no reset_batch yet)")
+        B = int(B)
+        U = np.empty((B, self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)
+        J = np.empty((B, self.cfg.K), dtype=self.cfg.np_dtype)
+        self._check(fn(self._h, _ptr(U), _ptr(J)))
+        return U, J
+
+    def mppi_reset_batch(self, nominals):
+        """Set the B nominal plans (B, N, 3) of the batched MPPI; (re)allocates its buffers when B changes."""
+        self._mppi_B = self._plan_reset_batch(self.lib.rovmpc_mppi_reset_batch, nominals, "nominals")
+
+    def mppi_step_batch(self, states, seeds, step: int, params: MPPIParams):
+        """One MPPI control step of B problems (states (B, 16), seeds (B,)): returns (records (B, result_len),
+        nu* (B, N, 3), stats (B, 4)); problem b's are bit for bit those of ``mppi_step`` on its own."""
+        if not isinstance(params, MPPIParams):
+            raise TypeError("params must be an MPPIParams (MPPIParams.make(...))")
+        B = len(seeds)
+        st, sd = self._batch_inputs(B, states, seeds)
+        rec = np.empty((B, self.result_len)); nu = np.empty((B, self.cfg.N, 3)); stats = np.empty((B, 4))
+        self._check(self.lib.rovmpc_mppi_step_batch(self._h, B, _ptr(st), _ptr(sd), int(step) & 0xFFFFFFFFFFFFFFFF, C.byref(params),
+                                                    _ptr(rec), _ptr(nu), _ptr(stats)))
+        self._mppi_B = B                 # the library took the step, so its batch has B problems
+        return rec, nu, stats
+
+    def mppi_last_batch(self, B: Optional[int] = None):
+        """Host copies of the last batched MPPI iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
+        return self._plan_last_batch(self.lib.rovmpc_mppi_last_batch, B, getattr(self, "_mppi_B", 0), "mppi_last_batch")
+
+    def cem_reset_batch(self, means):
+        """Set the B mean plans (B, N, 3) of the batched CEM; (re)allocates its buffers when B changes."""
+        self._cem_B = self._plan_reset_batch(self.lib.rovmpc_cem_reset_batch, means, "means")
+
+    def cem_step_batch(self, states, seeds, step: int, params: CEMParams):
+        """One CEM control step of B problems: returns (records (B, result_len), mu* (B, N, 3), sigma* (B, N, 3),
+        elites (B, n_elite) int64, stats (B, 4)); problem b's are bit for bit those of ``cem_step`` on its own."""
+        if not isinstance(params, CEMParams):
+            raise TypeError("params must be a CEMParams (CEMParams.make(...))")
+        B = len(seeds)
+        st, sd = self._batch_inputs(B, states, seeds)
+        rec = np.empty((B, self.result_len)); mu = np.empty((B, self.cfg.N, 3)); sg = np.empty((B, self.cfg.N, 3))
+        el = np.empty((B, params.n_elite), dtype=np.int64); stats = np.empty((B, 4))
+        self._check(self.lib.rovmpc_cem_step_batch(self._h, B, _ptr(st), _ptr(sd), int(step) & 0xFFFFFFFFFFFFFFFF, C.byref(params),
+                                                   _ptr(rec), _ptr(mu), _ptr(sg), _ptr(el), _ptr(stats)))
+        self._cem_B = B                  # the library took the step, so its batch has B problems
+        return rec, mu, sg, el, stats
+
+    def cem_last_batch(self, B: Optional[int] = None):
+        """Host copies of the last batched CEM iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
+        return self._plan_last_batch(self.lib.rovmpc_cem_last_batch, B, getattr(self, "_cem_B", 0), "cem_last_batch")
+
     def sampled_candidates(self) -> np.ndarray:
         """Host copy of the candidate tensor of the last ``mpc_step_sampled`` (tests / inspection)."""
         U = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)

@@ -199,6 +199,145 @@ class CEM(_PlanController):
                                      "J0": float(stats[3])})
 
 
+BATCH_MAX = 1024      # problems of a batched controller (PLAN_BATCH_MAX of the library)
+
+
+def batch_plans(value, B: int, N: int, default, name: str) -> np.ndarray:
+    """(B, N, 3) from (B, N, 3), from (N, 3) or (3,) repeated, or from None (``default`` (3,) on every node)."""
+    plan = np.asarray(default if value is None else value, dtype=np.float64)
+    if plan.shape not in ((3,), (N, 3), (B, N, 3)):
+        raise ValueError(f"{name} must have shape ({B}, {N}, 3), ({N}, 3) or (3,), got {plan.shape}")
+    return np.array(np.broadcast_to(plan, (B, N, 3)), dtype=np.float64, order="C")      # a copy of its own
+
+
+def batch_seeds(seeds, seed: int, B: int) -> np.ndarray:
+    """(B,) uint64: the given seeds, or seed + b."""
+    if seeds is None:
+        return (np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + np.arange(B, dtype=np.uint64)).astype(np.uint64)
+    if len(seeds) != B:
+        raise ValueError(f"seeds must have length B = {B} (got {len(seeds)})")
+    return np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds], dtype=np.uint64)
+
+
+def batch_states(states, B: int) -> np.ndarray:
+    """(B, 16) from an array of that shape or from a sequence of B MPCState / dicts / 16 floats."""
+    if isinstance(states, np.ndarray) and states.ndim == 2:
+        st = np.ascontiguousarray(states, dtype=np.float64)
+    else:
+        st = np.stack([state_array(v) for v in states]) if len(states) else np.empty((0, 16))
+    if st.shape != (B, 16):
+        raise ValueError(f"states must be (B, 16) = ({B}, 16) or a sequence of {B} states, got {st.shape}")
+    return st
+
+
+def _config_N(cfg, overrides) -> int:
+    return int(overrides["N"]) if "N" in overrides else (cfg.N if cfg is not None else MPCConfig().N)
+
+
+def check_batch(B, seed: int, seeds, plan, N: int, name: str):
+    """B, the seeds and the shape of the plans of a batched controller, checked before an engine exists (ValueError);
+    returns (B, seeds (B,) uint64)."""
+    if isinstance(B, bool) or int(B) != B or not 1 <= int(B) <= BATCH_MAX:
+        raise ValueError(f"B must be an integer in 1..{BATCH_MAX} (got {B!r})")
+    B = int(B)
+    sd = batch_seeds(seeds, seed, B)
+    if plan is not None and np.shape(plan) not in ((3,), (N, 3), (B, N, 3)):
+        raise ValueError(f"{name} must have shape ({B}, {N}, 3), ({N}, 3) or (3,), got {np.shape(plan)}")
+    return B, sd
+
+
+class _BatchedPlanController(_PlanController):
+    """What BatchedMPPI and BatchedCEM share on top of _PlanController: B, the seeds and the per-problem results."""
+
+    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict):
+        self.B, self.seeds = check_batch(B, seed, seeds, plan, _config_N(cfg, overrides), name)
+        super().__init__(cfg, model, int(self.seeds[0]), overrides)
+        self.records: Optional[np.ndarray] = None
+
+    def _plans(self, value, name: str) -> np.ndarray:
+        return batch_plans(value, self.B, self.cfg.N, self._default_mean, name)
+
+    def _took_steps(self, records, stats: dict) -> np.ndarray:
+        self.step_count += 1
+        self.records = records
+        self.last = [StepResult.from_record(r, self.cfg.N) for r in records]
+        self.last_stats = stats
+        return records[:, 2:5].copy()
+
+
+class BatchedMPPI(_BatchedPlanController):
+    """``ctl = BatchedMPPI(B=64, N=20, K=4096, lam=1.0); u = ctl.step(states)``: B independent MPPI plans, each with its own
+    state, seed (default ``seed + b``) and warm-started nominal, advanced by one library call per control step; lam, std and
+    n_iter are shared.  Problem b's results are bit for bit those of ``MPPI(seed=seeds[b], nominal=nominal[b])`` on its own
+    (include/rovmpc.h, rovmpc_mppi_step_batch).  ``nominal``: (B, N, 3), or (N, 3) / (3,) repeated; default the scaler mean.
+    ``step(states)`` takes (B, 16) or a sequence of B states and returns u (B, 3).  After it: ``records`` (B, result_len),
+    ``last`` (a list of StepResult), ``nominal`` (B, N, 3), ``last_stats`` (rho, eta, ess, J0: arrays of length B)."""
+
+    def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int, lam: float = 1.0,
+                 std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, **overrides):
+        self.std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
+        self.params = _lib.MPPIParams.make(n_iter, lam, self.std)        # ValueError before the library is called
+        self.lam, self.n_iter = float(lam), int(n_iter)
+        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides)
+        self.nominal: Optional[np.ndarray] = None
+        self.reset(nominal)
+
+    def reset(self, nominal=None):
+        nu = self._plans(nominal, "nominal")
+        self.engine.mppi_reset_batch(nu)
+        self.nominal = nu.copy()
+
+    def step(self, states) -> np.ndarray:
+        st = batch_states(states, self.B)
+        rec, self.nominal, stats = self.engine.mppi_step_batch(st, self.seeds, self.step_count, self.params)
+        return self._took_steps(rec, {"rho": stats[:, 0].copy(), "eta": stats[:, 1].copy(), "ess": stats[:, 2].copy(),
+                                      "J0": stats[:, 3].copy()})
+
+    def candidates(self):
+        """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
+        return self.engine.mppi_last_batch()
+
+
+class BatchedCEM(_BatchedPlanController):
+    """``ctl = BatchedCEM(B=64, N=20, K=4096, n_elite=64); u = ctl.step(states)``: B independent CEM plans, each with its own
+    state, seed (default ``seed + b``) and warm-started mean, advanced by one library call per control step; the parameters
+    of ``CEM`` are shared.  Problem b's results are bit for bit those of ``CEM(seed=seeds[b], mean=mean[b])`` on its own
+    (include/rovmpc.h, rovmpc_cem_step_batch).  After ``step``: ``records``, ``last`` (a list of StepResult), ``mean`` and
+    ``std`` (B, N, 3), ``elites`` (B, n_elite), ``last_stats`` (J_best, J_worst_elite, n_finite, J0: arrays of length B)."""
+
+    def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int,
+                 n_elite: Optional[int] = None, n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0),
+                 lo=(-np.inf,) * 3, hi=(np.inf,) * 3, seed: int = 20250523, seeds=None, mean=None, reserved: int = 0, **overrides):
+        K = int(overrides["K"]) if "K" in overrides else (cfg.K if cfg is not None else MPCConfig().K)
+        if n_elite is None:
+            n_elite = max(K // 64, 1)
+        if isinstance(n_elite, bool) or int(n_elite) != n_elite or int(n_elite) > K:
+            raise ValueError(f"n_elite must be an integer <= K = {K} (got {n_elite!r})")
+        std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
+        self.params = _lib.CEMParams.make(n_iter, n_elite, alpha, std, std_min, lo, hi, reserved)   # ValueError before the library is called
+        self.n_iter, self.n_elite, self.alpha = int(n_iter), int(n_elite), float(alpha)
+        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides)
+        self.mean: Optional[np.ndarray] = None
+        self.std: Optional[np.ndarray] = None
+        self.elites: Optional[np.ndarray] = None
+        self.reset(mean)
+
+    def reset(self, mean=None):
+        mu = self._plans(mean, "mean")
+        self.engine.cem_reset_batch(mu)
+        self.mean = mu.copy()
+
+    def step(self, states) -> np.ndarray:
+        st = batch_states(states, self.B)
+        rec, self.mean, self.std, self.elites, stats = self.engine.cem_step_batch(st, self.seeds, self.step_count, self.params)
+        return self._took_steps(rec, {"J_best": stats[:, 0].copy(), "J_worst_elite": stats[:, 1].copy(),
+                                      "n_finite": stats[:, 2].astype(np.int64), "J0": stats[:, 3].copy()})
+
+    def candidates(self):
+        """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
+        return self.engine.cem_last_batch()
+
+
 def synthetic_problem(K: int, N: int, seed: int = 20250523, dtype=np.float64):
     """The synthetic MPC step of SURVEY section 8(d) / BASELINE.md section 3: state at the scaler means,
     candidates drawn from the scaler statistics of x3..x5.  Returns (state(16,), U(K,N,3))."""

@@ -218,7 +218,7 @@ int rovmpc_sample_candidates_device(rovmpc_handle *h, uint64_t seed, uint64_t st
  * rovmpc_step / rovmpc_mpc_step_sampled on the same handle give the same bits with or without MPPI steps in between.
  * Errors: ROVMPC_ERR_INVALID for bad parameters, a struct_size mismatch or a step before the first reset;
  * ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
- * Not provided: sharded MPPI (it needs an all-reduce of the 3 N + 3 partials), batched and closed-loop device entries,
+ * Not provided: sharded MPPI (it needs an all-reduce of the 3 N + 3 partials), closed-loop device entries,
  * sampling folded into the fused sampled rollout kernel, control bounds. */
 typedef struct rovmpc_mppi_params {
     int32_t struct_size;        /* = sizeof(rovmpc_mppi_params), ABI check                  */
@@ -266,7 +266,7 @@ int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, const void *d_U
  * or without CEM steps in between.
  * Errors: ROVMPC_ERR_INVALID for parameters outside the ranges below (n_elite > cfg.K included), a struct_size mismatch or a
  * step before the first reset, before anything is launched; ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
- * Not provided: sharded CEM, batched and closed-loop device entries. */
+ * Not provided: sharded CEM, closed-loop device entries. */
 typedef struct rovmpc_cem_params {
     int32_t struct_size;        /* = sizeof(rovmpc_cem_params), ABI check                   */
     int32_t n_iter;             /* iterations per control step, 1..64                       */
@@ -293,6 +293,44 @@ int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const void *d_U,
                              const double *d_mean_in, const double *d_std_in, double *d_mean_out, double *d_std_out,
                              int64_t *d_elite_out, double *d_stats, void *stream);
 
+/* ---- batched MPPI and CEM: B independent plans, each with its own state, seed and warm-started plan, advanced one control
+ * step by one call with one host wait (a fleet of ROVs, an ensemble of state hypotheses, several seeds) --------------------
+ * Law.  For every b, every output of rovmpc_mppi_step_batch is bit for bit what rovmpc_mppi_step(states[b], seeds[b], step, p)
+ * returns (the MPPI law above) on a handle of the same configuration and model that was reset with nominals[b] and has taken
+ * the same earlier steps: the record, nu*, the stats, the kept shifted nominal, and the last candidates and costs
+ * (rovmpc_mppi_last_batch against rovmpc_mppi_last).  Likewise rovmpc_cem_step_batch against rovmpc_cem_step (the CEM law
+ * above): record, mu*, sigma*, the elite list in rank order with -1 padding, stats, kept mean, last candidates and costs.
+ * The parameters, `step` and n_iter are shared by the batch; states, seeds and plans are per problem.  A problem whose costs
+ * are all non-finite keeps its plan bit for bit and reports the single-problem stats of that case; it has no effect on any
+ * other problem, and permuting the problems permutes the outputs and changes nothing else.
+ * Per iteration there are three launches for the whole batch (sampler and update with the problem on the grid's second
+ * axis, the rollout of rovmpc_step_batch_device), no host round trip between iterations; states and seeds cross once per
+ * step through one block of mapped host memory.
+ * State.  The batched controllers own their buffers (U[B][K][N][3], J[B][K], states, records, plans and spreads, a slab
+ * and a ticket per problem, a mailbox of B rows), allocated at rovmpc_*_reset_batch and again, after a device synchronise,
+ * when B changes.  The single-problem plan of rovmpc_mppi_reset / rovmpc_cem_reset and the batched plans are separate, and
+ * steps of rovmpc_step / rovmpc_mpc_step_sampled / rovmpc_mppi_step / rovmpc_cem_step / rovmpc_step_batch_device on the same
+ * handle give the same bits with or without batched controller steps in between, and the other way round.
+ * Errors, before anything is launched: ROVMPC_ERR_INVALID for B outside 1..1024, a null required pointer, a step before the
+ * batched reset or with a B other than the reset's, a struct_size mismatch and the parameter ranges of the single-problem
+ * entries; ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.  A failed allocation is ROVMPC_ERR_HIP and leaves the
+ * previous batched state usable. */
+/* nominals[B][N][3] (host, double). */
+int rovmpc_mppi_reset_batch(rovmpc_handle *h, int32_t B, const double *nominals);
+/* One control step of all B problems (blocking): states[B], seeds[B], records_out[B][result_len]; nominals_out[B][N][3] and
+ * stats_out[B][4] may be NULL. */
+int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                           const rovmpc_mppi_params *p, double *records_out, double *nominals_out, double *stats_out);
+/* Host copies of the last iteration's candidates U[B][K][N][3] and costs J[B][K] (reals of cfg.dtype); either may be NULL. */
+int rovmpc_mppi_last_batch(rovmpc_handle *h, void *U_out, void *J_out);
+/* means[B][N][3] (host, double). */
+int rovmpc_cem_reset_batch(rovmpc_handle *h, int32_t B, const double *means);
+/* As rovmpc_mppi_step_batch; means_out[B][N][3], stds_out[B][N][3], elites_out[B][n_elite] and stats_out[B][4] may be NULL. */
+int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                          const rovmpc_cem_params *p, double *records_out, double *means_out, double *stds_out,
+                          int64_t *elites_out, double *stats_out);
+int rovmpc_cem_last_batch(rovmpc_handle *h, void *U_out, void *J_out);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
@@ -311,7 +349,8 @@ int rovmpc_step_device(rovmpc_handle *h, const double *d_state, const void *d_U,
  * of the reference's per-frame loop over independent states (catenary_from_data.py:40-50), and the way to fill the
  * chip when one problem (K = 4096) is only one workgroup per CU.  Problem b's record is bit-identical to
  * rovmpc_step_device on (d_states[b], d_U[b]).  rovmpc_batch_costs_device returns the device pointer of the costs
- * J[B][K] of the last batched launch (reals of cfg.dtype; valid until the next launch on the handle). */
+ * J[B][K] of the last batched launch (reals of cfg.dtype; valid until the next launch on the handle).  The batched MPPI and
+ * CEM steps write their costs into buffers of their own (rovmpc_*_last_batch) and do not change what it returns. */
 int rovmpc_step_batch_device(rovmpc_handle *h, int32_t B, const double *d_states, const void *d_U,
                              double *d_results, void *stream);
 int rovmpc_batch_costs_device(rovmpc_handle *h, const void **d_J);
