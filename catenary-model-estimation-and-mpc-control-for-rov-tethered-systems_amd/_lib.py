@@ -139,6 +139,12 @@ _SIGNATURES = {
     "rovmpc_cem_reset_batch": (C.c_int, [_P, C.c_int32, _P]),
     "rovmpc_cem_step_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint64, C.POINTER(CEMParams), _P, _P, _P, _P, _P]),
     "rovmpc_cem_last_batch": (C.c_int, [_P, _P, _P]),
+    "rovmpc_mppi_row_len": (C.c_int32, [_P]),
+    "rovmpc_cem_row_len": (C.c_int32, [_P, C.c_int32]),
+    "rovmpc_mppi_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P]),
+    "rovmpc_cem_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(CEMParams), _P]),
+    "rovmpc_mppi_closed_loop_batch_device": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_uint64, C.POINTER(MPPIParams), _P]),
+    "rovmpc_cem_closed_loop_batch_device": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_uint64, C.POINTER(CEMParams), _P]),
     "rovmpc_mpc_step_sampled": (C.c_int, [_P, C.POINTER(State), C.c_uint64, C.c_uint64, _P, _P, C.c_int32, _P]),
     "rovmpc_sampled_candidates": (C.c_int, [_P, _P]),
     "rovmpc_sample_candidates_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P]),

@@ -95,6 +95,25 @@ def state_of_step(rows: np.ndarray, report: "ClosedLoopReport", i: int, feedback
     return st
 
 
+def run_plan_closed_loop(controller, exp_case: int = 12, n_steps: int = 1000, feedback: bool = False, seed: int = 0) -> ClosedLoopReport:
+    """The closed loop of ``run_closed_loop`` driven by a controller that keeps a plan (``MPPI`` or ``CEM``): the measured rows
+    of ``closed_loop_inputs``, all ``n_steps`` control steps and the plant update by one library call (``controller.run``).
+    The report's ``u`` is the control each step returned (nu*[0] / clamp(mu*[0])); ``cost``, ``index`` and ``theta_gamma``
+    are those of each step's last rollout.  The wall time includes the transfer of the rows."""
+    if hasattr(controller, "B"):
+        raise ValueError("run_plan_closed_loop takes a single-problem controller (MPPI or CEM); a batched one has `run` itself")
+    rows, _ = closed_loop_inputs(controller.engine, exp_case, n_steps, seed)
+    cfg = controller.cfg
+    t_start = _time.perf_counter()
+    res = controller.run(rows, feedback)
+    wall = _time.perf_counter() - t_start
+    rec = res.records
+    tg = np.vstack([rec[0, 5:7], rec[:, 7:9]])
+    sim = n_steps * cfg.dt
+    return ClosedLoopReport(n_steps, wall, sim, sim / wall, n_steps * controller.n_iter * cfg.K * cfg.N / wall, rec[:, 2:5].copy(), tg,
+                            rec[:, 0].copy(), rec[:, 1].astype(np.int64))
+
+
 def run_closed_loop(engine: Engine, exp_case: int = 12, n_steps: int = 1000, n_pools: int = 8,
                     seed: int = 0, k_offset: int = 0, feedback: bool = False, mode: str = "", pools=None) -> ClosedLoopReport:
     """Runs the loop on ``engine``'s device.  If the engine has a native communicator

@@ -13,6 +13,7 @@ RV_DEV double cem_clamp(double v, double lo, double hi) { return ::fmin(::fmax(v
 struct CemSampleArgs {
     rovmpc_state state;                 // written to d_state by block 0 (null d_state: not written)
     double *d_state;
+    const double *state_src;            // not null: d_state <- these 16 doubles in device memory instead (first step of a device loop)
     unsigned long long seed, counter;
     double std[3], lo[3], hi[3];
     long long total;                    // K * N * 3
@@ -46,7 +47,7 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 cem_sample_kernel(const CemSampleArgs a, T *__restrict__ U) {
     if (a.d_state && blockIdx.x == 0 && threadIdx.x < ROVMPC_STATE_LEN)
-        a.d_state[threadIdx.x] = reinterpret_cast<const double *>(&a.state)[threadIdx.x];
+        a.d_state[threadIdx.x] = a.state_src ? a.state_src[threadIdx.x] : reinterpret_cast<const double *>(&a.state)[threadIdx.x];
     cem_sample_body<T>(a.seed, a.counter, a.std, a.lo, a.hi, a.total, a.N, a.mu, a.sigma, U);
 }
 
@@ -108,6 +109,9 @@ struct CemUpdateArgs {
     double *host_out;
     long long *host_elite;
     unsigned long long *done_flag, done_seq;
+    // a step of a device loop (see PlanHandoff): loop.row = [record (R), mu* (3N), sigma* (3N), stats (4), elite list (E, as
+    // int64)]; only the loop's last step has a mailbox (host_out, host_elite and done_flag null otherwise)
+    PlanHandoff loop;
 };
 
 struct CemShared {
@@ -387,14 +391,23 @@ RV_DEV void cem_update_body(const CemUpdateArgs &a, const PlanBatchAt &at) {
     if (a.record && wv == 0) {
         // the control to apply is clamp(mu*[0]); the rest of the record is the last rollout's
         auto u = [&](int c) { return cem_clamp(s.mu[c], a.lo[c], a.hi[c]); };
-        double *record = a.record + at.b * a.R, *o = a.host_out + at.b * at.host_stride;
-        long long *host_elite = a.host_elite + at.b * at.host_stride;
+        double *record = a.record + at.b * a.R;
         if (lane < 3) record[2 + lane] = u(lane);
-        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? u(i - 2) : record[i];
-        for (int c = lane; c < C3; c += 64) { o[a.R + c] = s.mu[c]; o[a.R + C3 + c] = s.sg[c]; }
-        for (int i = lane; i < a.E; i += 64) host_elite[i] = i < nE ? s.ridx[i] : -1;
-        if (lane == 0) { o[a.R + 2 * C3] = st0; o[a.R + 2 * C3 + 1] = st1; o[a.R + 2 * C3 + 2] = st2; o[a.R + 2 * C3 + 3] = st3; }
-        plan_publish(a.done_flag, a.done_seq, at.step_ticket, at.B);          // (see mppi_update_body)
+        auto row_to = [&](double *o, long long *elite) {
+            for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? u(i - 2) : record[i];
+            for (int c = lane; c < C3; c += 64) { o[a.R + c] = s.mu[c]; o[a.R + C3 + c] = s.sg[c]; }
+            for (int i = lane; i < a.E; i += 64) elite[i] = i < nE ? s.ridx[i] : -1;
+            if (lane == 0) { o[a.R + 2 * C3] = st0; o[a.R + 2 * C3 + 1] = st1; o[a.R + 2 * C3 + 2] = st2; o[a.R + 2 * C3 + 3] = st3; }
+        };
+        if (a.loop.row) {
+            double *o = a.loop.row + at.b * a.loop.row_stride;
+            row_to(o, reinterpret_cast<long long *>(o + a.R + 2 * C3 + 4));
+            plan_handoff_state(a.loop, at.b, record);
+        }
+        if (a.host_out) {
+            row_to(a.host_out + at.b * at.host_stride, a.host_elite + at.b * at.host_stride);
+            plan_publish(a.done_flag, a.done_seq, at.step_ticket, at.B);          // (see mppi_update_body)
+        }
     }
 }
 

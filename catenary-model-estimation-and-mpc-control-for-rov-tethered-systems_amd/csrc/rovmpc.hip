@@ -1457,41 +1457,75 @@ static int plan_rollout(rovmpc_handle *h, PlanCtl &c) {
     return rc;
 }
 
+// A device-resident closed loop around the control steps (rovmpc_*_closed_loop*_device): T steps from the measured rows
+// d_exo [T][16] ([B][T][16] in a batch), each step's row into d_rows [T][W] ([T][B][W]).  PlanLoop{}: one step from a host state.
+struct PlanLoop {
+    const double *d_exo = nullptr;
+    long long T = 1;
+    int feedback = 0;
+    double *d_rows = nullptr;
+    size_t W = 0;
+};
+
+// The argument checks the four loop entries share, before anything is launched
+static int plan_loop_check(rovmpc_handle *h, const char *fn, const void *d_exo, int64_t T, int32_t feedback, const void *d_rows) {
+    if (!d_exo || !d_rows) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (d_exo or d_rows)", fn);
+    if (T < 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: T must be >= 1 (got %lld)", fn, (long long)T);
+    if (feedback != 0 && feedback != 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: feedback must be 0 or 1 (got %d)", fn, feedback);
+    return ROVMPC_OK;
+}
+
 // What the loop hands the two launches of iteration i.  The last group is set in the last iteration only (the update then
 // also shifts the plan by one node, passes the rollout's record on and fills the mailbox); *_update_device passes PlanIter{}.
 struct PlanIter {
-    const rovmpc_state *state = nullptr;   // iteration 0 only (the sampler stores it for the step's rollouts)
+    bool first = false;                    // iteration 0 of its step (CEM: the spread restarts from std)
+    const rovmpc_state *state = nullptr;   // iteration 0 of a single step only (the sampler stores it for the step's rollouts)
+    const double *state_src = nullptr;     // iteration 0 of a loop's first step only: the same from device memory
     uint64_t counter = 0;                  // of the draw: step * n_iter + i (wraps)
     size_t in = 0, out = 0;                // offsets of the halves of plan (and spread) the iteration reads and writes
     int shift = 0;
-    double *record = nullptr, *host_out = nullptr;
+    double *record = nullptr, *host_out = nullptr;     // host_out, done_flag: a single step, or the last step of a loop
     unsigned long long *done_flag = nullptr, done_seq = 0;
+    PlanHandoff loop = {};                 // a loop's steps: the row in device memory and the next step's state
 };
 
-// rovmpc_*_step: n_iter x (sample, rollout, update) on the handle's stream without a host round trip, then one wait for the
-// mailbox.  sample(it) and update(it) launch the controller's kernels.
+// rovmpc_*_step and rovmpc_*_closed_loop_device: loop.T x n_iter x (sample, rollout, update) on the handle's stream without a
+// host round trip, then one wait for the mailbox, which the last step's last update fills.  sample(it) and update(it)
+// launch the controller's kernels.
 template <typename Sample, typename Update>
-static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *state, uint64_t step, int n_iter, Sample sample, Update update) {
+static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *state, const PlanLoop &loop, uint64_t step, int n_iter,
+                     Sample sample, Update update) {
     int rc;
     if ((rc = check_single_gpu(h, c.name))) return rc;
-    if (!c.allocated) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_step before rovmpc_%s_reset", c.abi, c.abi);
+    if (!c.allocated) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_%s before rovmpc_%s_reset", c.abi, loop.d_rows ? "closed_loop_device" : "step", c.abi);
     if ((rc = check_ready(h))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t C3 = 3 * (size_t)h->cfg.N;
     const unsigned long long seq = ++c.box.seq;
     int cur = c.cur;
-    for (int i = 0; i < n_iter; ++i) {
-        PlanIter it;
-        it.state = i == 0 ? state : nullptr; it.counter = step * (uint64_t)n_iter + (uint64_t)i;
-        it.in = cur * C3; it.out = (cur ^ 1) * C3; it.done_seq = seq;
-        if (i + 1 == n_iter) { it.shift = 1; it.record = c.record; it.host_out = c.box.d_out; it.done_flag = c.box.d_done; }
-        if ((rc = sample(it))) return rc;
-        if ((rc = plan_rollout(h, c))) return rc;
-        if ((rc = update(it))) return rc;
-        cur ^= 1;
+    for (long long t = 0; t < loop.T; ++t) {
+        const bool last_step = t + 1 == loop.T;
+        for (int i = 0; i < n_iter; ++i) {
+            PlanIter it;
+            it.first = i == 0;
+            if (i == 0 && t == 0) { it.state = state; it.state_src = loop.d_exo; }
+            it.counter = (step + (uint64_t)t) * (uint64_t)n_iter + (uint64_t)i;
+            it.in = cur * C3; it.out = (cur ^ 1) * C3; it.done_seq = seq;
+            if (i + 1 == n_iter) {
+                it.shift = 1; it.record = c.record;
+                if (last_step) { it.host_out = c.box.d_out; it.done_flag = c.box.d_done; }
+                if (loop.d_rows)
+                    it.loop = PlanHandoff{loop.d_rows + (size_t)t * loop.W, last_step ? nullptr : loop.d_exo + (size_t)(t + 1) * ROVMPC_STATE_LEN,
+                                          c.state, loop.feedback, 0, 0};
+            }
+            if ((rc = sample(it))) return rc;
+            if ((rc = plan_rollout(h, c))) return rc;
+            if ((rc = update(it))) return rc;
+            cur ^= 1;
+        }
     }
     c.cur = cur;
-    ++c.steps;
+    c.steps += (unsigned long long)loop.T;
     return mailbox_wait(h, c.box, seq, c.step_name);
 }
 
@@ -1527,6 +1561,7 @@ static int launch_mppi_update(rovmpc_handle *h, const void *d_J, const void *d_U
     a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.lambda = lambda;
     a.nu_in = nu_in; a.nu_out = nu_out; a.shift = pub.shift; a.stats = stats; a.slab = (double *)slab.rows; a.ticket = slab.ticket;
     a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
+    a.loop = pub.loop;
     LAUNCH_T_QC(mppi_update_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
     return launched(h, "MPPI update");
 }
@@ -1537,11 +1572,12 @@ extern "C" int rovmpc_mppi_reset(rovmpc_handle *h, const double *nominal) {
     return plan_reset(h, h->mppi, nominal, mppi_slab_bytes(h), 3 * (size_t)h->cfg.N + 4, false);   // mailbox: record, nu*, stats
 }
 
-static int launch_mppi_sample(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t counter, const double *std3,
-                              const double *nu) {
+static int launch_mppi_sample(rovmpc_handle *h, const PlanIter &it, uint64_t seed, const double *std3, const double *nu) {
+    const uint64_t counter = it.counter;
     MppiSampleArgs sa;
     memset(&sa, 0, sizeof(sa));
-    if (state) { sa.state = *state; sa.d_state = h->mppi.state; }
+    if (it.state) { sa.state = *it.state; sa.d_state = h->mppi.state; }
+    if (it.state_src) { sa.state_src = it.state_src; sa.d_state = h->mppi.state; }
     sa.seed = seed; sa.counter = counter;
     for (int i = 0; i < 3; ++i) sa.std[i] = std3[i];
     sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.nu = nu;
@@ -1551,6 +1587,16 @@ static int launch_mppi_sample(rovmpc_handle *h, const rovmpc_state *state, uint6
     return launched(h, "MPPI sampler");
 }
 
+// one step from a host state, or a device loop of loop.T steps
+static int mppi_run(rovmpc_handle *h, const rovmpc_state *state, const PlanLoop &loop, uint64_t seed, uint64_t step, const rovmpc_mppi_params *p) {
+    PlanCtl &c = h->mppi;
+    return plan_step(h, c, state, loop, step, p->n_iter,
+                     [&](const PlanIter &it) { return launch_mppi_sample(h, it, seed, p->std, c.plan + it.in); },
+                     [&](const PlanIter &it) {
+                         return launch_mppi_update(h, c.J, c.U, p->lambda, c.plan + it.in, c.plan + it.out, nullptr, c.slab, it, h->stream);
+                     });
+}
+
 extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step,
                                 const rovmpc_mppi_params *p, double *record_out, double *nominal_out, double *stats_out) {
     if (!h) return ROVMPC_ERR_INVALID;
@@ -1558,17 +1604,26 @@ extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uin
     int rc = mppi_check_params(h, p);
     if (rc) return rc;
     PlanCtl &c = h->mppi;
-    rc = plan_step(h, c, state, step, p->n_iter,
-                   [&](const PlanIter &it) { return launch_mppi_sample(h, it.state, seed, it.counter, p->std, c.plan + it.in); },
-                   [&](const PlanIter &it) {
-                       return launch_mppi_update(h, c.J, c.U, p->lambda, c.plan + it.in, c.plan + it.out, nullptr, c.slab, it, h->stream);
-                   });
-    if (rc) return rc;
+    if ((rc = mppi_run(h, state, PlanLoop{}, seed, step, p))) return rc;
     const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
     const double *o = c.box.h_out;
     memcpy(record_out, o, R * sizeof(double));
     if (nominal_out) memcpy(nominal_out, o + R, C3 * sizeof(double));
     if (stats_out) memcpy(stats_out, o + R + C3, 4 * sizeof(double));
+    return take_device_errors(h);
+}
+
+// row of a control step: record, nu* (3N), stats (4) -- the mailbox row of a batched problem too
+static size_t mppi_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 3 * (size_t)h->cfg.N + 4; }
+
+extern "C" int32_t rovmpc_mppi_row_len(const rovmpc_handle *h) { return h ? (int32_t)mppi_row_words(h) : 0; }
+
+extern "C" int rovmpc_mppi_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, int32_t feedback, uint64_t seed,
+                                              uint64_t step0, const rovmpc_mppi_params *p, double *d_rows) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = plan_loop_check(h, "rovmpc_mppi_closed_loop_device", d_exo, T, feedback, d_rows);
+    if (rc || (rc = mppi_check_params(h, p))) return rc;
+    if ((rc = mppi_run(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, mppi_row_words(h)}, seed, step0, p))) return rc;
     return take_device_errors(h);
 }
 
@@ -1630,6 +1685,7 @@ static int launch_cem_update(rovmpc_handle *h, const void *d_J, const void *d_U,
     a.elite = elite; a.stats = stats; a.slab = (unsigned long long *)slab.rows; a.ticket = slab.ticket;
     a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.host_elite = host_elite;
     a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
+    a.loop = pub.loop;
     LAUNCH_T_QC(cem_update_kernel, h, a.C3 > CEM_NT, dim3(g.G), dim3(CEM_NT), 0, s, a);
     return launched(h, "CEM update");
 }
@@ -1641,11 +1697,13 @@ extern "C" int rovmpc_cem_reset(rovmpc_handle *h, const double *mean) {
     return plan_reset(h, h->cem, mean, cem_slab_bytes(h), 6 * (size_t)h->cfg.N + 4 + CEM_MAX_ELITE, true);
 }
 
-static int launch_cem_sample(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t counter, const rovmpc_cem_params *p,
+static int launch_cem_sample(rovmpc_handle *h, const PlanIter &it, uint64_t seed, const rovmpc_cem_params *p,
                              const double *mu, const double *sigma) {
+    const uint64_t counter = it.counter;
     CemSampleArgs sa;
     memset(&sa, 0, sizeof(sa));
-    if (state) { sa.state = *state; sa.d_state = h->cem.state; }
+    if (it.state) { sa.state = *it.state; sa.d_state = h->cem.state; }
+    if (it.state_src) { sa.state_src = it.state_src; sa.d_state = h->cem.state; }
     sa.seed = seed; sa.counter = counter;
     for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
     sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.mu = mu; sa.sigma = sigma;
@@ -1653,6 +1711,21 @@ static int launch_cem_sample(rovmpc_handle *h, const rovmpc_state *state, uint64
     if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(cem_sample_kernel<double>, grid, bs, 0, h->stream, sa, (double *)h->cem.U);
     else hipLaunchKernelGGL(cem_sample_kernel<float>, grid, bs, 0, h->stream, sa, (float *)h->cem.U);
     return launched(h, "CEM sampler");
+}
+
+// one step from a host state, or a device loop of loop.T steps
+static int cem_run(rovmpc_handle *h, const rovmpc_state *state, const PlanLoop &loop, uint64_t seed, uint64_t step, const rovmpc_cem_params *p) {
+    PlanCtl &c = h->cem;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    return plan_step(h, c, state, loop, step, p->n_iter,
+                     [&](const PlanIter &it) {                                   // sigma_0 = std
+                         return launch_cem_sample(h, it, seed, p, c.plan + it.in, it.first ? nullptr : c.spread + it.in);
+                     },
+                     [&](const PlanIter &it) {
+                         return launch_cem_update(h, c.J, c.U, p, c.plan + it.in, it.first ? nullptr : c.spread + it.in, c.plan + it.out,
+                                                  c.spread + it.out, nullptr, nullptr, c.slab, it,
+                                                  it.host_out ? (long long *)(it.host_out + R + 2 * C3 + 4) : nullptr, h->stream);
+                     });
 }
 
 extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const rovmpc_cem_params *p,
@@ -1663,22 +1736,29 @@ extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint
     if (rc) return rc;
     PlanCtl &c = h->cem;
     const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    rc = plan_step(h, c, state, step, p->n_iter,
-                   [&](const PlanIter &it) {                                   // sigma_0 = std
-                       return launch_cem_sample(h, it.state, seed, it.counter, p, c.plan + it.in, it.state ? nullptr : c.spread + it.in);
-                   },
-                   [&](const PlanIter &it) {
-                       return launch_cem_update(h, c.J, c.U, p, c.plan + it.in, it.state ? nullptr : c.spread + it.in, c.plan + it.out,
-                                                c.spread + it.out, nullptr, nullptr, c.slab, it,
-                                                it.host_out ? (long long *)(it.host_out + R + 2 * C3 + 4) : nullptr, h->stream);
-                   });
-    if (rc) return rc;
+    if ((rc = cem_run(h, state, PlanLoop{}, seed, step, p))) return rc;
     const double *o = c.box.h_out;
     memcpy(record_out, o, R * sizeof(double));
     if (mean_out) memcpy(mean_out, o + R, C3 * sizeof(double));
     if (std_out) memcpy(std_out, o + R + C3, C3 * sizeof(double));
     if (stats_out) memcpy(stats_out, o + R + 2 * C3, 4 * sizeof(double));
     if (elite_out) memcpy(elite_out, o + R + 2 * C3 + 4, (size_t)p->n_elite * sizeof(int64_t));
+    return take_device_errors(h);
+}
+
+// row of a loop's control step: record, mu* (3N), sigma* (3N), stats (4), the elite list (n_elite, int64)
+static size_t cem_loop_row_words(const rovmpc_handle *h, int n_elite) { return (size_t)rovmpc_result_len(h) + 6 * (size_t)h->cfg.N + 4 + (size_t)n_elite; }
+
+extern "C" int32_t rovmpc_cem_row_len(const rovmpc_handle *h, int32_t n_elite) {
+    return h && n_elite >= 1 && n_elite <= CEM_MAX_ELITE ? (int32_t)cem_loop_row_words(h, n_elite) : 0;
+}
+
+extern "C" int rovmpc_cem_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, int32_t feedback, uint64_t seed,
+                                             uint64_t step0, const rovmpc_cem_params *p, double *d_rows) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = plan_loop_check(h, "rovmpc_cem_closed_loop_device", d_exo, T, feedback, d_rows);
+    if (rc || (rc = cem_check_params(h, p))) return rc;
+    if ((rc = cem_run(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, cem_loop_row_words(h, p->n_elite)}, seed, step0, p))) return rc;
     return take_device_errors(h);
 }
 
@@ -1742,58 +1822,67 @@ struct PlanBatchIter {
     PlanBatchIn in;                        // stage set in iteration 0 only
     uint64_t counter = 0;
     size_t in_off = 0, out_off = 0;        // offsets of the halves of plan (and spread): [B][3N] each
-    bool first = false, last = false;
+    bool first = false, last = false;      // of its step
+    bool publish = false;                  // last, and the step has a mailbox: a single step, or the last step of a loop
     unsigned long long done_seq = 0;
+    PlanHandoff loop = {};                 // a loop's steps (last iteration): the rows in device memory and the next states
 };
 
 // The checks of a batched step that need no parameters, before anything is launched
-static int plan_batch_ready(rovmpc_handle *h, PlanBatch &c, const char *fn, int B, const rovmpc_state *states, const uint64_t *seeds,
-                            const double *records_out) {
+// (null_arg: one of the entry's required pointers, which `args` names, is null)
+static int plan_batch_ready(rovmpc_handle *h, PlanBatch &c, const char *fn, int B, bool null_arg, const char *args) {
     int rc;
     if ((rc = check_batch_size(h, fn, B))) return rc;
-    if (!states || !seeds || !records_out) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer", fn);
+    if (null_arg) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (%s)", fn, args);
     if ((rc = check_single_gpu(h, c.name))) return rc;
     if (c.B == 0) FAIL(h, ROVMPC_ERR_INVALID, "%s before rovmpc_%s_reset_batch", fn, c.abi);
     if (B != c.B) FAIL(h, ROVMPC_ERR_INVALID, "%s: B = %d but rovmpc_%s_reset_batch made %d problems", fn, B, c.abi, c.B);
     return ROVMPC_OK;
 }
 
-// rovmpc_*_step_batch: states and seeds into the staging block, n_iter x (sample, batched rollout, update) on the handle's
-// stream without a host round trip, then one wait for the whole batch's mailbox.
+// rovmpc_*_step_batch and rovmpc_*_closed_loop_batch_device: seeds (and, for a single step, states) into the staging block,
+// loop.T x n_iter x (sample, batched rollout, update) on the handle's stream without a host round trip, then one wait for
+// the whole batch's mailbox, which the last step's last update fills.  In a loop (states null) the first sampler takes the
+// states from row 0 of each problem's exo trajectory and every later step finds them where its predecessor left them.
 template <typename Sample, typename Update>
-static int plan_step_batch(rovmpc_handle *h, PlanBatch &c, const rovmpc_state *states, const uint64_t *seeds, uint64_t step, int n_iter,
-                           Sample sample, Update update) {
+static int plan_step_batch(rovmpc_handle *h, PlanBatch &c, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds,
+                           uint64_t step, int n_iter, Sample sample, Update update) {
     int rc;
     if ((rc = check_ready(h))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
     const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N;
-    memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
+    if (states) memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
     memcpy(c.h_stage + B * ROVMPC_STATE_LEN, seeds, B * sizeof(uint64_t));
+    const size_t exo_stride = (size_t)loop.T * ROVMPC_STATE_LEN;
     const unsigned long long seq = ++c.box.seq;
     int cur = c.cur;
-    for (int i = 0; i < n_iter; ++i) {
-        PlanBatchIter it;
-        it.in = PlanBatchIn{i == 0 ? c.d_stage : nullptr, c.state, c.seeds, c.B};
-        it.counter = step * (uint64_t)n_iter + (uint64_t)i;
-        it.in_off = cur * half; it.out_off = (cur ^ 1) * half; it.first = i == 0; it.last = i + 1 == n_iter; it.done_seq = seq;
-        if ((rc = sample(it))) return rc;
-        const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
-        h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
-        rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream, c.B);
-        h->arg_J = nullptr;
-        h->last_batch = last_batch;
-        if (rc) return rc;
-        if ((rc = update(it))) return rc;
-        cur ^= 1;
+    for (long long t = 0; t < loop.T; ++t) {
+        const bool last_step = t + 1 == loop.T;
+        for (int i = 0; i < n_iter; ++i) {
+            PlanBatchIter it;
+            it.in = PlanBatchIn{i == 0 && t == 0 ? c.d_stage : nullptr, c.state, c.seeds, c.B, loop.d_exo, exo_stride};
+            it.counter = (step + (uint64_t)t) * (uint64_t)n_iter + (uint64_t)i;
+            it.in_off = cur * half; it.out_off = (cur ^ 1) * half; it.first = i == 0; it.last = i + 1 == n_iter; it.done_seq = seq;
+            it.publish = it.last && last_step;
+            if (it.last && loop.d_rows)
+                it.loop = PlanHandoff{loop.d_rows + (size_t)t * B * loop.W, last_step ? nullptr : loop.d_exo + (size_t)(t + 1) * ROVMPC_STATE_LEN,
+                                      c.state, loop.feedback, loop.W, exo_stride};
+            if ((rc = sample(it))) return rc;
+            const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
+            h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
+            rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream, c.B);
+            h->arg_J = nullptr;
+            h->last_batch = last_batch;
+            if (rc) return rc;
+            if ((rc = update(it))) return rc;
+            cur ^= 1;
+        }
     }
     c.cur = cur;
-    ++c.steps;
+    c.steps += (unsigned long long)loop.T;
     return mailbox_wait(h, c.box, seq, c.name);
 }
-
-// mailbox row of a problem: record, nu* (3N), stats (4)
-static size_t mppi_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 3 * (size_t)h->cfg.N + 4; }
 
 extern "C" int rovmpc_mppi_reset_batch(rovmpc_handle *h, int32_t B, const double *nominals) {
     if (!h) return ROVMPC_ERR_INVALID;
@@ -1803,15 +1892,14 @@ extern "C" int rovmpc_mppi_reset_batch(rovmpc_handle *h, int32_t B, const double
     return plan_reset_batch(h, h->mppi_b, B, nominals, mppi_slab_bytes(h) / 8, mppi_row_words(h), false);
 }
 
-extern "C" int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
-                                      const rovmpc_mppi_params *p, double *records_out, double *nominals_out, double *stats_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
+// one step of the batch from host states, or a device loop of loop.T steps
+static int mppi_run_batch(rovmpc_handle *h, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds, uint64_t step,
+                          const rovmpc_mppi_params *p) {
     PlanBatch &c = h->mppi_b;
-    int rc = plan_batch_ready(h, c, "rovmpc_mppi_step_batch", B, states, seeds, records_out);
-    if (rc || (rc = mppi_check_params(h, p))) return rc;
+    const int B = c.B;
     const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
     const long long total = (long long)h->cfg.K * h->cfg.N * 3;
-    rc = plan_step_batch(h, c, states, seeds, step, p->n_iter,
+    return plan_step_batch(h, c, states, loop, seeds, step, p->n_iter,
                          [&](const PlanBatchIter &it) {
                              MppiSampleBatchArgs sa;
                              memset(&sa, 0, sizeof(sa));
@@ -1832,20 +1920,39 @@ extern "C" int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_
                              a.nu_in = c.plan + it.in_off; a.nu_out = c.plan + it.out_off; a.slab = (double *)c.slab; a.ticket = c.tickets;
                              a.R = (int)R;
                              ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = B;
-                             if (it.last) {
-                                 a.shift = 1; a.record = c.record; a.host_out = c.box.d_out; a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
+                             if (it.last) { a.shift = 1; a.record = c.record; a.loop = it.loop; }
+                             if (it.publish) {
+                                 a.host_out = c.box.d_out; a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
                                  ba.step_ticket = c.tickets + B;
                              }
                              LAUNCH_T_QC(mppi_update_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, B), dim3(MPPI_NT), 0, h->stream, ba);
                              return launched(h, "batched MPPI update");
                          });
-    if (rc) return rc;
+}
+
+extern "C" int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                                      const rovmpc_mppi_params *p, double *records_out, double *nominals_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    PlanBatch &c = h->mppi_b;
+    int rc = plan_batch_ready(h, c, "rovmpc_mppi_step_batch", B, !states || !seeds || !records_out, "states, seeds or records_out");
+    if (rc || (rc = mppi_check_params(h, p))) return rc;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    if ((rc = mppi_run_batch(h, states, PlanLoop{}, seeds, step, p))) return rc;
     for (size_t b = 0; b < (size_t)B; ++b) {
         const double *o = c.box.h_out + b * c.row;
         memcpy(records_out + b * R, o, R * sizeof(double));
         if (nominals_out) memcpy(nominals_out + b * C3, o + R, C3 * sizeof(double));
         if (stats_out) memcpy(stats_out + b * 4, o + R + C3, 4 * sizeof(double));
     }
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_mppi_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
+                                                    const uint64_t *seeds, uint64_t step0, const rovmpc_mppi_params *p, double *d_rows) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = plan_batch_ready(h, h->mppi_b, "rovmpc_mppi_closed_loop_batch_device", B, !d_exo || !seeds || !d_rows, "d_exo, seeds or d_rows");
+    if (rc || (rc = plan_loop_check(h, "rovmpc_mppi_closed_loop_batch_device", d_exo, T, feedback, d_rows)) || (rc = mppi_check_params(h, p))) return rc;
+    if ((rc = mppi_run_batch(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, mppi_row_words(h)}, seeds, step0, p))) return rc;
     return take_device_errors(h);
 }
 
@@ -1864,16 +1971,14 @@ extern "C" int rovmpc_cem_reset_batch(rovmpc_handle *h, int32_t B, const double 
     return plan_reset_batch(h, h->cem_b, B, means, cem_slab_bytes(h) / 8, cem_row_words(h), true);
 }
 
-extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
-                                     const rovmpc_cem_params *p, double *records_out, double *means_out, double *stds_out,
-                                     int64_t *elites_out, double *stats_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
+// one step of the batch from host states, or a device loop of loop.T steps
+static int cem_run_batch(rovmpc_handle *h, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds, uint64_t step,
+                         const rovmpc_cem_params *p) {
     PlanBatch &c = h->cem_b;
-    int rc = plan_batch_ready(h, c, "rovmpc_cem_step_batch", B, states, seeds, records_out);
-    if (rc || (rc = cem_check_params(h, p))) return rc;
+    const int B = c.B;
     const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
     const long long total = (long long)h->cfg.K * h->cfg.N * 3;
-    rc = plan_step_batch(h, c, states, seeds, step, p->n_iter,
+    return plan_step_batch(h, c, states, loop, seeds, step, p->n_iter,
                          [&](const PlanBatchIter &it) {                           // sigma_0 = std
                              CemSampleBatchArgs sa;
                              memset(&sa, 0, sizeof(sa));
@@ -1897,8 +2002,9 @@ extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_s
                              a.mu_out = c.plan + it.out_off; a.sigma_out = c.spread + it.out_off;
                              a.slab = (unsigned long long *)c.slab; a.ticket = c.tickets; a.R = (int)R;
                              ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = B;
-                             if (it.last) {
-                                 a.shift = 1; a.record = c.record; a.host_out = c.box.d_out;
+                             if (it.last) { a.shift = 1; a.record = c.record; a.loop = it.loop; }
+                             if (it.publish) {
+                                 a.host_out = c.box.d_out;
                                  a.host_elite = (long long *)(c.box.d_out + R + 2 * C3 + 4);
                                  a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
                                  ba.step_ticket = c.tickets + B;
@@ -1906,7 +2012,17 @@ extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_s
                              LAUNCH_T_QC(cem_update_batch_kernel, h, a.C3 > CEM_NT, dim3(g.G, B), dim3(CEM_NT), 0, h->stream, ba);
                              return launched(h, "batched CEM update");
                          });
-    if (rc) return rc;
+}
+
+extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                                     const rovmpc_cem_params *p, double *records_out, double *means_out, double *stds_out,
+                                     int64_t *elites_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    PlanBatch &c = h->cem_b;
+    int rc = plan_batch_ready(h, c, "rovmpc_cem_step_batch", B, !states || !seeds || !records_out, "states, seeds or records_out");
+    if (rc || (rc = cem_check_params(h, p))) return rc;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    if ((rc = cem_run_batch(h, states, PlanLoop{}, seeds, step, p))) return rc;
     for (size_t b = 0; b < (size_t)B; ++b) {
         const double *o = c.box.h_out + b * c.row;
         memcpy(records_out + b * R, o, R * sizeof(double));
@@ -1915,6 +2031,15 @@ extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_s
         if (stats_out) memcpy(stats_out + b * 4, o + R + 2 * C3, 4 * sizeof(double));
         if (elites_out) memcpy(elites_out + b * (size_t)p->n_elite, o + R + 2 * C3 + 4, (size_t)p->n_elite * sizeof(int64_t));
     }
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_cem_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
+                                                   const uint64_t *seeds, uint64_t step0, const rovmpc_cem_params *p, double *d_rows) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = plan_batch_ready(h, h->cem_b, "rovmpc_cem_closed_loop_batch_device", B, !d_exo || !seeds || !d_rows, "d_exo, seeds or d_rows");
+    if (rc || (rc = plan_loop_check(h, "rovmpc_cem_closed_loop_batch_device", d_exo, T, feedback, d_rows)) || (rc = cem_check_params(h, p))) return rc;
+    if ((rc = cem_run_batch(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, cem_loop_row_words(h, p->n_elite)}, seeds, step0, p))) return rc;
     return take_device_errors(h);
 }
 

@@ -58,6 +58,7 @@ sample_candidates_kernel(const SampleArgs a, T *__restrict__ U) {
 struct MppiSampleArgs {
     rovmpc_state state;                 // written to d_state by block 0 (null d_state: not written)
     double *d_state;
+    const double *state_src;            // not null: d_state <- these 16 doubles in device memory instead (first step of a device loop)
     unsigned long long seed, counter;
     double std[3];
     long long total;                    // K * N * 3
@@ -89,19 +90,24 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 mppi_sample_kernel(const MppiSampleArgs a, T *__restrict__ U) {
     if (a.d_state && blockIdx.x == 0 && threadIdx.x < ROVMPC_STATE_LEN)
-        a.d_state[threadIdx.x] = reinterpret_cast<const double *>(&a.state)[threadIdx.x];
+        a.d_state[threadIdx.x] = a.state_src ? a.state_src[threadIdx.x] : reinterpret_cast<const double *>(&a.state)[threadIdx.x];
     mppi_sample_body<T>(a.seed, a.counter, a.std, a.total, a.N, a.nu, U);
 }
 
 // Batched form (rovmpc_mppi_step_batch): blockIdx.y = problem.  B states do not fit in the kernel arguments, so the first
 // iteration of a control step reads states [B][16] and seeds [B] from one staging block in mapped host memory and block 0
 // of each problem keeps them in device memory (d_state, d_seeds) for the step's rollouts and later draws; the later
-// iterations read the seeds from there (stage null).
+// iterations read the seeds from there (stage null).  In a device loop (rovmpc_*_closed_loop_batch_device) only the first
+// iteration of the first step has a stage, and it takes the seeds alone from it: problem b's state is then row 0 of its exo
+// trajectory in device memory (state_src + b * state_src_stride); every later step finds the state its predecessor's last
+// update left in d_state (PlanHandoff below).
 struct PlanBatchIn {
     const double *stage;                // mapped: states [B][16], then seeds [B]; null after the first iteration
     double *d_state;                    // [B][16]
     unsigned long long *d_seeds;        // [B]
     int B;
+    const double *state_src;            // not null: the states come from here (device), not from the stage
+    size_t state_src_stride;            // doubles between two problems' rows of state_src
 };
 
 RV_DEV unsigned long long plan_batch_seed(const PlanBatchIn &in, int b) {
@@ -109,7 +115,8 @@ RV_DEV unsigned long long plan_batch_seed(const PlanBatchIn &in, int b) {
     const unsigned long long seed = reinterpret_cast<const unsigned long long *>(in.stage + (size_t)in.B * ROVMPC_STATE_LEN)[b];
     if (blockIdx.x == 0) {
         if (threadIdx.x < ROVMPC_STATE_LEN)
-            in.d_state[(size_t)b * ROVMPC_STATE_LEN + threadIdx.x] = in.stage[(size_t)b * ROVMPC_STATE_LEN + threadIdx.x];
+            in.d_state[(size_t)b * ROVMPC_STATE_LEN + threadIdx.x] = in.state_src ? in.state_src[(size_t)b * in.state_src_stride + threadIdx.x]
+                                                                                  : in.stage[(size_t)b * ROVMPC_STATE_LEN + threadIdx.x];
         if (threadIdx.x == 0) in.d_seeds[b] = seed;
     }
     return seed;
@@ -143,6 +150,36 @@ constexpr int MPPI_MAX_COLS = 1024;         // 3 N (N < 341)
 constexpr int MPPI_ROWS_PER_WG = 64;        // candidates per workgroup, until the grid reaches MPPI_MAX_WG
 constexpr int MPPI_MAX_WG = MPPI_NT;        // the combine reads one slab row per thread
 
+// Loop hand-off of a control step's last update (rovmpc_*_closed_loop*_device; row null: off, as in every single step).
+// Wave 0 of the finishing workgroup, which fills the mailbox, also writes the same row to `row` in device memory and turns
+// `state` into the next step's by plant_update_kernel's rule: slots 0..11 (feedback 0: 0..15) from the next measured row,
+// and with feedback (theta_prev, gamma_prev) <- (theta, gamma), (theta, gamma) <- record[7], record[8], the first predicted
+// node of this step's last rollout's cheapest candidate.  Plain stores: the step's rollouts are over (stream order), the
+// next sampler does not read the state, and the next rollout is a later launch on the same stream.  Problem b of a batch
+// lies b strides behind problem 0 (its state: b * 16).
+struct PlanHandoff {
+    double *row;                        // this step's row of d_rows
+    const double *exo_next;             // the next step's measured row [16], or null at the last step (state is left alone)
+    double *state;                      // the controller's device state [16]
+    int feedback;
+    size_t row_stride, exo_stride;      // doubles per problem
+};
+
+// by whole wave 0, after the record's u has been written
+RV_DEV void plan_handoff_state(const PlanHandoff &lp, size_t b, const double *record) {
+    if (!lp.exo_next) return;
+    const int lane = threadIdx.x & 63;
+    const double *nx = lp.exo_next + b * lp.exo_stride;
+    double *st = lp.state + b * ROVMPC_STATE_LEN;
+    if (lane < (lp.feedback ? 12 : ROVMPC_STATE_LEN)) {
+        st[lane] = nx[lane];
+    } else if (lp.feedback && lane == 12) {
+        const double th = st[12], ga = st[13];
+        st[14] = th; st[15] = ga;
+        st[12] = record[7]; st[13] = record[8];
+    }
+}
+
 struct MppiUpdateArgs {
     const void *J, *U;                  // T [K], T [K][3N]
     long long K, slice;                 // candidates, candidates per workgroup
@@ -160,6 +197,9 @@ struct MppiUpdateArgs {
     int R;
     double *host_out;
     unsigned long long *done_flag, done_seq;
+    // a step of a device loop: the row also goes to loop.row, the state moves on, and only the loop's last step has a
+    // mailbox (host_out and done_flag null otherwise)
+    PlanHandoff loop;
 };
 
 RV_DEV double wave_min(double v) {
@@ -372,12 +412,21 @@ RV_DEV void mppi_update_body(const MppiUpdateArgs &a, const PlanBatchAt &at) {
     if (a.stats && tid == 0) { a.stats[0] = st0; a.stats[1] = st1; a.stats[2] = st2; a.stats[3] = J0; }
     if (a.record && wv == 0) {
         // the control to apply is nu*[0]; the rest of the record is the rollout's
-        double *record = a.record + at.b * a.R, *o = a.host_out + at.b * at.host_stride;
+        double *record = a.record + at.b * a.R;
         if (lane < 3) record[2 + lane] = sNu[lane];
-        for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? sNu[i - 2] : record[i];
-        for (int c = lane; c < C3; c += 64) o[a.R + c] = sNu[c];
-        if (lane == 0) { o[a.R + C3] = st0; o[a.R + C3 + 1] = st1; o[a.R + C3 + 2] = st2; o[a.R + C3 + 3] = J0; }
-        plan_publish(a.done_flag, a.done_seq, at.step_ticket, at.B);
+        auto row_to = [&](double *o) {
+            for (int i = lane; i < a.R; i += 64) o[i] = (i >= 2 && i < 5) ? sNu[i - 2] : record[i];
+            for (int c = lane; c < C3; c += 64) o[a.R + c] = sNu[c];
+            if (lane == 0) { o[a.R + C3] = st0; o[a.R + C3 + 1] = st1; o[a.R + C3 + 2] = st2; o[a.R + C3 + 3] = J0; }
+        };
+        if (a.loop.row) {
+            row_to(a.loop.row + at.b * a.loop.row_stride);
+            plan_handoff_state(a.loop, at.b, record);
+        }
+        if (a.host_out) {
+            row_to(a.host_out + at.b * at.host_stride);
+            plan_publish(a.done_flag, a.done_seq, at.step_ticket, at.B);
+        }
     }
 }
 

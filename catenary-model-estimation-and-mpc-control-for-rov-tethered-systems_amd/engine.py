@@ -377,6 +377,47 @@ class Engine:
         """Host copies of the last batched CEM iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
         return self._plan_last_batch(self.lib.rovmpc_cem_last_batch, B, getattr(self, "_cem_B", 0), "cem_last_batch")
 
+    # -- device-resident closed loops of MPPI / CEM (rovmpc_*_closed_loop*_device): raw device pointers --------------
+    def mppi_row_len(self) -> int:
+        """Doubles per control step in the rows of the MPPI loops: [record, nu* (N x 3), stats (4)]."""
+        return int(self.lib.rovmpc_mppi_row_len(self._h))
+
+    def cem_row_len(self, n_elite: int) -> int:
+        """64-bit words per control step in the rows of the CEM loops: [record, mu*, sigma*, stats (4), elites (n_elite, int64)]."""
+        return int(self.lib.rovmpc_cem_row_len(self._h, int(n_elite)))
+
+    def mppi_closed_loop_device(self, d_exo: int, T: int, feedback: bool, seed: int, step0: int, params: MPPIParams, d_rows: int):
+        """T MPPI control steps by one call: d_exo[T][16] measured rows, d_rows[T][mppi_row_len] (device memory); blocks once."""
+        if not isinstance(params, MPPIParams):
+            raise TypeError("params must be an MPPIParams (MPPIParams.make(...))")
+        self._check(self.lib.rovmpc_mppi_closed_loop_device(self._h, d_exo, int(T), int(feedback), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                            int(step0) & 0xFFFFFFFFFFFFFFFF, C.byref(params), d_rows))
+
+    def cem_closed_loop_device(self, d_exo: int, T: int, feedback: bool, seed: int, step0: int, params: CEMParams, d_rows: int):
+        """T CEM control steps by one call: d_exo[T][16], d_rows[T][cem_row_len(params.n_elite)] (device memory); blocks once."""
+        if not isinstance(params, CEMParams):
+            raise TypeError("params must be a CEMParams (CEMParams.make(...))")
+        self._check(self.lib.rovmpc_cem_closed_loop_device(self._h, d_exo, int(T), int(feedback), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                           int(step0) & 0xFFFFFFFFFFFFFFFF, C.byref(params), d_rows))
+
+    def mppi_closed_loop_batch_device(self, d_exo: int, T: int, feedback: bool, seeds, step0: int, params: MPPIParams, d_rows: int):
+        """The same for the batch of B = len(seeds) problems: d_exo[B][T][16], d_rows[T][B][mppi_row_len]."""
+        if not isinstance(params, MPPIParams):
+            raise TypeError("params must be an MPPIParams (MPPIParams.make(...))")
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        self._check(self.lib.rovmpc_mppi_closed_loop_batch_device(self._h, len(sd), d_exo, int(T), int(feedback), _ptr(sd),
+                                                                  int(step0) & 0xFFFFFFFFFFFFFFFF, C.byref(params), d_rows))
+        self._mppi_B = len(sd)
+
+    def cem_closed_loop_batch_device(self, d_exo: int, T: int, feedback: bool, seeds, step0: int, params: CEMParams, d_rows: int):
+        """The same for the batch of B = len(seeds) problems: d_exo[B][T][16], d_rows[T][B][cem_row_len(params.n_elite)]."""
+        if not isinstance(params, CEMParams):
+            raise TypeError("params must be a CEMParams (CEMParams.make(...))")
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        self._check(self.lib.rovmpc_cem_closed_loop_batch_device(self._h, len(sd), d_exo, int(T), int(feedback), _ptr(sd),
+                                                                 int(step0) & 0xFFFFFFFFFFFFFFFF, C.byref(params), d_rows))
+        self._cem_B = len(sd)
+
     def sampled_candidates(self) -> np.ndarray:
         """Host copy of the candidate tensor of the last ``mpc_step_sampled`` (tests / inspection)."""
         U = np.empty((self.cfg.K, self.cfg.N, 3), dtype=self.cfg.np_dtype)

@@ -6,6 +6,7 @@ sequences, roll all of them over the horizon, return the first control of the ch
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -94,6 +95,75 @@ class MPC:
         self.engine.close()
 
 
+@dataclass
+class PlanLoopResult:
+    """The rows of a device-resident loop (``run``), split.  Single controller: records (T, result_len), plans (T, N, 3),
+    stats (T, 4), and for CEM spreads (T, N, 3) and elites (T, n_elite) int64 (None for MPPI); batched: a problem axis after T.
+    ``plans`` are nu* (MPPI) or mu* (CEM), ``stats`` as ``rovmpc_mppi_step`` / ``rovmpc_cem_step`` return them."""
+    records: np.ndarray
+    plans: np.ndarray
+    stats: np.ndarray
+    spreads: Optional[np.ndarray] = None
+    elites: Optional[np.ndarray] = None
+
+    @property
+    def u(self) -> np.ndarray:
+        return self.records[..., 2:5]
+
+    @property
+    def cost(self) -> np.ndarray:
+        return self.records[..., 0]
+
+
+def loop_feedback(feedback) -> bool:
+    """feedback of a ``run``: a bool, or 0 / 1."""
+    if not isinstance(feedback, (bool, np.bool_)) and not (isinstance(feedback, (int, np.integer)) and feedback in (0, 1)):
+        raise ValueError(f"feedback must be False / True (or 0 / 1), got {feedback!r}")
+    return bool(feedback)
+
+
+def loop_rows(rows) -> np.ndarray:
+    """(T, 16) float64, T >= 1: the measured rows of a single controller's ``run`` (``closed_loop_inputs``)."""
+    r = np.ascontiguousarray(rows, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != 16 or r.shape[0] < 1:
+        raise ValueError(f"rows must have shape (T, 16) with T >= 1, got {r.shape}")
+    return r
+
+
+def loop_rows_batch(rows, B: int) -> np.ndarray:
+    """(B, T, 16) float64 from (B, T, 16), or from (T, 16) given to every problem."""
+    r = np.asarray(rows, dtype=np.float64)
+    if r.ndim == 2:
+        r = np.broadcast_to(loop_rows(r), (B,) + r.shape)
+    if r.ndim != 3 or r.shape[0] != B or r.shape[2] != 16 or r.shape[1] < 1:
+        raise ValueError(f"rows must have shape ({B}, T, 16) or (T, 16) with T >= 1, got {r.shape}")
+    return np.array(r, dtype=np.float64, order="C")
+
+
+def split_rows(rows: np.ndarray, R: int, N: int, n_elite: Optional[int] = None) -> PlanLoopResult:
+    """Rows (..., W) of a loop into their parts: W = R + 3N + 4 (MPPI), or R + 6N + 4 + n_elite (CEM, the elites int64)."""
+    lead, C3 = rows.shape[:-1], 3 * N
+    rec, plans = rows[..., :R].copy(), rows[..., R:R + C3].reshape(lead + (N, 3)).copy()
+    if n_elite is None:
+        assert rows.shape[-1] == R + C3 + 4
+        return PlanLoopResult(rec, plans, rows[..., R + C3:].copy())
+    assert rows.shape[-1] == R + 2 * C3 + 4 + n_elite
+    return PlanLoopResult(rec, plans, rows[..., R + 2 * C3:R + 2 * C3 + 4].copy(),
+                          rows[..., R + C3:R + 2 * C3].reshape(lead + (N, 3)).copy(),
+                          np.ascontiguousarray(rows[..., R + 2 * C3 + 4:]).view(np.int64).copy())
+
+
+def _run_on_device(engine, rows: np.ndarray, W: int, lead: tuple, call) -> np.ndarray:
+    """Upload the measured rows, run ``call(d_exo, d_rows)``, download the loop's rows (lead + (W,))."""
+    import torch
+    dev = torch.device("cuda", engine.cfg.device)
+    exo = torch.tensor(rows, device=dev)
+    out = torch.empty(lead + (W,), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    call(exo.data_ptr(), out.data_ptr())
+    return out.cpu().numpy()
+
+
 class _PlanController:
     """What MPPI and CEM share: an engine of their own, the seed and step counter of the draws, the plan's shape and the
     result of the last step."""
@@ -156,6 +226,21 @@ class MPPI(_PlanController):
         rec, self.nominal, stats = self.engine.mppi_step(state, self.seed, self.step_count, self.params)
         return self._took_step(rec, {"rho": float(stats[0]), "eta": float(stats[1]), "ess": float(stats[2]), "J0": float(stats[3])})
 
+    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
+        """T = len(rows) control steps by one library call, the plant update on the GPU (rovmpc_mppi_closed_loop_device):
+        ``rows`` (T, 16) measured states; ``feedback``: from the second step on (theta, gamma) are the model's own first
+        predicted node.  Row i is what ``step`` would return on the state the plant rule gives; ``step`` and ``run``
+        interleave (the step counter advances by T)."""
+        r, fb = loop_rows(rows), loop_feedback(feedback)
+        e, T = self.engine, len(r)
+        out = _run_on_device(e, r, e.mppi_row_len(), (T,), lambda d_exo, d_rows: e.mppi_closed_loop_device(
+            d_exo, T, fb, self.seed, self.step_count, self.params, d_rows))
+        res = split_rows(out, e.result_len, self.cfg.N)
+        self.nominal = res.plans[-1].copy()
+        self._took_step(res.records[-1], dict(zip(("rho", "eta", "ess", "J0"), map(float, res.stats[-1]))))
+        self.step_count += T - 1
+        return res
+
 
 class CEM(_PlanController):
     """``cem = CEM(N=20, K=4096, n_elite=64); u = cem.step(state)``: the cross-entropy method.
@@ -197,6 +282,18 @@ class CEM(_PlanController):
         rec, self.mean, self.std, self.elites, stats = self.engine.cem_step(state, self.seed, self.step_count, self.params)
         return self._took_step(rec, {"J_best": float(stats[0]), "J_worst_elite": float(stats[1]), "n_finite": int(stats[2]),
                                      "J0": float(stats[3])})
+
+    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
+        """T = len(rows) control steps by one library call (rovmpc_cem_closed_loop_device); see ``MPPI.run``."""
+        r, fb = loop_rows(rows), loop_feedback(feedback)
+        e, T = self.engine, len(r)
+        out = _run_on_device(e, r, e.cem_row_len(self.n_elite), (T,), lambda d_exo, d_rows: e.cem_closed_loop_device(
+            d_exo, T, fb, self.seed, self.step_count, self.params, d_rows))
+        res = split_rows(out, e.result_len, self.cfg.N, self.n_elite)
+        self.mean, self.std, self.elites, st = res.plans[-1].copy(), res.spreads[-1].copy(), res.elites[-1].copy(), res.stats[-1]
+        self._took_step(res.records[-1], {"J_best": float(st[0]), "J_worst_elite": float(st[1]), "n_finite": int(st[2]), "J0": float(st[3])})
+        self.step_count += T - 1
+        return res
 
 
 BATCH_MAX = 1024      # problems of a batched controller (PLAN_BATCH_MAX of the library)
@@ -293,6 +390,20 @@ class BatchedMPPI(_BatchedPlanController):
         return self._took_steps(rec, {"rho": stats[:, 0].copy(), "eta": stats[:, 1].copy(), "ess": stats[:, 2].copy(),
                                       "J0": stats[:, 3].copy()})
 
+    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
+        """T control steps of all B problems by one library call (rovmpc_mppi_closed_loop_batch_device): ``rows`` (B, T, 16),
+        a trajectory per problem, or (T, 16) given to every problem.  The result's arrays are (T, B, ...); problem b's are
+        those of ``MPPI(seed=seeds[b], nominal=nominal[b]).run(rows[b])``."""
+        r, fb = loop_rows_batch(rows, self.B), loop_feedback(feedback)
+        e, T = self.engine, r.shape[1]
+        out = _run_on_device(e, r, e.mppi_row_len(), (T, self.B), lambda d_exo, d_rows: e.mppi_closed_loop_batch_device(
+            d_exo, T, fb, self.seeds, self.step_count, self.params, d_rows))
+        res = split_rows(out, e.result_len, self.cfg.N)
+        self.nominal, st = res.plans[-1].copy(), res.stats[-1]
+        self._took_steps(res.records[-1].copy(), {"rho": st[:, 0].copy(), "eta": st[:, 1].copy(), "ess": st[:, 2].copy(), "J0": st[:, 3].copy()})
+        self.step_count += T - 1
+        return res
+
     def candidates(self):
         """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
         return self.engine.mppi_last_batch()
@@ -332,6 +443,19 @@ class BatchedCEM(_BatchedPlanController):
         rec, self.mean, self.std, self.elites, stats = self.engine.cem_step_batch(st, self.seeds, self.step_count, self.params)
         return self._took_steps(rec, {"J_best": stats[:, 0].copy(), "J_worst_elite": stats[:, 1].copy(),
                                       "n_finite": stats[:, 2].astype(np.int64), "J0": stats[:, 3].copy()})
+
+    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
+        """T control steps of all B problems by one library call (rovmpc_cem_closed_loop_batch_device); see ``BatchedMPPI.run``."""
+        r, fb = loop_rows_batch(rows, self.B), loop_feedback(feedback)
+        e, T = self.engine, r.shape[1]
+        out = _run_on_device(e, r, e.cem_row_len(self.n_elite), (T, self.B), lambda d_exo, d_rows: e.cem_closed_loop_batch_device(
+            d_exo, T, fb, self.seeds, self.step_count, self.params, d_rows))
+        res = split_rows(out, e.result_len, self.cfg.N, self.n_elite)
+        self.mean, self.std, self.elites, st = res.plans[-1].copy(), res.spreads[-1].copy(), res.elites[-1].copy(), res.stats[-1]
+        self._took_steps(res.records[-1].copy(), {"J_best": st[:, 0].copy(), "J_worst_elite": st[:, 1].copy(),
+                                                  "n_finite": st[:, 2].astype(np.int64), "J0": st[:, 3].copy()})
+        self.step_count += T - 1
+        return res
 
     def candidates(self):
         """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""

@@ -218,8 +218,8 @@ int rovmpc_sample_candidates_device(rovmpc_handle *h, uint64_t seed, uint64_t st
  * rovmpc_step / rovmpc_mpc_step_sampled on the same handle give the same bits with or without MPPI steps in between.
  * Errors: ROVMPC_ERR_INVALID for bad parameters, a struct_size mismatch or a step before the first reset;
  * ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
- * Not provided: sharded MPPI (it needs an all-reduce of the 3 N + 3 partials), closed-loop device entries,
- * sampling folded into the fused sampled rollout kernel, control bounds. */
+ * Not provided: sharded MPPI (it needs an all-reduce of the 3 N + 3 partials), sampling folded into the fused sampled
+ * rollout kernel, control bounds. */
 typedef struct rovmpc_mppi_params {
     int32_t struct_size;        /* = sizeof(rovmpc_mppi_params), ABI check                  */
     int32_t n_iter;             /* iterations per control step, 1..64                       */
@@ -266,7 +266,7 @@ int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, const void *d_U
  * or without CEM steps in between.
  * Errors: ROVMPC_ERR_INVALID for parameters outside the ranges below (n_elite > cfg.K included), a struct_size mismatch or a
  * step before the first reset, before anything is launched; ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
- * Not provided: sharded CEM, closed-loop device entries. */
+ * Not provided: sharded CEM. */
 typedef struct rovmpc_cem_params {
     int32_t struct_size;        /* = sizeof(rovmpc_cem_params), ABI check                   */
     int32_t n_iter;             /* iterations per control step, 1..64                       */
@@ -330,6 +330,54 @@ int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *state
                           const rovmpc_cem_params *p, double *records_out, double *means_out, double *stds_out,
                           int64_t *elites_out, double *stats_out);
 int rovmpc_cem_last_batch(rovmpc_handle *h, void *U_out, void *J_out);
+
+/* ---- device-resident closed loop of MPPI and CEM, single and batched: T control steps by one call, the plant update on the
+ * GPU, no host round trip between steps (rovmpc_closed_loop_device's counterpart for the controllers that keep a plan) --------
+ * Rows.  Every step leaves one row of W doubles in device memory, the row its last update publishes into the mailbox:
+ *   MPPI, W = rovmpc_mppi_row_len(h) = result_len + 3 N + 4:               [record (result_len), nu* (N x 3), stats (4)];
+ *   CEM,  W = rovmpc_cem_row_len(h, n_elite) = result_len + 6 N + 4 + n_elite:
+ *         [record (result_len), mu* (N x 3), sigma* (N x 3), stats (4), elite list (n_elite 64-bit integers, rank order, -1 padded)]
+ * with record, plans, stats and elite list as rovmpc_mppi_step / rovmpc_cem_step return them.  (The elite entries are int64
+ * stored in the row's 8-byte slots, not doubles; the row length functions return 0 for a null handle or an n_elite outside
+ * 1..1024.)  d_rows is [T][W]; in the batched forms [T][B][W], and d_exo is [B][T][16]: a trajectory per problem.
+ * Law.  For i = 0 .. T - 1, row i is bit for bit what rovmpc_<ctl>_step(state_i, seed, step0 + i, p) publishes on a handle
+ * with the same configuration and model, reset with the same plan, that has taken steps 0 .. i - 1 the same way, where
+ * state_i follows the plant rule of rovmpc_closed_loop_device:
+ *   state_0 = exo[0];  for i >= 1 slots 0..11 (P0, P1, V1, A1) = exo[i][0..11];
+ *   feedback == 0: slots 12..15 = exo[i][12..15];
+ *   feedback == 1: (theta_prev, gamma_prev) = the (theta, gamma) step i - 1 started from, (theta, gamma) = record[7], record[8]
+ *   of step i - 1.
+ * record[7], record[8] are the first predicted node of the cheapest candidate of step i - 1's LAST rollout.  That is the
+ * existing loop's rule; it is not a model step under the control the step returns (u = nu*[0] or clamp(mu*[0])), which with
+ * n_iter >= 2 is never rolled out.  A one-node plant rollout under the applied control is not provided.
+ * After the call the handle is in the state T calls of rovmpc_<ctl>_step would have left it in: the same kept shifted plan,
+ * the CEM spread restarting from std, rovmpc_*_last / _last_batch returning the last iteration's U and J, the mailbox
+ * holding the last step's row; a following rovmpc_<ctl>_step gives the same bits either way.
+ * The batched forms obey the same law per problem against the single-problem loop with that problem's exo trajectory, seed
+ * and plan (and therefore against rovmpc_*_step_batch stepped from the host).
+ * Split calls.  With feedback == 0 a loop of T steps equals loops of T1 and T - T1 steps, the second on d_exo + T1 * 16 with
+ * step0 + T1: the plan carries over in the handle and every state is a measured row.  With feedback == 1 each call starts
+ * again from its own exo[0] -- the fed-back (theta, gamma) do not carry over from one call to the next.
+ * Execution.  Everything is enqueued on the handle's stream without host synchronisation; per control step there are
+ * exactly 3 n_iter launches (sampler, rollout, update) and no plant-update launch or copy: the finishing workgroup of the
+ * step's last update writes the row and the next state.  Intermediate steps touch neither the mailbox nor its sequence
+ * word; the call blocks once, on the last step's, and then reports what rovmpc_device_status would.
+ * Errors, before anything is launched: ROVMPC_ERR_INVALID for a null pointer, T < 1, feedback other than 0 or 1, the
+ * parameter and struct_size faults of the step entries, a call before the matching reset or (batched) with a B other than
+ * the reset's; ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
+ * Not provided: a pipelined (two-stream) form, a sharded form. */
+int32_t rovmpc_mppi_row_len(const rovmpc_handle *h);
+int32_t rovmpc_cem_row_len(const rovmpc_handle *h, int32_t n_elite);
+/* d_exo [T][16] and d_rows [T][W] in device memory. */
+int rovmpc_mppi_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, int32_t feedback, uint64_t seed,
+                                   uint64_t step0, const rovmpc_mppi_params *p, double *d_rows);
+int rovmpc_cem_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, int32_t feedback, uint64_t seed,
+                                  uint64_t step0, const rovmpc_cem_params *p, double *d_rows);
+/* d_exo [B][T][16] and d_rows [T][B][W] in device memory, seeds [B] on the host (they cross once per call). */
+int rovmpc_mppi_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
+                                         const uint64_t *seeds, uint64_t step0, const rovmpc_mppi_params *p, double *d_rows);
+int rovmpc_cem_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
+                                        const uint64_t *seeds, uint64_t step0, const rovmpc_cem_params *p, double *d_rows);
 
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
