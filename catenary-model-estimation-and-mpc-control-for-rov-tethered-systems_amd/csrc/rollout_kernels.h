@@ -98,7 +98,7 @@ template <typename T> struct RolloutArgs {
     const T *Rtab;            // [N][9] (VT_TABLE)
     T *J;                     // [K]
     T *traj_all;              // [K][N+1][2] or null
-    double *blk_traj;         // [nblocks][N+1][2]
+    double *blk_traj;         // [nblocks][N+1][2] (the tail of traj_all launches and of N + 1 > 64; the fast tail hands its trajectory over in the granules)
     int N, K, CK, M, n_th, n_ga, prev_mode, integrator, debug, fmap;
     // sharded step with the library's own collective: GPU-side hand-off of slot row `rank` (null: none).
     // The row may be written once *flag_consumed >= consumed_need; afterwards *flag_rolled = rolled_seq.
@@ -136,7 +136,8 @@ template <typename T> struct RolloutArgs {
     unsigned used_planes;         // bit s: exogenous plane s is read by the loaded expressions
     unsigned magic_3n;            // floor(2^32 / (3N)) + 1: g / (3N) == umulhi(g, magic) for g < 2^16
     // arg-min epilogue (run by the sweeping workgroup; null result = costs only)
-    unsigned long long *granules; // [3][nblocks]: {epoch << 32 | 32 bits} of cost hi, cost lo, winning lane -- the data is the flag
+    unsigned long long *granules; // {epoch << 32 | 32 bits}, the data is the flag: [GRAN][nblocks] cost hi, cost lo, winning lane (+ trajectory flag of
+                                  // the slow tail), then [nblocks][4 (N + 1)] every workgroup's best trajectory, two granules per double (gran_stride)
     unsigned epoch;               // launch counter of the handle, never 0: tag of this launch's granules
     int sweeper;                  // workgroup that sweeps: 0 when the grid is one round of workgroups (first dispatched, first
                                   // done, already polling when the stragglers publish), else the last (see argmin_epilogue)
@@ -154,7 +155,8 @@ template <typename T> struct RolloutArgs {
     double samp_mean[3], samp_std[3];
     const double *samp_warm;      // previous winner's sequence [N][3] (null: no warm start)
     double *samp_best;            // [N][3]: this step's winner's sequence
-    double *samp_blk_u;           // [nblocks][3 N]: every workgroup's best candidate's controls, handed over like its trajectory
+    unsigned long long *samp_blk_u;   // [nblocks][6 N] tagged granules: every workgroup's best candidate's controls, handed over like its trajectory;
+                                  // behind them [nblocks][3 N] plain doubles, the slow tail's plane (never read as granules)
     double samp_state[ROVMPC_STATE_LEN];
     // Long horizons: the gamma table of the launch, shared between workgroups (null: none).  Workgroup 0 stores its finished
     // table here (write-through) and tags it with the launch epoch; a workgroup that finds the tag when it starts -- the later
@@ -220,6 +222,29 @@ RV_DEV void raise_error(unsigned *err, unsigned bit) {
     if (err) __hip_atomic_fetch_or(err, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// In-kernel phase stamps exist only in the diagnostic library (make diag, -DROVMPC_STAMPS); the
+// product library contains none of this code.
+#ifdef ROVMPC_STAMPS
+#define RV_NSTAMP 24     // slots per workgroup: 0..15 the phases of every workgroup, 16.. the sweeping workgroup's tail
+#define RV_STAMP(i) do { if (threadIdx.x == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)] = wall_clock64(); } while (0)
+#define RV_STAMP_W(i) do { if ((threadIdx.x & 63) == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)] = wall_clock64(); } while (0)   // lane 0 of the calling wave
+// slot i <- SIMD of every wave of the workgroup: nibble w = 8 | SIMD_ID of wave w (HW_ID bits 5:4)
+#define RV_STAMP_SIMD(i) do { if ((threadIdx.x & 63) == 0 && a.stamps) atomicOr(&a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)], \
+    (unsigned long long)(8u | ((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3u)) << (4 * (threadIdx.x >> 6))); } while (0)
+// slot i <- HW_ID (hwreg 4: wave, simd, pipe, cu, sh, se) | XCC_ID (hwreg 20) << 32: which CU ran the workgroup
+#define RV_STAMP_HW(i) do { if (threadIdx.x == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)] = \
+    (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32); } while (0)
+// thread t, once its own loads and stores are through (the sweeper's tail: trajectory in registers, record stored)
+#define RV_STAMP_T(i, t) do { if (threadIdx.x == (t) && a.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)] = wall_clock64(); } } while (0)
+#else
+#define RV_STAMP(i) do { } while (0)
+#define RV_STAMP_T(i, t) do { } while (0)
+#define RV_STAMP_HW(i) do { } while (0)
+#define RV_STAMP_SIMD(i) do { } while (0)
+#define RV_STAMP_W(i) do { } while (0)
+#endif
+
 // ---- arg-min epilogue ----------------------------------------------------------------------
 // Agent-scope (sc1, write-through / L1-bypassing) accessors for the bytes one workgroup hands
 // to another inside a launch.
@@ -229,10 +254,14 @@ RV_DEV void st_agent(unsigned long long *p, unsigned long long v) { __hip_atomic
 RV_DEV unsigned long long ld_agent(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // The workgroup's best as three tagged granules (epoch << 32 | 32 payload bits): cost high word, cost low word,
 // winning lane.  The reader takes a workgroup's record only when all three tags equal this launch's epoch.
-// A fourth granule per workgroup says that its best trajectory (write-through stores) has been acknowledged: the cost
-// granules go out WITHOUT waiting for that drain, so the sweep sees a workgroup's cost ~0.7 us earlier, and only the
-// winner's trajectory flag is waited for (it is almost always up by then).
+// Fast tail: the workgroup's best trajectory (and, sampled, its controls) goes out the same way -- every double as two
+// granules, high word then low word -- so nothing drains and no flag follows: the sweeper loads the winner's granules and
+// takes each one whose tag is this launch's epoch (ld_tagged).
+// Slow tail (traj_all launches, N + 1 > 64): the trajectory is plain write-through doubles in blk_traj, and a fourth
+// granule per workgroup says that those stores have been acknowledged.
 constexpr int GRAN = 4;
+// granules of one problem: the GRAN planes, then 4 (N + 1) per workgroup for its trajectory
+__host__ __device__ inline size_t gran_stride(int nblocks, int N) { return (size_t)nblocks * (size_t)(GRAN + 4 * (N + 1)); }
 RV_DEV void publish_traj_ready(unsigned long long *granules, int nblocks, unsigned epoch) {
     st_agent(granules + 3 * (size_t)nblocks + blockIdx.x, (unsigned long long)epoch << 32);
 }
@@ -243,6 +272,30 @@ RV_DEV void publish_best(unsigned long long *granules, int nblocks, unsigned epo
     st_agent(granules + 2 * (size_t)nblocks + blockIdx.x, tag | lane);
 }
 RV_DEV double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// One double as two tagged granules at g[0] (high word) and g[1] (low word); the 64 payload bits pass through untouched.
+RV_DEV void st_tagged(unsigned long long *g, unsigned epoch, double v) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(v), tag = (unsigned long long)epoch << 32;
+    st_agent(g, tag | (bits >> 32));
+    st_agent(g + 1, tag | (bits & 0xffffffffULL));
+}
+// ... and read back: both granules in one round trip; a granule whose tag is not this launch's epoch (its store is still
+// on the way) is loaded again, alone, until it is -- bounded by `ticks` of the 100 MHz clock, then ERR_SWEEP and a NaN.
+// wait == false (the sweep itself gave up): one look, a NaN if the double is not there.
+RV_DEV double ld_tagged(const unsigned long long *g, unsigned epoch, bool wait, unsigned long long ticks, unsigned *err) {
+    unsigned long long g0 = ld_agent(g), g1 = ld_agent(g + 1);
+    if ((unsigned)(g0 >> 32) != epoch || (unsigned)(g1 >> 32) != epoch) {
+        const unsigned long long give_up = wall_clock64() + ticks;
+        for (;;) {
+            if (!wait) return __builtin_nan("");
+            if ((unsigned)(g0 >> 32) != epoch) g0 = ld_agent(g);
+            if ((unsigned)(g1 >> 32) != epoch) g1 = ld_agent(g + 1);
+            if ((unsigned)(g0 >> 32) == epoch && (unsigned)(g1 >> 32) == epoch) break;
+            if (wall_clock64() > give_up) { raise_error(err, ERR_SWEEP); return __builtin_nan(""); }
+            __builtin_amdgcn_s_sleep(1);
+        }
+    }
+    return __longlong_as_double((long long)((g0 << 32) | (g1 & 0xffffffffULL)));
+}
 RV_DEV float ld_agent(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 RV_DEV void st_agent(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 RV_DEV long long ld_agent(const long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -253,8 +306,8 @@ RV_DEV long long ld_agent(const long long *p) { return __hip_atomic_load(p, __AT
 // (input of the single all-reduce(min) of the candidate-sharded step).  `scratch` = 16
 // doubles of LDS.
 template <typename T, bool LEAN = false, bool SAMPLE = false>
-RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *granules, const double *blk_traj, const T *U,
-                            double *result, double *scratch) {
+RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *granules, const double *blk_traj, const bool tagged,
+                            const T *U, double *result, double *scratch) {
     const int nblocks = a.nblocks, N = a.N, CK = a.CK, NT = a.NT, rank = a.rank, world = a.world;
     long long *slots = a.slots;
     const unsigned epoch = a.epoch;
@@ -268,52 +321,129 @@ RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *g
         Jd = better ? oJ : Jd; kk = better ? ok : kk;
     };
     // Sweep (cdna_hip_programming.md G16, form R2: the data is the flag): every workgroup publishes its best as
-    // three 8-byte granules tagged with this launch's epoch, after draining the write-through stores of its
-    // trajectory.  This workgroup (number 0 when the whole grid is resident at once; otherwise the LAST one of the
+    // three 8-byte granules tagged with this launch's epoch.  This workgroup (number 0 when the whole grid is resident at once; otherwise the LAST one of the
     // grid, dispatched last, so that it never sits on a CU slot while earlier rounds of workgroups still queue for
     // one -- measured: workgroup 0 as the sweeper cost a whole round at C3's two-round launch) re-reads, with agent-scope loads, the granules it has not yet seen complete, until none
     // is pending -- no ticket counter, no fence, and the other workgroups leave as soon as they have published.
-    {
-        int j = 0;
-        // 60 s of the 100 MHz clock; in the closed loop with GPU-side hand-off the hand-off timeout (both grids in flight
-        // have to drain)
-        const unsigned long long give_up = wall_clock64() + (a.ring ? a.handoff_ticks : 6000000000ULL);
-        for (unsigned it = 1;; ++it) {
-            bool pending = false;
-            for (;;) {
-                const int b = tid + j * NT;
-                if (b >= nblocks) break;
-                const unsigned long long g0 = ld_agent(granules + b), g1 = ld_agent(granules + nblocks + b),
-                                         g2 = ld_agent(granules + 2 * (size_t)nblocks + b);
-                if ((unsigned)(g0 >> 32) != epoch || (unsigned)(g1 >> 32) != epoch || (unsigned)(g2 >> 32) != epoch) { pending = true; break; }
-                const double cost = __longlong_as_double((long long)((g0 << 32) | (g1 & 0xffffffffULL)));
-                take(cost, (long long)b * CK + (long long)(g2 & 0xffffffffULL));
-                ++j;
+    // Up to 256 workgroups (four per lane; the single-problem step at K = 4096, every problem of a batch): WAVE 0 ALONE sweeps.
+    // Each pass it loads all its granules at once (clamped addresses, no branch between the loads), rebuilds its minimum
+    // from those that carry the epoch, and asks the wave -- a ballot -- whether any is pending: no workgroup reduction and no
+    // barrier inside a pass, and the wave minimum behind the last pass needs neither LDS nor a barrier.  The other waves
+    // wait at one barrier for the result in LDS; in the lean fast tail nothing later needs them, and they leave at once.
+    // More workgroups than that: every thread sweeps its share one granule after the other, as before.
+    // (The shuffles of both forms take whole waves: NT is a multiple of 64 -- rovmpc_create refuses any other threads_per_block.)
+    const bool small = nblocks <= 256;
+    const bool solo = LEAN && small && tagged;
+    if (small) {
+        if (solo && tid >= 64) return;
+        if (tid < 64) {
+            const unsigned long long give_up = wall_clock64() + (a.ring ? a.handoff_ticks : 6000000000ULL);
+            bool gave_up = false;
+            for (unsigned it = 1;; ++it) {
+                unsigned long long g0[4], g1[4], g2[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int b = min(tid + 64 * q, nblocks - 1);
+                    g0[q] = ld_agent(granules + b); g1[q] = ld_agent(granules + nblocks + b); g2[q] = ld_agent(granules + 2 * (size_t)nblocks + b);
+                }
+                Jd = __builtin_inf(); kk = 0x7fffffffffffffffLL;
+                bool pending = false;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int b = tid + 64 * q;
+                    const bool ok = (unsigned)(g0[q] >> 32) == epoch && (unsigned)(g1[q] >> 32) == epoch && (unsigned)(g2[q] >> 32) == epoch;
+                    pending |= (b < nblocks) & !ok;
+                    const double cost = __longlong_as_double((long long)((g0[q] << 32) | (g1[q] & 0xffffffffULL)));
+                    const bool use = (b < nblocks) & ok;
+                    take(use ? cost : __builtin_inf(), use ? (long long)b * CK + (long long)(g2[q] & 0xffffffffULL) : 0x7fffffffffffffffLL);
+                }
+                if (__builtin_amdgcn_ballot_w64(pending) == 0) break;
+                if ((it & 1023u) == 0 && __builtin_amdgcn_ballot_w64(wall_clock64() > give_up) != 0) {   // some workgroup never published: a NaN cost says so
+                    gave_up = true;
+                    if (tid == 0) raise_error(a.err, ERR_SWEEP);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(2);
             }
-            if (!__syncthreads_or(pending)) break;
-            if ((it & 1023u) == 0 && __syncthreads_or(wall_clock64() > give_up)) {   // some workgroup never published: a NaN cost says so
-                Jd = __builtin_nan(""); kk = 0;
-                if (tid == 0) raise_error(a.err, ERR_SWEEP);
-                break;
+            RV_STAMP(16);
+            take(__shfl_down(Jd, 32, 64), __shfl_down(kk, 32, 64));
+            take(__shfl_down(Jd, 16, 64), __shfl_down(kk, 16, 64));
+            take(row_shl<8>(Jd), row_shl<8>(kk));
+            take(row_shl<4>(Jd), row_shl<4>(kk));
+            take(row_shl<2>(Jd), row_shl<2>(kk));
+            take(row_shl<1>(Jd), row_shl<1>(kk));
+            if (gave_up) { Jd = __builtin_nan(""); kk = 0; }
+            if (solo) {
+                // lane 0's pair to every lane
+                const unsigned long long jb = (unsigned long long)__double_as_longlong(Jd), kb = (unsigned long long)kk;
+                const unsigned jl = __builtin_amdgcn_readfirstlane((int)(unsigned)jb), jh = __builtin_amdgcn_readfirstlane((int)(unsigned)(jb >> 32));
+                const unsigned kl = __builtin_amdgcn_readfirstlane((int)(unsigned)kb), kh = __builtin_amdgcn_readfirstlane((int)(unsigned)(kb >> 32));
+                Jd = __longlong_as_double((long long)(((unsigned long long)jh << 32) | jl));
+                kk = (long long)(((unsigned long long)kh << 32) | kl);
+            } else if (tid == 0) {
+                sJ[0] = Jd; sK[0] = kk;
             }
-            __builtin_amdgcn_s_sleep(4);
         }
+        if (!solo) {
+            __syncthreads();
+            Jd = sJ[0]; kk = sK[0];
+        }
+    } else {
+        {
+            int j = 0;
+            // 60 s of the 100 MHz clock; in the closed loop with GPU-side hand-off the hand-off timeout (both grids in flight
+            // have to drain)
+            const unsigned long long give_up = wall_clock64() + (a.ring ? a.handoff_ticks : 6000000000ULL);
+            for (unsigned it = 1;; ++it) {
+                bool pending = false;
+                for (;;) {
+                    const int b = tid + j * NT;
+                    if (b >= nblocks) break;
+                    const unsigned long long g0 = ld_agent(granules + b), g1 = ld_agent(granules + nblocks + b),
+                                             g2 = ld_agent(granules + 2 * (size_t)nblocks + b);
+                    if ((unsigned)(g0 >> 32) != epoch || (unsigned)(g1 >> 32) != epoch || (unsigned)(g2 >> 32) != epoch) { pending = true; break; }
+                    const double cost = __longlong_as_double((long long)((g0 << 32) | (g1 & 0xffffffffULL)));
+                    take(cost, (long long)b * CK + (long long)(g2 & 0xffffffffULL));
+                    ++j;
+                }
+                if (!__syncthreads_or(pending)) break;
+                if ((it & 1023u) == 0 && __syncthreads_or(wall_clock64() > give_up)) {   // some workgroup never published: a NaN cost says so
+                    Jd = __builtin_nan(""); kk = 0;
+                    if (tid == 0) raise_error(a.err, ERR_SWEEP);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(4);
+            }
+        }
+        RV_STAMP(16);
+        // wave minimum in lane 0: two shuffles across the 16-lane rows, then DPP shifts inside row 0 (a ds_bpermute round trip
+        // per 32 bits and step otherwise); then EVERY thread folds the waves' minima itself -- the nw <= 8 LDS reads are in flight
+        // together, and there is neither a second barrier nor a broadcast through LDS.  (cost, index) is a total order, so the
+        // order of the folds does not matter.
+        take(__shfl_down(Jd, 32, 64), __shfl_down(kk, 32, 64));
+        take(__shfl_down(Jd, 16, 64), __shfl_down(kk, 16, 64));
+        take(row_shl<8>(Jd), row_shl<8>(kk));
+        take(row_shl<4>(Jd), row_shl<4>(kk));
+        take(row_shl<2>(Jd), row_shl<2>(kk));
+        take(row_shl<1>(Jd), row_shl<1>(kk));
+        if ((tid & 63) == 0) { sJ[tid >> 6] = Jd; sK[tid >> 6] = kk; }
+        __syncthreads();
+        Jd = sJ[0]; kk = sK[0];
+        for (int w = 1; w < nw; ++w) take(sJ[w], sK[w]);
     }
-    for (int off = 32; off > 0; off >>= 1) take(__shfl_down(Jd, off, 64), __shfl_down(kk, off, 64));
-    if ((tid & 63) == 0) { sJ[tid >> 6] = Jd; sK[tid >> 6] = kk; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < nw; ++w)
-            if (sJ[w] < Jd || (sJ[w] == Jd && sK[w] < kk)) { Jd = sJ[w]; kk = sK[w]; }
-        sK[0] = kk;
-        sJ[0] = Jd;
-    }
-    __syncthreads();
-    const long long kbest = sK[0];
-    const double Jbest = sJ[0];
+    const long long kbest = kk;
+    const double Jbest = Jd;
+    RV_STAMP(17);
     const int R = 5 + 2 * (N + 1);
     const double *bt = blk_traj + (size_t)(kbest / CK) * (N + 1) * 2;
-    if (Jbest == Jbest) {
+    // The winner's trajectory.  Fast tail (tagged): its granules behind the GRAN planes, each reader checks the tags of what it
+    // loads -- no flag, no barrier, one round trip; a sweep that gave up (NaN cost) waits for nothing more.  Slow tail: plain
+    // doubles behind the winner's flag granule.
+    const unsigned long long *tg = granules + (size_t)GRAN * nblocks + (size_t)(kbest / CK) * 4 * (N + 1);
+    const bool have = Jbest == Jbest;
+    const unsigned long long tail_ticks = a.ring ? a.handoff_ticks : 6000000000ULL;
+    auto winner = [&](int i) -> double { return tagged ? ld_tagged(tg + 2 * i, epoch, have, tail_ticks, a.err) : ld_agent(&bt[i]); };
+    if (!tagged && have) {
         // the winner's trajectory must be out (its flag granule; the cost granules did not wait for it)
         if (tid == 0) {
             const unsigned long long *f = granules + 3 * (size_t)nblocks + (size_t)(kbest / CK);
@@ -324,20 +454,22 @@ RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *g
             }
         }
         __syncthreads();
+        RV_STAMP(20);
     }
     // (sharded closed loop: the next step's theta is the GLOBAL winner's -- select_kernel hands it over behind the all-reduce)
     if (!LEAN && a.ring && a.publish && !slots && tid < 64) {
         // closed loop, GPU-side hand-off: the next step's (theta0, gamma0, theta_prev, gamma_prev) = nodes 1 and 0 of the
         // winner, before anything else -- the record below is off the loop's critical path
-        if (a.plant_feedback && tid < 4) st_agent(&a.ring[(int)((a.step + 1) & 3) * 4 + tid], ld_agent(&bt[tid < 2 ? 2 + tid : tid - 2]));
+        if (a.plant_feedback && tid < 4) st_agent(&a.ring[(int)((a.step + 1) & 3) * 4 + tid], winner(tid < 2 ? 2 + tid : tid - 2));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (tid == 0) st_agent(a.seq_theta, (unsigned long long)(a.step + 1));
     }
     if (SAMPLE) {
         // the winner's control sequence (its workgroup handed it over with the trajectory): the record's u and the next
         // step's warm start
-        const double *bu = a.samp_blk_u + (size_t)(kbest / CK) * 3 * N;
-        for (int j = tid; j < 3 * N; j += NT) a.samp_best[j] = ld_agent(&bu[j]);
+        const unsigned long long *bug = a.samp_blk_u + (size_t)(kbest / CK) * 6 * N;
+        const double *bu = reinterpret_cast<const double *>(a.samp_blk_u + (size_t)nblocks * 6 * N) + (size_t)(kbest / CK) * 3 * N;
+        for (int j = tid; j < 3 * N; j += NT) a.samp_best[j] = tagged ? ld_tagged(bug + 2 * j, epoch, have, tail_ticks, a.err) : ld_agent(&bu[j]);
         __syncthreads();
     }
     bool row_free = true;
@@ -345,7 +477,8 @@ RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *g
         // the slot buffer is reused every few steps: its previous contents must have been read by that step's select.
         // If that never happens (a failed collective) the row is NOT rewritten: the error word and the slot's
         // bad-use mark make this step's global record a NaN and rovmpc_comm_sync an error.
-        int *s_ok = reinterpret_cast<int *>(scratch + 15);     // sK[7]: read by thread 0 only, before the last barrier
+        int *s_ok = reinterpret_cast<int *>(scratch + 15);     // sK[7]: every thread has folded the waves' minima behind this barrier
+        __syncthreads();
         if (tid == 0) {
             const unsigned long long give_up = wall_clock64() + a.handoff_ticks;
             bool ok = true;
@@ -359,16 +492,18 @@ RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *g
         __syncthreads();
         row_free = *s_ok != 0;
     }
-    for (int i = tid; i < R; i += NT) {
+    for (int i = tid; i < R; i += (solo ? 64 : NT)) {
         double v;
         if (i == 0) v = row_free ? Jbest : __builtin_nan("");
         else if (i == 1) v = (double)(kbest + a.k_offset);
         else if (i < 5) v = SAMPLE ? a.samp_best[i - 2] : (double)U[(size_t)kbest * N * 3 + (i - 2)];
-        else v = ld_agent(&bt[i - 5]);
+        else v = winner(i - 5);
+        RV_STAMP_T(18, 5);
         result[i] = v;
         if (!LEAN && a.result_host) a.result_host[i] = v;
         if (!LEAN && slots && row_free) st_agent(&slots[(size_t)rank * R + i], ordered_key(v));
     }
+    RV_STAMP_T(19, 5);
     if (!LEAN && slots && row_free) {
         for (int i = tid; i < world * R; i += NT)
             if (i / R != rank) st_agent(&slots[i], 0x7fffffffffffffffLL);
@@ -400,9 +535,9 @@ RV_DEV void argmin_epilogue(const RolloutArgs<T> &a, const unsigned long long *g
             plant_state[tid] = plant_next[tid];
         } else if (tid == 12) {
             // (theta, gamma) of this step = node 0 of the winner's trajectory, of the next = node 1
-            const double th = a.ring ? ld_agent(&bt[0]) : plant_state[12], ga = a.ring ? ld_agent(&bt[1]) : plant_state[13];
+            const double th = a.ring ? winner(0) : plant_state[12], ga = a.ring ? winner(1) : plant_state[13];
             plant_state[14] = th; plant_state[15] = ga;
-            plant_state[12] = ld_agent(&bt[2]); plant_state[13] = ld_agent(&bt[3]);
+            plant_state[12] = winner(2); plant_state[13] = winner(3);
         }
     }
 }
@@ -415,24 +550,6 @@ RV_DEV void theta_slot_mark(double *p) { __hip_atomic_store(reinterpret_cast<uns
 RV_DEV void theta_slot_mark(float *p) { __hip_atomic_store(reinterpret_cast<unsigned int *>(p), 0x7fc5ea71u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 RV_DEV bool theta_slot_marked(double *p) { return __hip_atomic_load(reinterpret_cast<unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0x7ff85ea71e5007e7ull; }
 RV_DEV bool theta_slot_marked(float *p) { return __hip_atomic_load(reinterpret_cast<unsigned int *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0x7fc5ea71u; }
-
-// In-kernel phase stamps exist only in the diagnostic library (make diag, -DROVMPC_STAMPS); the
-// product library contains none of this code.
-#ifdef ROVMPC_STAMPS
-#define RV_STAMP(i) do { if (threadIdx.x == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = wall_clock64(); } while (0)
-#define RV_STAMP_W(i) do { if ((threadIdx.x & 63) == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = wall_clock64(); } while (0)   // lane 0 of the calling wave
-// slot i <- SIMD of every wave of the workgroup: nibble w = 8 | SIMD_ID of wave w (HW_ID bits 5:4)
-#define RV_STAMP_SIMD(i) do { if ((threadIdx.x & 63) == 0 && a.stamps) atomicOr(&a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)], \
-    (unsigned long long)(8u | ((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3u)) << (4 * (threadIdx.x >> 6))); } while (0)
-// slot i <- HW_ID (hwreg 4: wave, simd, pipe, cu, sh, se) | XCC_ID (hwreg 20) << 32: which CU ran the workgroup
-#define RV_STAMP_HW(i) do { if (threadIdx.x == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = \
-    (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32); } while (0)
-#else
-#define RV_STAMP(i) do { } while (0)
-#define RV_STAMP_HW(i) do { } while (0)
-#define RV_STAMP_SIMD(i) do { } while (0)
-#define RV_STAMP_W(i) do { } while (0)
-#endif
 
 // LDS plane addressing: plane p, node n (0..N), lane c (0..CK-1); c fastest => conflict-free.
 #define RV_PL(base, p, n, c) (base)[((p) * (N + 1) + (n)) * CK + (c)]
@@ -1964,7 +2081,7 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
     T *Jb = a.J + (size_t)prob * K;
     T *trajb = a.traj_all ? a.traj_all + (size_t)prob * K * (N + 1) * 2 : nullptr;
     double *blk_trajb = a.blk_traj + (size_t)prob * a.nblocks * (N + 1) * 2;
-    unsigned long long *granb = a.granules + (size_t)prob * GRAN * a.nblocks;
+    unsigned long long *granb = a.granules + (size_t)prob * gran_stride(a.nblocks, N);
     double *resultb = a.result ? a.result + (size_t)prob * (5 + 2 * (N + 1)) : nullptr;
     const bool fast_tail = resultb && !a.traj_all && N + 1 <= 64;
     double &s_best_J = *reinterpret_cast<double *>(reinterpret_cast<char *>(smem) + 16);   // header bytes 16..23
@@ -2005,21 +2122,20 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
         }
         if (c == 0) *s_best_c = (int)(kk - k0);
         if (fast_tail) {
-            // the common case: this wave alone hands the workgroup's best over (lane 0 holds it after the reduction):
-            // trajectory stores (write-through), drain, then the three tagged granules
+            // the common case: this wave alone hands the workgroup's best over (lane 0 holds it after the reduction): the
+            // three cost granules, then the trajectory as tagged granules (lane n: node n, four granules) -- every store
+            // carries its own tag, so the wave neither drains nor flags
             const int cb = __builtin_amdgcn_readfirstlane((int)(kk - k0));
-            double *bt = blk_trajb + (size_t)blockIdx.x * (N + 1) * 2;
+            if (c == 0) publish_best(granb, a.nblocks, a.epoch, Jd, (unsigned)cb);
+            unsigned long long *tg = granb + (size_t)GRAN * a.nblocks + (size_t)blockIdx.x * 4 * (N + 1);
             if (c <= N) {
-                st_agent(&bt[2 * c], (double)RV_PL(sY, 0, c, cb));
-                st_agent(&bt[2 * c + 1], (double)RV_PL(sY, 1, c, cb));
+                st_tagged(tg + 4 * c, a.epoch, (double)RV_PL(sY, 0, c, cb));
+                st_tagged(tg + 4 * c + 2, a.epoch, (double)RV_PL(sY, 1, c, cb));
             }
             if (SAMPLE) {
-                double *bu = a.samp_blk_u + (size_t)blockIdx.x * 3 * N;
-                for (int j = c; j < 3 * N; j += 64) st_agent(&bu[j], (double)sU[cb * US + j]);
+                unsigned long long *bu = a.samp_blk_u + (size_t)blockIdx.x * 6 * N;
+                for (int j = c; j < 3 * N; j += 64) st_tagged(bu + 2 * j, a.epoch, (double)sU[cb * US + j]);
             }
-            if (c == 0) publish_best(granb, a.nblocks, a.epoch, Jd, (unsigned)cb);     // the cost does not wait for the drain
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (c == 0) publish_traj_ready(granb, a.nblocks, a.epoch);
         } else if (c == 0) {
             s_best_J = Jd;
         }
@@ -2035,7 +2151,7 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             st_agent(&bt[2 * i + 1], (double)RV_PL(sY, 1, i, cb));
         }
         if (SAMPLE) {
-            double *bu = a.samp_blk_u + (size_t)blockIdx.x * 3 * N;
+            double *bu = reinterpret_cast<double *>(a.samp_blk_u + (size_t)a.nblocks * 6 * N) + (size_t)blockIdx.x * 3 * N;
             for (int j = tid; j < 3 * N; j += NT) st_agent(&bu[j], (double)sU[cb * US + j]);
         }
         if (trajb) {
@@ -2062,11 +2178,11 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
     RV_STAMP(7);
     if ((int)blockIdx.x != a.sweeper) return;
     if (HANDOFF) {
-        argmin_epilogue<T>(a, granb, blk_trajb, Ub, resultb, reinterpret_cast<double *>(smem + 4));
+        argmin_epilogue<T>(a, granb, blk_trajb, fast_tail, Ub, resultb, reinterpret_cast<double *>(smem + 4));
     } else if (LEAN) {
-        argmin_epilogue<T, true>(a, granb, blk_trajb, Ub, resultb, reinterpret_cast<double *>(smem + 4));
+        argmin_epilogue<T, true>(a, granb, blk_trajb, fast_tail, Ub, resultb, reinterpret_cast<double *>(smem + 4));
     } else if (SAMPLE) {
-        argmin_epilogue<T, false, true>(a, granb, blk_trajb, Ub, resultb, reinterpret_cast<double *>(smem + 4));
+        argmin_epilogue<T, false, true>(a, granb, blk_trajb, fast_tail, Ub, resultb, reinterpret_cast<double *>(smem + 4));
     } else {
         // The epilogue's own arguments (hand-off flags, slot buffer, plant update, host mirror ...) are cold: one workgroup
         // reads them once.  Read here through the kernarg segment pointer made opaque, their scalar loads cannot be
@@ -2079,7 +2195,7 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
 #else
         const RolloutArgs<T> *ap = &a;
 #endif
-        argmin_epilogue<T>(*ap, granb, blk_trajb, Ub, resultb, reinterpret_cast<double *>(smem + 4));
+        argmin_epilogue<T>(*ap, granb, blk_trajb, fast_tail, Ub, resultb, reinterpret_cast<double *>(smem + 4));
     }
 }
 
@@ -2171,7 +2287,7 @@ struct HandoffArgs {
     unsigned long long *seq_theta;    // steps whose (theta | gamma) record the sweepers have published (0 before the loop)
     unsigned long long *seq_gamma;
     double *ring;                     // [4][4], see RolloutArgs
-    unsigned long long *granules2;    // [2][GRAN][nblocks] and
+    unsigned long long *granules2;    // [2][gran_stride] and
     double *blk_traj2;                // [2][nblocks][N+1][2]: hand-off buffers by step parity (two steps are in flight)
     long long step;                   // global index of this launch's step
 };
@@ -2181,7 +2297,7 @@ template <typename T, int MODEL, int VT, int CKC = 0, int NC = 0>
 RV_DEV void closed_loop_step_body(const RolloutArgs<T> &a0, const HandoffArgs &p) {
     const long long g = p.step;
     RolloutArgs<T> a = a0;
-    a.granules = p.granules2 + (size_t)(g & 1) * GRAN * a0.nblocks;
+    a.granules = p.granules2 + (size_t)(g & 1) * gran_stride(a0.nblocks, a0.N);
     a.blk_traj = p.blk_traj2 + (size_t)(g & 1) * a0.nblocks * (a0.N + 1) * 2;
     a.exo_cur = p.exo + (size_t)g * ROVMPC_STATE_LEN;
     a.ring = p.ring; a.seq_theta = p.seq_theta; a.seq_gamma = p.seq_gamma;

@@ -106,7 +106,7 @@ struct rovmpc_handle {
     size_t lds_bytes = 0, esz = 8;
     void *d_U = nullptr, *d_J = nullptr, *d_traj_all = nullptr;
     double *d_state = nullptr, *d_blk_traj = nullptr, *d_result = nullptr;
-    unsigned long long *d_granules = nullptr;  // [3][max_blocks] tagged hand-off granules
+    unsigned long long *d_granules = nullptr;  // [gran_stride(max_blocks, N)] tagged hand-off granules: costs, then best trajectories
     unsigned *epoch_ctr = nullptr;            // launches issued (host counter; tag of the next launch = ++*epoch_ctr, never 0)
     unsigned long long *d_stamps = nullptr;   // diagnostic library only
     void *d_gtab = nullptr;                   // shared gamma table of a launch (long horizons) + its epoch tag behind it
@@ -126,7 +126,7 @@ struct rovmpc_handle {
     Mailbox samp_box;
     unsigned long long samp_steps = 0;
     double *d_best = nullptr;                    // [2][N][3]: winner's sequence of the last fused-sampling steps, by step parity
-    double *d_blk_u = nullptr;                   // [max_blocks][3 N]: per-workgroup best controls of a fused-sampling step
+    unsigned long long *d_blk_u = nullptr;       // [max_blocks][6 N] tagged granules + [max_blocks][3 N] doubles: per-workgroup best controls of a fused-sampling step
     // what the last sampled step drew with (rovmpc_sampled_candidates re-draws the tensor for inspection)
     unsigned long long last_seed = 0, last_step = 0; double last_mean[3] = {}, last_std[3] = {}; int last_warm = 0; bool last_fused = false;
     double *arg_result_host = nullptr; unsigned long long *arg_done_flag = nullptr; unsigned long long arg_done_seq = 0;
@@ -521,8 +521,8 @@ extern "C" int rovmpc_create(const rovmpc_config *cfg, rovmpc_handle **out) {
     CR(hipMalloc((void **)&h->d_consts64, ROVMPC_MAX_CODE * 8));
     CR(hipMalloc(&h->d_Rtab, (size_t)cfg->N * 9 * h->esz));
     CR(hipMalloc(&h->d_k, sizeof(RolloutConsts<double>)));
-    CR(hipMalloc((void **)&h->d_granules, (size_t)GRAN * max_blocks * sizeof(unsigned long long)));
-    CR(hipMemset(h->d_granules, 0, (size_t)GRAN * max_blocks * sizeof(unsigned long long)));
+    CR(hipMalloc((void **)&h->d_granules, gran_stride((int)max_blocks, cfg->N) * sizeof(unsigned long long)));
+    CR(hipMemset(h->d_granules, 0, gran_stride((int)max_blocks, cfg->N) * sizeof(unsigned long long)));
     h->epoch_ctr = new unsigned(0);
     CR(hipMalloc(&h->d_gtab, (size_t)8 * (cfg->N + 1) * 8 + 64));
     CR(hipMemset(h->d_gtab, 0, (size_t)8 * (cfg->N + 1) * 8 + 64));
@@ -530,8 +530,8 @@ extern "C" int rovmpc_create(const rovmpc_config *cfg, rovmpc_handle **out) {
     *h->h_err = 0;
     CR(hipHostGetDevicePointer((void **)&h->d_err, h->h_err, 0));
 #ifdef ROVMPC_STAMPS
-    CR(hipMalloc((void **)&h->d_stamps, (size_t)max_blocks * 16 * sizeof(unsigned long long)));
-    CR(hipMemset(h->d_stamps, 0, (size_t)max_blocks * 16 * sizeof(unsigned long long)));
+    CR(hipMalloc((void **)&h->d_stamps, (size_t)max_blocks * RV_NSTAMP * sizeof(unsigned long long)));
+    CR(hipMemset(h->d_stamps, 0, (size_t)max_blocks * RV_NSTAMP * sizeof(unsigned long long)));
 #endif
 #undef CR
     *out = h;
@@ -1123,7 +1123,7 @@ static int ensure_batch(rovmpc_handle *h, int B) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const rovmpc_config &c = h->cfg;
     const size_t max_blocks = c.candidates_per_block > 0 ? (size_t)((c.K + c.candidates_per_block - 1) / c.candidates_per_block) : (size_t)c.K;
-    const size_t gran_bytes = (size_t)B * GRAN * max_blocks * sizeof(unsigned long long);
+    const size_t gran_bytes = (size_t)B * gran_stride((int)max_blocks, c.N) * sizeof(unsigned long long);
     void *fresh[3] = {nullptr, nullptr, nullptr};
     hipError_t e = hipMalloc(&fresh[0], (size_t)B * c.K * h->esz);
     if (e == hipSuccess) e = hipMalloc(&fresh[1], (size_t)B * max_blocks * (c.N + 1) * 2 * sizeof(double));
@@ -1281,7 +1281,10 @@ extern "C" int rovmpc_mpc_step_sampled(rovmpc_handle *h, const rovmpc_state *sta
         if (!h->d_best) {
             const size_t max_blocks = h->cfg.candidates_per_block > 0 ? (size_t)((h->cfg.K + h->cfg.candidates_per_block - 1) / h->cfg.candidates_per_block) : (size_t)h->cfg.K;
             HIPCHK(h, hipMalloc((void **)&h->d_best, (size_t)2 * h->cfg.N * 3 * sizeof(double)));
-            HIPCHK(h, hipMalloc((void **)&h->d_blk_u, max_blocks * (size_t)h->cfg.N * 3 * sizeof(double)));
+            // (tagged granules, two per double: zeroed once, epoch 0 is never a valid tag)
+            // (then the slow tail's plane of plain doubles, 3 N per workgroup)
+            HIPCHK(h, hipMalloc((void **)&h->d_blk_u, max_blocks * (size_t)h->cfg.N * 9 * sizeof(unsigned long long)));
+            HIPCHK(h, hipMemset(h->d_blk_u, 0, max_blocks * (size_t)h->cfg.N * 9 * sizeof(unsigned long long)));
         }
         rc = h->cfg.dtype == ROVMPC_F64 ? fused_sampled_step_t<double>(h, state, seed, step, mean3, std3, warm, seq)
                                         : fused_sampled_step_t<float>(h, state, seed, step, mean3, std3, warm, seq);
@@ -2344,13 +2347,15 @@ extern "C" int rovmpc_velocity_transform(rovmpc_handle *h, const double *R, cons
 }
 
 #ifdef ROVMPC_STAMPS
-// Diagnostic library only: copy the per-workgroup phase stamps of the last launch to the host.
+// Diagnostic library only: stamp slots per workgroup (the row length of what rovmpc_diag_read_stamps copies) ...
+extern "C" int32_t rovmpc_diag_stamp_slots(void) { return RV_NSTAMP; }
+// ... and copy the per-workgroup phase stamps of the last launch to the host.
 extern "C" int rovmpc_diag_read_stamps(rovmpc_handle *h, unsigned long long *out, int32_t *nblocks) {
     if (!h || !out) return ROVMPC_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMemcpy(out, h->d_stamps, (size_t)h->nblocks * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemset(h->d_stamps, 0, (size_t)h->nblocks * 16 * sizeof(unsigned long long)));   // (slot 11 is OR-ed into)
+    HIPCHK(h, hipMemcpy(out, h->d_stamps, (size_t)h->nblocks * RV_NSTAMP * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemset(h->d_stamps, 0, (size_t)h->nblocks * RV_NSTAMP * sizeof(unsigned long long)));   // (slot 11 is OR-ed into)
     if (nblocks) *nblocks = h->nblocks;
     return ROVMPC_OK;
 }
@@ -2928,8 +2933,8 @@ static int closed_loop_workspace(rovmpc_handle *h, HandoffArgs &p, hipStream_t s
     const size_t max_blocks = c.candidates_per_block > 0 ? (size_t)((c.K + c.candidates_per_block - 1) / c.candidates_per_block) : (size_t)c.K;
     if (!h->d_step_seq) {
         HIPCHK(h, hipMalloc((void **)&h->d_step_seq, 256));
-        HIPCHK(h, hipMalloc((void **)&h->d_cl_granules, 2 * GRAN * max_blocks * sizeof(unsigned long long)));
-        HIPCHK(h, hipMemset(h->d_cl_granules, 0, 2 * GRAN * max_blocks * sizeof(unsigned long long)));
+        HIPCHK(h, hipMalloc((void **)&h->d_cl_granules, 2 * gran_stride((int)max_blocks, c.N) * sizeof(unsigned long long)));
+        HIPCHK(h, hipMemset(h->d_cl_granules, 0, 2 * gran_stride((int)max_blocks, c.N) * sizeof(unsigned long long)));
         HIPCHK(h, hipMalloc((void **)&h->d_cl_blk_traj, 2 * max_blocks * (size_t)(c.N + 1) * 2 * sizeof(double)));
     }
     HIPCHK(h, hipMemsetAsync(h->d_step_seq, 0, 128, s));

@@ -42,7 +42,10 @@ if os.environ.get("STAMPS_BACK_TO_BACK"):        # steady state: launches back t
     torch.cuda.synchronize()
 lib = eng.lib
 lib.rovmpc_diag_read_stamps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-buf = np.zeros((K, 16), dtype=np.uint64)
+lib.rovmpc_diag_stamp_slots.restype = C.c_int32
+NSLOT = int(lib.rovmpc_diag_stamp_slots())         # RV_NSTAMP of the diagnostic library
+assert NSLOT >= 24, NSLOT
+buf = np.zeros((K, NSLOT), dtype=np.uint64)
 nb = C.c_int32()
 if not os.environ.get("STAMPS_BACK_TO_BACK"):     # clear what the warm-up launches left, then one launch to read
     lib.rovmpc_diag_read_stamps(eng._h, buf.ctypes.data_as(C.c_void_p), C.byref(nb))
@@ -51,7 +54,9 @@ assert lib.rovmpc_diag_read_stamps(eng._h, buf.ctypes.data_as(C.c_void_p), C.byr
 st = buf[:nb.value].astype(np.int64)
 t0 = st[:, 0].min()
 names = ["start", "U in LDS", None, "features done", "integration done", "geometry done", "outputs stored", "ticket drawn",
-         "gamma wave: chain starts", "gamma wave: chain done", "gamma wave: sines done", None, "phase 2a done (wave 0)", "phase 2a barrier passed", "phase 5: block arg-min done", "phase 5: barrier passed"]
+         "gamma wave: chain starts", "gamma wave: chain done", "gamma wave: sines done", None, "phase 2a done (wave 0)", "phase 2a barrier passed", "phase 5: block arg-min done", "phase 5: barrier passed",
+         "sweep: all cost granules seen", "sweep: block reduce done", "sweep: winner's trajectory in registers", "sweep: record stored",
+         "sweep: winner's trajectory flag seen", None, None, None]
 print(f"{nb.value} workgroups; times in us from the first workgroup's start (100 MHz clock)")
 for i, n in enumerate(names):
     if n is None:
@@ -102,3 +107,16 @@ print("start by XCC (us after the first workgroup): " + "  ".join(f"xcc{x}: {np.
 order = np.argsort(start, kind="stable")
 print("start of the k-th workgroup to start: " + "  ".join(f"{k}: {(start[order[k]] - t0) / 100:.2f}" for k in (0, 1, 2, 4, 8, 16, 32, 64, 128, 192, 255) if k < len(order)))
 print("start by blockIdx: " + "  ".join(f"{b}: {(start[b] - t0) / 100:.2f}" for b in (0, 1, 2, 7, 8, 9, 16, 64, 128, 255) if b < len(start)))
+
+# the sweeping workgroup's tail (slots 16..20, stamped by that workgroup alone): what lies behind the last ordinary workgroup
+sw = np.nonzero(st[:, 16] > 0)[0]
+if len(sw):
+    b = int(sw[0])
+    last = st[:, 7].max()
+    print(f"sweep tail (workgroup {b}); us after the LAST workgroup's ticket / after the sweeper's own ticket / after the previous row:")
+    prev = st[b, 7]
+    for i in (16, 17, 20, 18, 19):
+        if st[b, i] > 0:
+            print(f"  {names[i]:40s} {(st[b, i] - last) / 100:7.2f} {(st[b, i] - st[b, 7]) / 100:7.2f} {(st[b, i] - prev) / 100:7.2f}")
+            prev = st[b, i]
+    print(f"  reduce done -> record stored {(st[b, 19] - st[b, 17]) / 100:.2f}; of that the store itself (trajectory in registers -> record stored) {(st[b, 19] - st[b, 18]) / 100:.2f}")
