@@ -307,6 +307,14 @@ template <typename T> RV_DEV void theta_gamma_axes(V3<T> rel, V3<T> &th_axis, V3
     ga_axis = {rel.x * inv, rel.y * inv, rel.z * inv};
 }
 
+// The cable chain below (root, tension, lowest point) is compiled three times: into the library's compiled-in and interpreter
+// kernels and, by hiprtc, into the kernel specialised for a loaded model.  Under the default contraction mode the backend picks
+// which product of an expression is fused into an FMA from the code around it, so the same source rounded differently per
+// build and an iterate next to the u = 0.5 switch took the series form in one build and the exponential form in another.
+// From here to the end of augmented_finish only the language-level fusion applies (a * b + c within one expression, chosen
+// by the front end from the source alone): every build of this chain produces the same bits.
+#pragma clang fp contract(on)
+
 // f(C) of main_fun.py:423, same expression order.
 template <typename T> RV_DEV T catenary_f(T C, T l, T L2mH2) {
     T s = m_sinh(T(0.5) * l * C);
@@ -378,7 +386,7 @@ RV_DEV float exp_increment(float d) {
 // without a usable warm start takes the series bound and the tail loop runs the extra iterations it needs.
 template <typename T, bool WARM>
 RV_DEV CatRoot<T> solve_catenary_root_impl(T l, T dH, T L, T c_lo, T c_hi, T u_warm, T e_warm) {
-    const T L2 = L * L - dH * dH;
+    const T L2 = m_fma(-dH, dH, L * L);          // one rounding of L^2 (exact for a short L such as 3), dH^2 unrounded
     const T sq = m_sqrtq(L2);
     // 1 / l once, for r here and C at the end (l = 0 gives NaN, l = inf gives 0: either way not a valid system below, as
     // with the quotients themselves)
@@ -545,6 +553,8 @@ RV_DEV T augmented_finish(const AugShape<T> &a, CatRoot<T> c, T L, int M, T inv_
     }
     return up * best;
 }
+
+#pragma clang fp contract(fast)
 
 // The four lanes of a quad (lanes 4q .. 4q+3) each receive all four lanes' values:
 // out[j] = v of lane 4 (lane / 4) + j.  One v_mov_b32_dpp quad_perm per 32-bit half and source
