@@ -821,6 +821,18 @@ kabsch_kernel(const double *__restrict__ P, const double *__restrict__ Q, const 
         for (int i = 0; i < M; ++i)
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) A[a][b] += (p[3 * i + a] - cp[a]) * (q[3 * i + b] - cq[b]);
+        // R does not depend on a scaling of H, but the squared column norms below overflow (and the columns divided by an
+        // infinite norm are a finite zero matrix) or vanish once the markers are scaled far enough.  Bring the largest
+        // magnitude of H into [0.5, 1) by its power of two: exact, so a frame the sweeps could already handle keeps its
+        // bits.  An H that is not finite or all zero has no rotation: NaN row.
+        double amax = 0;
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) { ok = ok && m_finite(A[a][b]); amax = m_abs(A[a][b]) > amax ? m_abs(A[a][b]) : amax; }
+        ok = ok && amax > 0;
+        int hexp = 0;
+        ::frexp(ok ? amax : 1.0, &hexp);
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) A[a][b] = ::ldexp(A[a][b], -hexp);
         double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
         for (int sweep = 0; sweep < 30; ++sweep) {
             bool rotated = false;
@@ -861,7 +873,18 @@ kabsch_kernel(const double *__restrict__ P, const double *__restrict__ Q, const 
         const double vv[3][3] = {{v1.x, v1.y, v1.z}, {v2.x, v2.y, v2.z}, {v3.x, v3.y, v3.z}};
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) R[3 * a + b] = vv[0][a] * uu[0][b] + vv[1][a] * uu[1][b] + vv[2][a] * uu[2][b];
-        for (int a = 0; a < 9; ++a) ok = ok && m_finite(R[a]);
+        // A rank-one H (collinear markers) determines no rotation.  The sweeps then leave a residual column parallel to the
+        // dominant one, u2 = +-u1 and R is a finite matrix of rank one -- unless the residual happens to underflow first.
+        // So the result itself is gated, as the reference's batch loop gates its own (:94, there to 1e-2): a frame
+        // whose R is not orthogonal to 32 eps is a NaN row.  Converged sweeps leave |u1.u2| <= 1e-15 and a defect of a
+        // few eps; det R = +1 follows from the cross products once R is orthogonal.
+        double defect = 0;
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b) {
+                const double s = R[3 * a] * R[3 * b] + R[3 * a + 1] * R[3 * b + 1] + R[3 * a + 2] * R[3 * b + 2] - (a == b ? 1.0 : 0.0);
+                defect = m_abs(s) > defect || s != s ? m_abs(s) : defect;
+            }
+        ok = ok && defect <= 32 * m_eps<double>();
     }
     const double *w = v + 3 * t;
     for (int a = 0; a < 3; ++a)

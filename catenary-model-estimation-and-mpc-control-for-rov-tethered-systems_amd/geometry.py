@@ -187,7 +187,9 @@ def kabsch_velocity_transform(original_points, corrected_points, rob_speed, batc
     """``rob_cor_speed`` for T frames: Kabsch rotation of the cable markers (T, M, 3) original ->
     corrected, applied to ``rob_speed`` (T, 3).  ``batch_gates=True`` follows
     velocity_transform_batch.py:75-101 (NaN rows for non-finite markers, fewer than 3 markers or
-    |P - Q| < 1e-6), ``False`` follows velocity_transform.py:60-80.  Returns (v (T,3), R (T,3,3))."""
+    |P - Q| < 1e-6), ``False`` follows velocity_transform.py:60-80.  In both modes a frame that determines no
+    rotation is a NaN row too: a cross-covariance that is not finite or all zero, or markers so close to
+    collinear that the computed R is not orthogonal to 32 eps.  Returns (v (T,3), R (T,3,3))."""
     return default_engine().kabsch_velocity_transform(original_points, corrected_points, rob_speed, batch_gates)
 
 

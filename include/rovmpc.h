@@ -589,7 +589,11 @@ int rovmpc_extract_features(rovmpc_handle *h, const double *P0, const double *P1
  * (batch_gates = 0) for T frames of M cable markers: R = Kabsch rotation of the centred marker
  * sets P[T][M][3] -> Q[T][M][3] (3x3 SVD with the reflection fix), v_out = R @ v.
  * Frames with a non-finite marker, M < 3 or (batch_gates) |P - Q|_F < 1e-6 yield NaN rows,
- * as the reference writes.  R_out[T][9] may be NULL. */
+ * as the reference writes.  So do, with either value of batch_gates, frames that determine no
+ * rotation: a cross-covariance H that is not finite (it overflows for coordinates beyond about
+ * 1e150) or all zero, and marker sets so close to collinear that the computed R is not orthogonal
+ * to 32 eps (a rank-one H; the reference's batch loop gates |R^T R - I| at 1e-2 the same way).
+ * The result does not depend on the unit of the coordinates.  R_out[T][9] may be NULL. */
 int rovmpc_kabsch_velocity_transform(rovmpc_handle *h, const double *P, const double *Q, const double *v,
                                      int64_t T, int32_t M, int32_t batch_gates, double *v_out, double *R_out);
 
