@@ -33,38 +33,29 @@ struct Mailbox {
     unsigned long long seq = 0;                  // last sequence number handed out
 };
 
-// Partial results of an update kernel's workgroups and the ticket word its last workgroup re-arms (zeroed once).
+// Partial results of an update kernel's workgroups and the ticket word its last workgroup re-arms (zeroed once): the set of
+// rovmpc_*_update_device; a controller keeps one per problem in its PlanCtl.
 struct Slab { void *rows = nullptr; unsigned *ticket = nullptr; };
 
-// What a controller that iterates on a plan (MPPI: the nominal; CEM: mean and spread) owns, allocated at its first reset: a
-// candidate tensor, costs, state and record of its own (the other entry points' buffers are never touched), the plan
-// double-buffered by iteration, the update's slab and the mailbox [record, plan*, ..., stats] of its step.
+// What a controller that iterates on a plan (MPPI: the nominal; CEM: mean and spread) owns, for B problems side by side (every
+// per-problem array the one-problem array repeated B times): candidate tensors, costs, states and records of its own (the
+// other entry points' buffers are never touched), the plans double-buffered by iteration, the update's slabs and tickets
+// and the mailbox [B][row] of its step.  Made at rovmpc_*_reset_batch, again when B changes.  `single`: the one-problem
+// controller of rovmpc_*_reset / _step, made at its first reset with B = 1; state and seed reach its sampler as kernel
+// arguments, so it has no staging block and no seeds.
 struct PlanCtl {
-    const char *name, *abi, *step_name;          // "MPPI", "mppi", "MPPI step": for the messages
-    bool allocated = false;
-    void *U = nullptr, *J = nullptr;             // T [K][N][3], T [K]
-    double *state = nullptr, *record = nullptr;
-    double *plan = nullptr, *spread = nullptr;   // [2][3N] each; spread: CEM only
-    int cur = 0;                                 // half of plan (and spread) holding the handle's
-    Slab slab, slab_x;                           // of *_step; of *_update_device (allocated at its first call)
-    Mailbox box;
-    unsigned long long steps = 0;
-};
-
-// The batched form of such a controller (rovmpc_*_step_batch): B problems side by side in buffers of its own, every
-// per-problem array the single-problem array repeated B times; allocated at rovmpc_*_reset_batch, again when B changes.
-struct PlanBatch {
-    const char *name, *abi;                      // "MPPI", "mppi"
+    const char *name, *abi;                      // "MPPI", "mppi": for the messages
+    bool single;
     int B = 0;                                   // 0: no reset yet
     void *U = nullptr, *J = nullptr;             // T [B][K][N][3], T [B][K]
     double *state = nullptr, *record = nullptr;  // [B][16], [B][result_len]
-    unsigned long long *seeds = nullptr;         // [B]: kept by the first sampler of a step for the later ones
+    unsigned long long *seeds = nullptr;         // [B]: kept by the first sampler of a step for the later ones (batched)
     double *plan = nullptr, *spread = nullptr;   // [2][B][3N] each; spread: CEM only
-    int cur = 0;
+    int cur = 0;                                 // half of plan (and spread) holding the handle's
     void *slab = nullptr;                        // [B] slabs of slab_stride 64-bit words
     unsigned *tickets = nullptr;                 // [B] of the problems' updates, then the step's
     size_t slab_stride = 0, row = 0;             // row: 64-bit words per problem of the mailbox
-    double *h_stage = nullptr, *d_stage = nullptr;   // mapped: states [B][16], seeds [B] of the step being enqueued
+    double *h_stage = nullptr, *d_stage = nullptr;   // mapped: states [B][16], seeds [B] of the step being enqueued (batched)
     Mailbox box;                                 // [B][row]
     unsigned long long steps = 0;
 };
@@ -132,8 +123,9 @@ struct rovmpc_handle {
     double *arg_result_host = nullptr; unsigned long long *arg_done_flag = nullptr; unsigned long long arg_done_seq = 0;
     void *arg_J = nullptr;                       // costs of the launch being enqueued go here instead of d_J (null: d_J)
     // MPPI (rovmpc_mppi_*): mailbox [record, nu*, stats]; CEM (rovmpc_cem_*): [record, mu*, sigma*, stats, elite list]
-    PlanCtl mppi{"MPPI", "mppi", "MPPI step"}, cem{"CEM", "cem", "CEM step"};
-    PlanBatch mppi_b{"MPPI", "mppi"}, cem_b{"CEM", "cem"};
+    PlanCtl mppi{"MPPI", "mppi", true}, cem{"CEM", "cem", true};
+    PlanCtl mppi_b{"MPPI", "mppi", false}, cem_b{"CEM", "cem", false};
+    Slab mppi_slab_x, cem_slab_x;                // of rovmpc_*_update_device (allocated at its first call)
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -252,32 +244,6 @@ static int slab_alloc(rovmpc_handle *h, Slab &s, size_t bytes) {
 }
 
 static void plan_free(PlanCtl &c) {
-    dev_free(c.U); dev_free(c.J); dev_free(c.state); dev_free(c.record); dev_free(c.plan); dev_free(c.spread);
-    slab_free(c.slab); slab_free(c.slab_x);
-    mailbox_free(c.box);
-    c.allocated = false;
-}
-
-// The controller's sizes: bytes of its update's slab, doubles behind the record in its mailbox, a spread next to the plan.
-static int plan_alloc(rovmpc_handle *h, PlanCtl &c, size_t slab_bytes, size_t extra_doubles, bool with_spread) {
-    if (c.allocated) return ROVMPC_OK;
-    const size_t K = (size_t)h->cfg.K, C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    hipError_t e = hipSuccess;
-    auto dev = [&e](auto **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void **)p, bytes); };
-    dev(&c.U, K * C3 * h->esz); dev(&c.J, K * h->esz);
-    dev(&c.state, ROVMPC_STATE_LEN * sizeof(double)); dev(&c.record, R * sizeof(double));
-    dev(&c.plan, 2 * C3 * sizeof(double));
-    if (with_spread) dev(&c.spread, 2 * C3 * sizeof(double));
-    int rc = ROVMPC_OK;
-    if (e != hipSuccess) { h->err = std::string(c.name) + " buffers: " + hipGetErrorString(e); rc = ROVMPC_ERR_HIP; }
-    if (!rc) rc = slab_alloc(h, c.slab, slab_bytes);
-    if (!rc) rc = mailbox_alloc(h, c.box, R + extra_doubles);
-    if (rc) plan_free(c);
-    c.allocated = !rc;
-    return rc;
-}
-
-static void plan_batch_free(PlanBatch &c) {
     dev_free(c.U); dev_free(c.J); dev_free(c.state); dev_free(c.record); dev_free(c.seeds); dev_free(c.plan); dev_free(c.spread);
     dev_free(c.slab); dev_free(c.tickets);
     if (c.h_stage) (void)hipHostFree(c.h_stage);
@@ -286,25 +252,28 @@ static void plan_batch_free(PlanBatch &c) {
     c.B = 0;
 }
 
-// Into a fresh PlanBatch, all or nothing: the caller swaps it in, so a failure leaves the previous batched state usable.
-static int plan_batch_alloc(rovmpc_handle *h, PlanBatch &c, int B, size_t slab_words, size_t row_words, bool with_spread) {
+// Into a fresh PlanCtl, all or nothing: the caller swaps it in, so a failure leaves the previous state usable.  The
+// controller's sizes: 64-bit words of a problem's slab and of its mailbox row, a spread next to the plan.
+static int plan_alloc(rovmpc_handle *h, PlanCtl &c, int B, size_t slab_words, size_t row_words, bool with_spread) {
     const size_t K = (size_t)h->cfg.K, C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h), nb = (size_t)B;
     hipError_t e = hipSuccess;
     auto dev = [&e](auto **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void **)p, bytes); };
     dev(&c.U, nb * K * C3 * h->esz); dev(&c.J, nb * K * h->esz);
     dev(&c.state, nb * ROVMPC_STATE_LEN * sizeof(double)); dev(&c.record, nb * R * sizeof(double));
-    dev(&c.seeds, nb * sizeof(unsigned long long));
+    if (!c.single) dev(&c.seeds, nb * sizeof(unsigned long long));
     dev(&c.plan, 2 * nb * C3 * sizeof(double));
     if (with_spread) dev(&c.spread, 2 * nb * C3 * sizeof(double));
     if (slab_words) dev(&c.slab, nb * slab_words * 8);
     dev(&c.tickets, (nb + 1) * sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(c.tickets, 0, (nb + 1) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c.h_stage, nb * (ROVMPC_STATE_LEN + 1) * 8, hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&c.d_stage, c.h_stage, 0);
+    if (!c.single) {
+        if (e == hipSuccess) e = hipHostMalloc((void **)&c.h_stage, nb * (ROVMPC_STATE_LEN + 1) * 8, hipHostMallocMapped);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&c.d_stage, c.h_stage, 0);
+    }
     int rc = ROVMPC_OK;
-    if (e != hipSuccess) { h->err = std::string("batched ") + c.name + " buffers: " + hipGetErrorString(e); rc = ROVMPC_ERR_HIP; }
+    if (e != hipSuccess) { h->err = std::string(c.single ? "" : "batched ") + c.name + " buffers: " + hipGetErrorString(e); rc = ROVMPC_ERR_HIP; }
     if (!rc) rc = mailbox_alloc(h, c.box, nb * row_words);
-    if (rc) { plan_batch_free(c); return rc; }
+    if (rc) { plan_free(c); return rc; }
     c.B = B; c.slab_stride = slab_words; c.row = row_words;
     return ROVMPC_OK;
 }
@@ -553,10 +522,8 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     mailbox_free(h->samp_box);
     if (h->h_err) (void)hipHostFree(h->h_err);
-    plan_free(h->mppi);
-    plan_free(h->cem);
-    plan_batch_free(h->mppi_b);
-    plan_batch_free(h->cem_b);
+    for (PlanCtl *c : {&h->mppi, &h->cem, &h->mppi_b, &h->cem_b}) plan_free(*c);
+    slab_free(h->mppi_slab_x); slab_free(h->cem_slab_x);
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete h->epoch_ctr;
     if (h->h_result) (void)hipHostFree(h->h_result);
@@ -1412,8 +1379,13 @@ extern "C" int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state,
     return ROVMPC_OK;
 }
 
-// ---- controllers that iterate on a plan (MPPI, CEM): what their entry points share ----------------------------------------
-// A controller supplies two launches (its sampler and its update) and two sizes (plan_alloc); everything else is here.
+// ---- controllers that iterate on a plan (MPPI, CEM): one host path for a single problem and for a batch of B -----------------
+// A controller supplies two launches (its sampler and its update) and its sizes (plan_reset); everything else is here.  The
+// one-problem controllers (h->mppi, h->cem) are the B = 1 case with `single` set, which the code below asks about in these
+// places only: how state and seed reach a step's first sampler (kernel arguments and the one-problem sampler, against the
+// mapped staging block and the batched sampler), which update kernel runs (one problem and no step ticket, against
+// blockIdx.y = problem and a step ticket, B = 1 included), the buffers (made once, with no device synchronise) and the
+// wording of the messages.
 static int check_n_iter(rovmpc_handle *h, int n_iter) {
     if (n_iter < 1 || n_iter > 64) FAIL(h, ROVMPC_ERR_INVALID, "n_iter must be in 1..64 (got %d)", n_iter);
     return ROVMPC_OK;
@@ -1430,38 +1402,49 @@ static int check_single_gpu(rovmpc_handle *h, const char *name) {
     return ROVMPC_OK;
 }
 
-// rovmpc_*_reset: the plan goes into half 0 (the spread, where there is one, restarts from std at every step)
-static int plan_reset(rovmpc_handle *h, PlanCtl &c, const double *plan, size_t slab_bytes, size_t extra_doubles, bool with_spread) {
+static const int PLAN_BATCH_MAX = 1024;
+
+static int check_batch_size(rovmpc_handle *h, const char *fn, int B) {
+    if (B < 1 || B > PLAN_BATCH_MAX) FAIL(h, ROVMPC_ERR_INVALID, "%s: B must be in 1..%d (got %d)", fn, PLAN_BATCH_MAX, B);
+    return ROVMPC_OK;
+}
+
+// rovmpc_*_reset and _reset_batch: buffers for B problems (kept when B is the one they were made for, so the single
+// controller's are made at its first reset and never again), the plans into half 0 (the spread, where there is one,
+// restarts from std at every step)
+static int plan_reset(rovmpc_handle *h, PlanCtl &c, int B, const double *plans, size_t slab_words, size_t row_words, bool with_spread) {
     int rc;
     if ((rc = check_single_gpu(h, c.name))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = plan_alloc(h, c, slab_bytes, extra_doubles, with_spread))) return rc;
-    HIPCHK(h, hipMemcpyAsync(c.plan, plan, 3 * (size_t)h->cfg.N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (B != c.B) {
+        PlanCtl fresh{c.name, c.abi, c.single};
+        if ((rc = plan_alloc(h, fresh, B, slab_words, row_words, with_spread))) return rc;
+        if (B > 1 && (rc = ensure_batch(h, B))) { plan_free(fresh); return rc; }     // the batched rollout's workspace
+        if (!c.single) HIPCHK(h, hipDeviceSynchronize());       // nothing may still be using the old buffers (single: there are none)
+        plan_free(c);
+        c = fresh;
+    }
+    HIPCHK(h, hipMemcpyAsync(c.plan, plans, (size_t)B * 3 * h->cfg.N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     c.cur = 0;
     return ROVMPC_OK;
 }
 
-// rovmpc_*_last: host copies of the last iteration's candidates and costs
+// rovmpc_*_last and _last_batch: host copies of the last iteration's candidates and costs
 static int plan_last(rovmpc_handle *h, PlanCtl &c, void *U_out, void *J_out) {
-    if (c.steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_last: no %s yet", c.abi, c.step_name);
+    if (c.steps == 0) {
+        if (c.single) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_last: no %s step yet", c.abi, c.name);
+        else FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_last_batch: no batched %s step yet", c.abi, c.name);
+    }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (U_out) HIPCHK(h, hipMemcpy(U_out, c.U, (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
-    if (J_out) HIPCHK(h, hipMemcpy(J_out, c.J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost));
+    if (U_out) HIPCHK(h, hipMemcpy(U_out, c.U, (size_t)c.B * h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
+    if (J_out) HIPCHK(h, hipMemcpy(J_out, c.J, (size_t)c.B * h->cfg.K * h->esz, hipMemcpyDeviceToHost));
     return ROVMPC_OK;
 }
 
-// the rollout of rovmpc_step on the controller's tensor, costs into its own buffer
-static int plan_rollout(rovmpc_handle *h, PlanCtl &c) {
-    h->arg_J = c.J;
-    const int rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream);
-    h->arg_J = nullptr;
-    return rc;
-}
-
 // A device-resident closed loop around the control steps (rovmpc_*_closed_loop*_device): T steps from the measured rows
-// d_exo [T][16] ([B][T][16] in a batch), each step's row into d_rows [T][W] ([T][B][W]).  PlanLoop{}: one step from a host state.
+// d_exo [T][16] ([B][T][16] in a batch), each step's row into d_rows [T][W] ([T][B][W]).  PlanLoop{}: one step from host states.
 struct PlanLoop {
     const double *d_exo = nullptr;
     long long T = 1;
@@ -1478,59 +1461,120 @@ static int plan_loop_check(rovmpc_handle *h, const char *fn, const void *d_exo, 
     return ROVMPC_OK;
 }
 
-// What the loop hands the two launches of iteration i.  The last group is set in the last iteration only (the update then
-// also shifts the plan by one node, passes the rollout's record on and fills the mailbox); *_update_device passes PlanIter{}.
+// The checks of a single controller's step that need no parameters (entry: "step" or "closed_loop_device")
+static int plan_single_ready(rovmpc_handle *h, PlanCtl &c, const char *entry) {
+    int rc;
+    if ((rc = check_single_gpu(h, c.name))) return rc;
+    if (c.B == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_%s before rovmpc_%s_reset", c.abi, entry, c.abi);
+    return ROVMPC_OK;
+}
+
+// The same of a batched step (null_arg: one of the entry's required pointers, which `args` names, is null)
+static int plan_batch_ready(rovmpc_handle *h, PlanCtl &c, const char *fn, int B, bool null_arg, const char *args) {
+    int rc;
+    if ((rc = check_batch_size(h, fn, B))) return rc;
+    if (null_arg) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (%s)", fn, args);
+    if ((rc = check_single_gpu(h, c.name))) return rc;
+    if (c.B == 0) FAIL(h, ROVMPC_ERR_INVALID, "%s before rovmpc_%s_reset_batch", fn, c.abi);
+    if (B != c.B) FAIL(h, ROVMPC_ERR_INVALID, "%s: B = %d but rovmpc_%s_reset_batch made %d problems", fn, B, c.abi, c.B);
+    return ROVMPC_OK;
+}
+
+// What the loop hands the two launches of iteration i.  The last group is set in the last iteration of a step only (the
+// update then also shifts the plan by one node, passes the rollout's record on and, where the step has a mailbox, fills
+// it); *_update_device passes PlanIter{}.
 struct PlanIter {
     bool first = false;                    // iteration 0 of its step (CEM: the spread restarts from std)
-    const rovmpc_state *state = nullptr;   // iteration 0 of a single step only (the sampler stores it for the step's rollouts)
-    const double *state_src = nullptr;     // iteration 0 of a loop's first step only: the same from device memory
+    // How state and seed reach the sampler.  Single: as kernel arguments, the state in the call's first iteration only
+    // (from the host, or in a loop from device memory); the sampler stores it for the step's rollouts.
+    uint64_t seed = 0;
+    const rovmpc_state *state = nullptr;
+    const double *state_src = nullptr;
+    PlanBatchIn in = {};                   // batched: the staging block, in the call's first iteration only
     uint64_t counter = 0;                  // of the draw: step * n_iter + i (wraps)
-    size_t in = 0, out = 0;                // offsets of the halves of plan (and spread) the iteration reads and writes
+    size_t in_off = 0, out_off = 0;        // offsets of the halves of plan (and spread) the iteration reads and writes: [B][3N] each
     int shift = 0;
     double *record = nullptr, *host_out = nullptr;     // host_out, done_flag: a single step, or the last step of a loop
     unsigned long long *done_flag = nullptr, done_seq = 0;
-    PlanHandoff loop = {};                 // a loop's steps: the row in device memory and the next step's state
+    PlanHandoff loop = {};                 // a loop's steps: the rows in device memory and the next step's states
 };
 
-// rovmpc_*_step and rovmpc_*_closed_loop_device: loop.T x n_iter x (sample, rollout, update) on the handle's stream without a
-// host round trip, then one wait for the mailbox, which the last step's last update fills.  sample(it) and update(it)
-// launch the controller's kernels.
+// All eight step and loop entries: seeds (and, for a step, states) of a batch into the staging block, then
+// loop.T x n_iter x (sample, rollout, update) on the handle's stream without a host round trip, then one wait for the
+// mailbox, which the last step's last update fills.  sample(it) and update(it) launch the controller's kernels.  In a loop
+// (states null) the first sampler takes the states from row 0 of each problem's exo trajectory and every later step finds
+// them where its predecessor left them.
 template <typename Sample, typename Update>
-static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *state, const PlanLoop &loop, uint64_t step, int n_iter,
-                     Sample sample, Update update) {
+static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds,
+                     uint64_t step, int n_iter, Sample sample, Update update) {
     int rc;
-    if ((rc = check_single_gpu(h, c.name))) return rc;
-    if (!c.allocated) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_%s before rovmpc_%s_reset", c.abi, loop.d_rows ? "closed_loop_device" : "step", c.abi);
     if ((rc = check_ready(h))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t C3 = 3 * (size_t)h->cfg.N;
+    if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
+    const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N, exo_stride = (size_t)loop.T * ROVMPC_STATE_LEN;
+    if (!c.single) {
+        if (states) memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
+        memcpy(c.h_stage + B * ROVMPC_STATE_LEN, seeds, B * sizeof(uint64_t));
+    }
     const unsigned long long seq = ++c.box.seq;
     int cur = c.cur;
     for (long long t = 0; t < loop.T; ++t) {
         const bool last_step = t + 1 == loop.T;
         for (int i = 0; i < n_iter; ++i) {
+            const bool start = i == 0 && t == 0;
             PlanIter it;
             it.first = i == 0;
-            if (i == 0 && t == 0) { it.state = state; it.state_src = loop.d_exo; }
+            if (!c.single) it.in = PlanBatchIn{start ? c.d_stage : nullptr, c.state, c.seeds, c.B, loop.d_exo, exo_stride};
+            else { it.seed = *seeds; if (start) { it.state = states; it.state_src = loop.d_exo; } }
             it.counter = (step + (uint64_t)t) * (uint64_t)n_iter + (uint64_t)i;
-            it.in = cur * C3; it.out = (cur ^ 1) * C3; it.done_seq = seq;
+            // (done_seq is read only where done_flag is set, and the strides of `loop` only for problems b > 0: a single
+            // controller's launches carry them too, where the two separate paths left zeros)
+            it.in_off = cur * half; it.out_off = (cur ^ 1) * half; it.done_seq = seq;
             if (i + 1 == n_iter) {
                 it.shift = 1; it.record = c.record;
                 if (last_step) { it.host_out = c.box.d_out; it.done_flag = c.box.d_done; }
                 if (loop.d_rows)
-                    it.loop = PlanHandoff{loop.d_rows + (size_t)t * loop.W, last_step ? nullptr : loop.d_exo + (size_t)(t + 1) * ROVMPC_STATE_LEN,
-                                          c.state, loop.feedback, 0, 0};
+                    it.loop = PlanHandoff{loop.d_rows + (size_t)t * B * loop.W, last_step ? nullptr : loop.d_exo + (size_t)(t + 1) * ROVMPC_STATE_LEN,
+                                          c.state, loop.feedback, loop.W, exo_stride};
             }
             if ((rc = sample(it))) return rc;
-            if ((rc = plan_rollout(h, c))) return rc;
+            const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
+            h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
+            rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream, c.B);
+            h->arg_J = nullptr;
+            h->last_batch = last_batch;
+            if (rc) return rc;
             if ((rc = update(it))) return rc;
             cur ^= 1;
         }
     }
     c.cur = cur;
     c.steps += (unsigned long long)loop.T;
-    return mailbox_wait(h, c.box, seq, c.step_name);
+    return mailbox_wait(h, c.box, seq, c.single ? (std::string(c.name) + " step").c_str() : c.name);      // (the wording of each form's message)
 }
+
+// state and seed of a single controller's sampler: kernel arguments
+template <typename SA> static void plan_single_in(SA &sa, const PlanCtl &c, const PlanIter &it) {
+    sa.seed = it.seed;
+    if (it.state) sa.state = *it.state;
+    sa.state_src = it.state_src;
+    if (it.state || it.state_src) sa.d_state = c.state;
+}
+
+// an update's arguments for the B problems of c (blockIdx.y = problem); only a step with a mailbox takes the step ticket
+template <typename BA, typename A> static BA plan_batch_args(const A &a, const PlanCtl &c) {
+    BA ba;
+    memset(&ba, 0, sizeof(ba));
+    ba.a = a; ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = c.B;
+    if (a.host_out) ba.step_ticket = c.tickets + c.B;
+    return ba;
+}
+
+#define LAUNCH_SAMPLER(kern, h, grid, sa, U)                                                                                  \
+    do {                                                                                                                      \
+        if ((h)->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(kern<double>, grid, dim3(SAMPLER_NT), 0, (h)->stream, sa, (double *)(U)); \
+        else hipLaunchKernelGGL(kern<float>, grid, dim3(SAMPLER_NT), 0, (h)->stream, sa, (float *)(U));                       \
+    } while (0)
 
 // ---- MPPI: sampling around a warm-started nominal, exp(-J/lambda)-weighted update on the GPU -------------------------
 struct MppiGeo { int G; long long slice; };
@@ -1556,48 +1600,79 @@ static size_t mppi_slab_bytes(const rovmpc_handle *h) {
     return (size_t)mppi_geometry(h->cfg.K).G * (3 + 3 * (size_t)h->cfg.N) * sizeof(double);
 }
 
+// row of a control step: record, nu* (3N), stats (4) -- the mailbox row of a problem too
+static size_t mppi_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 3 * (size_t)h->cfg.N + 4; }
+
+extern "C" int32_t rovmpc_mppi_row_len(const rovmpc_handle *h) { return h ? (int32_t)mppi_row_words(h) : 0; }
+
+// The update's launch on problem 0's pointers: one problem (batch null: a single controller, rovmpc_mppi_update_device), or
+// the B problems of *batch.  pub: the iteration's publish fields.
 static int launch_mppi_update(rovmpc_handle *h, const void *d_J, const void *d_U, double lambda, const double *nu_in, double *nu_out,
-                              double *stats, const Slab &slab, const PlanIter &pub, hipStream_t s) {
+                              double *stats, void *slab, unsigned *ticket, const PlanIter &pub, const PlanCtl *batch, hipStream_t s) {
     const MppiGeo g = mppi_geometry(h->cfg.K);
     MppiUpdateArgs a;
     memset(&a, 0, sizeof(a));
     a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.lambda = lambda;
-    a.nu_in = nu_in; a.nu_out = nu_out; a.shift = pub.shift; a.stats = stats; a.slab = (double *)slab.rows; a.ticket = slab.ticket;
+    a.nu_in = nu_in; a.nu_out = nu_out; a.shift = pub.shift; a.stats = stats; a.slab = (double *)slab; a.ticket = ticket;
     a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
     a.loop = pub.loop;
-    LAUNCH_T_QC(mppi_update_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
-    return launched(h, "MPPI update");
+    if (!batch) {
+        LAUNCH_T_QC(mppi_update_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
+        return launched(h, "MPPI update");
+    }
+    const MppiUpdateBatchArgs ba = plan_batch_args<MppiUpdateBatchArgs>(a, *batch);
+    LAUNCH_T_QC(mppi_update_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, batch->B), dim3(MPPI_NT), 0, s, ba);
+    return launched(h, "batched MPPI update");
+}
+
+template <typename SA> static SA mppi_sample_args(const rovmpc_handle *h, const PlanIter &it, const double *std3, const double *nu) {
+    SA sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.counter = it.counter;
+    for (int i = 0; i < 3; ++i) sa.std[i] = std3[i];
+    sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.nu = nu;
+    return sa;
+}
+
+static int launch_mppi_sample(rovmpc_handle *h, const PlanCtl &c, const PlanIter &it, const double *std3) {
+    const double *nu = c.plan + it.in_off;
+    const int gx = sampler_grid((long long)h->cfg.K * h->cfg.N * 3);
+    if (c.single) {
+        MppiSampleArgs sa = mppi_sample_args<MppiSampleArgs>(h, it, std3, nu);
+        plan_single_in(sa, c, it);
+        LAUNCH_SAMPLER(mppi_sample_kernel, h, dim3(gx), sa, c.U);
+        return launched(h, "MPPI sampler");
+    }
+    MppiSampleBatchArgs sa = mppi_sample_args<MppiSampleBatchArgs>(h, it, std3, nu);
+    sa.in = it.in;
+    LAUNCH_SAMPLER(mppi_sample_batch_kernel, h, dim3(gx, c.B), sa, c.U);
+    return launched(h, "batched MPPI sampler");
+}
+
+// one step of c's problems from host states, or a device loop of loop.T steps; then the mailbox rows into the caller's arrays
+static int mppi_run(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds, uint64_t step,
+                    const rovmpc_mppi_params *p, double *records_out = nullptr, double *nominals_out = nullptr, double *stats_out = nullptr) {
+    int rc = plan_step(h, c, states, loop, seeds, step, p->n_iter,
+                       [&](const PlanIter &it) { return launch_mppi_sample(h, c, it, p->std); },
+                       [&](const PlanIter &it) {
+                           return launch_mppi_update(h, c.J, c.U, p->lambda, c.plan + it.in_off, c.plan + it.out_off, nullptr, c.slab,
+                                                     c.tickets, it, c.single ? nullptr : &c, h->stream);
+                       });
+    if (rc) return rc;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
+    for (size_t b = 0; records_out && b < (size_t)c.B; ++b) {
+        const double *o = c.box.h_out + b * c.row;
+        memcpy(records_out + b * R, o, R * sizeof(double));
+        if (nominals_out) memcpy(nominals_out + b * C3, o + R, C3 * sizeof(double));
+        if (stats_out) memcpy(stats_out + b * 4, o + R + C3, 4 * sizeof(double));
+    }
+    return take_device_errors(h);
 }
 
 extern "C" int rovmpc_mppi_reset(rovmpc_handle *h, const double *nominal) {
     if (!h) return ROVMPC_ERR_INVALID;
     if (!nominal) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_reset: null nominal");
-    return plan_reset(h, h->mppi, nominal, mppi_slab_bytes(h), 3 * (size_t)h->cfg.N + 4, false);   // mailbox: record, nu*, stats
-}
-
-static int launch_mppi_sample(rovmpc_handle *h, const PlanIter &it, uint64_t seed, const double *std3, const double *nu) {
-    const uint64_t counter = it.counter;
-    MppiSampleArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    if (it.state) { sa.state = *it.state; sa.d_state = h->mppi.state; }
-    if (it.state_src) { sa.state_src = it.state_src; sa.d_state = h->mppi.state; }
-    sa.seed = seed; sa.counter = counter;
-    for (int i = 0; i < 3; ++i) sa.std[i] = std3[i];
-    sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.nu = nu;
-    const dim3 grid(sampler_grid(sa.total)), bs(SAMPLER_NT);
-    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(mppi_sample_kernel<double>, grid, bs, 0, h->stream, sa, (double *)h->mppi.U);
-    else hipLaunchKernelGGL(mppi_sample_kernel<float>, grid, bs, 0, h->stream, sa, (float *)h->mppi.U);
-    return launched(h, "MPPI sampler");
-}
-
-// one step from a host state, or a device loop of loop.T steps
-static int mppi_run(rovmpc_handle *h, const rovmpc_state *state, const PlanLoop &loop, uint64_t seed, uint64_t step, const rovmpc_mppi_params *p) {
-    PlanCtl &c = h->mppi;
-    return plan_step(h, c, state, loop, step, p->n_iter,
-                     [&](const PlanIter &it) { return launch_mppi_sample(h, it, seed, p->std, c.plan + it.in); },
-                     [&](const PlanIter &it) {
-                         return launch_mppi_update(h, c.J, c.U, p->lambda, c.plan + it.in, c.plan + it.out, nullptr, c.slab, it, h->stream);
-                     });
+    return plan_reset(h, h->mppi, 1, nominal, mppi_slab_bytes(h) / 8, mppi_row_words(h), false);
 }
 
 extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step,
@@ -1605,29 +1680,16 @@ extern "C" int rovmpc_mppi_step(rovmpc_handle *h, const rovmpc_state *state, uin
     if (!h) return ROVMPC_ERR_INVALID;
     if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_step: null pointer");
     int rc = mppi_check_params(h, p);
-    if (rc) return rc;
-    PlanCtl &c = h->mppi;
-    if ((rc = mppi_run(h, state, PlanLoop{}, seed, step, p))) return rc;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    const double *o = c.box.h_out;
-    memcpy(record_out, o, R * sizeof(double));
-    if (nominal_out) memcpy(nominal_out, o + R, C3 * sizeof(double));
-    if (stats_out) memcpy(stats_out, o + R + C3, 4 * sizeof(double));
-    return take_device_errors(h);
+    if (rc || (rc = plan_single_ready(h, h->mppi, "step"))) return rc;
+    return mppi_run(h, h->mppi, state, PlanLoop{}, &seed, step, p, record_out, nominal_out, stats_out);
 }
-
-// row of a control step: record, nu* (3N), stats (4) -- the mailbox row of a batched problem too
-static size_t mppi_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 3 * (size_t)h->cfg.N + 4; }
-
-extern "C" int32_t rovmpc_mppi_row_len(const rovmpc_handle *h) { return h ? (int32_t)mppi_row_words(h) : 0; }
 
 extern "C" int rovmpc_mppi_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, int32_t feedback, uint64_t seed,
                                               uint64_t step0, const rovmpc_mppi_params *p, double *d_rows) {
     if (!h) return ROVMPC_ERR_INVALID;
     int rc = plan_loop_check(h, "rovmpc_mppi_closed_loop_device", d_exo, T, feedback, d_rows);
-    if (rc || (rc = mppi_check_params(h, p))) return rc;
-    if ((rc = mppi_run(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, mppi_row_words(h)}, seed, step0, p))) return rc;
-    return take_device_errors(h);
+    if (rc || (rc = mppi_check_params(h, p)) || (rc = plan_single_ready(h, h->mppi, "closed_loop_device"))) return rc;
+    return mppi_run(h, h->mppi, nullptr, PlanLoop{d_exo, T, feedback, d_rows, mppi_row_words(h)}, &seed, step0, p);
 }
 
 extern "C" int rovmpc_mppi_last(rovmpc_handle *h, void *U_out, void *J_out) {
@@ -1640,9 +1702,38 @@ extern "C" int rovmpc_mppi_update_device(rovmpc_handle *h, const void *d_J, cons
     if (!d_J || !d_U || !d_nominal_in || !d_nominal_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_update_device: null pointer");
     if (!(isfinite(lambda) && lambda > 0)) FAIL(h, ROVMPC_ERR_INVALID, "lambda must be finite and > 0 (got %g)", lambda);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = slab_alloc(h, h->mppi.slab_x, mppi_slab_bytes(h));
+    Slab &x = h->mppi_slab_x;
+    int rc = slab_alloc(h, x, mppi_slab_bytes(h));
     if (rc) return rc;
-    return launch_mppi_update(h, d_J, d_U, lambda, d_nominal_in, d_nominal_out, d_stats, h->mppi.slab_x, PlanIter{}, (hipStream_t)stream);
+    return launch_mppi_update(h, d_J, d_U, lambda, d_nominal_in, d_nominal_out, d_stats, x.rows, x.ticket, PlanIter{}, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int rovmpc_mppi_reset_batch(rovmpc_handle *h, int32_t B, const double *nominals) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_batch_size(h, "rovmpc_mppi_reset_batch", B);
+    if (rc) return rc;
+    if (!nominals) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_reset_batch: null nominals");
+    return plan_reset(h, h->mppi_b, B, nominals, mppi_slab_bytes(h) / 8, mppi_row_words(h), false);
+}
+
+extern "C" int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
+                                      const rovmpc_mppi_params *p, double *records_out, double *nominals_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = plan_batch_ready(h, h->mppi_b, "rovmpc_mppi_step_batch", B, !states || !seeds || !records_out, "states, seeds or records_out");
+    if (rc || (rc = mppi_check_params(h, p))) return rc;
+    return mppi_run(h, h->mppi_b, states, PlanLoop{}, seeds, step, p, records_out, nominals_out, stats_out);
+}
+
+extern "C" int rovmpc_mppi_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
+                                                    const uint64_t *seeds, uint64_t step0, const rovmpc_mppi_params *p, double *d_rows) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = plan_batch_ready(h, h->mppi_b, "rovmpc_mppi_closed_loop_batch_device", B, !d_exo || !seeds || !d_rows, "d_exo, seeds or d_rows");
+    if (rc || (rc = plan_loop_check(h, "rovmpc_mppi_closed_loop_batch_device", d_exo, T, feedback, d_rows)) || (rc = mppi_check_params(h, p))) return rc;
+    return mppi_run(h, h->mppi_b, nullptr, PlanLoop{d_exo, T, feedback, d_rows, mppi_row_words(h)}, seeds, step0, p);
+}
+
+extern "C" int rovmpc_mppi_last_batch(rovmpc_handle *h, void *U_out, void *J_out) {
+    return h ? plan_last(h, h->mppi_b, U_out, J_out) : ROVMPC_ERR_INVALID;
 }
 
 // ---- CEM: clamped sampling around a per-node mean and spread, exact elite selection and refit on the GPU ---------------
@@ -1675,79 +1766,8 @@ static size_t cem_slab_bytes(const rovmpc_handle *h) {
     return g.G > 1 ? (size_t)g.G * (2 + 2 * (size_t)g.Lcap) * sizeof(unsigned long long) : 0;
 }
 
-static int launch_cem_update(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p, const double *mu_in,
-                             const double *sigma_in, double *mu_out, double *sigma_out, long long *elite, double *stats,
-                             const Slab &slab, const PlanIter &pub, long long *host_elite, hipStream_t s) {
-    const CemGeo g = cem_geometry(h->cfg.K);
-    CemUpdateArgs a;
-    memset(&a, 0, sizeof(a));
-    a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.E = p->n_elite; a.Lcap = g.Lcap;
-    a.alpha = p->alpha;
-    for (int i = 0; i < 3; ++i) { a.std[i] = p->std[i]; a.std_min[i] = p->std_min[i]; a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
-    a.mu_in = mu_in; a.sigma_in = sigma_in; a.mu_out = mu_out; a.sigma_out = sigma_out; a.shift = pub.shift;
-    a.elite = elite; a.stats = stats; a.slab = (unsigned long long *)slab.rows; a.ticket = slab.ticket;
-    a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.host_elite = host_elite;
-    a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
-    a.loop = pub.loop;
-    LAUNCH_T_QC(cem_update_kernel, h, a.C3 > CEM_NT, dim3(g.G), dim3(CEM_NT), 0, s, a);
-    return launched(h, "CEM update");
-}
-
-extern "C" int rovmpc_cem_reset(rovmpc_handle *h, const double *mean) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!mean) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_reset: null mean");
-    // mailbox: record, mu* (3N), sigma* (3N), stats (4), then the elite list (int64 [CEM_MAX_ELITE])
-    return plan_reset(h, h->cem, mean, cem_slab_bytes(h), 6 * (size_t)h->cfg.N + 4 + CEM_MAX_ELITE, true);
-}
-
-static int launch_cem_sample(rovmpc_handle *h, const PlanIter &it, uint64_t seed, const rovmpc_cem_params *p,
-                             const double *mu, const double *sigma) {
-    const uint64_t counter = it.counter;
-    CemSampleArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    if (it.state) { sa.state = *it.state; sa.d_state = h->cem.state; }
-    if (it.state_src) { sa.state_src = it.state_src; sa.d_state = h->cem.state; }
-    sa.seed = seed; sa.counter = counter;
-    for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
-    sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.mu = mu; sa.sigma = sigma;
-    const dim3 grid(sampler_grid(sa.total)), bs(SAMPLER_NT);
-    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(cem_sample_kernel<double>, grid, bs, 0, h->stream, sa, (double *)h->cem.U);
-    else hipLaunchKernelGGL(cem_sample_kernel<float>, grid, bs, 0, h->stream, sa, (float *)h->cem.U);
-    return launched(h, "CEM sampler");
-}
-
-// one step from a host state, or a device loop of loop.T steps
-static int cem_run(rovmpc_handle *h, const rovmpc_state *state, const PlanLoop &loop, uint64_t seed, uint64_t step, const rovmpc_cem_params *p) {
-    PlanCtl &c = h->cem;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    return plan_step(h, c, state, loop, step, p->n_iter,
-                     [&](const PlanIter &it) {                                   // sigma_0 = std
-                         return launch_cem_sample(h, it, seed, p, c.plan + it.in, it.first ? nullptr : c.spread + it.in);
-                     },
-                     [&](const PlanIter &it) {
-                         return launch_cem_update(h, c.J, c.U, p, c.plan + it.in, it.first ? nullptr : c.spread + it.in, c.plan + it.out,
-                                                  c.spread + it.out, nullptr, nullptr, c.slab, it,
-                                                  it.host_out ? (long long *)(it.host_out + R + 2 * C3 + 4) : nullptr, h->stream);
-                     });
-}
-
-extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const rovmpc_cem_params *p,
-                               double *record_out, double *mean_out, double *std_out, int64_t *elite_out, double *stats_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_step: null pointer");
-    int rc = cem_check_params(h, p);
-    if (rc) return rc;
-    PlanCtl &c = h->cem;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    if ((rc = cem_run(h, state, PlanLoop{}, seed, step, p))) return rc;
-    const double *o = c.box.h_out;
-    memcpy(record_out, o, R * sizeof(double));
-    if (mean_out) memcpy(mean_out, o + R, C3 * sizeof(double));
-    if (std_out) memcpy(std_out, o + R + C3, C3 * sizeof(double));
-    if (stats_out) memcpy(stats_out, o + R + 2 * C3, 4 * sizeof(double));
-    if (elite_out) memcpy(elite_out, o + R + 2 * C3 + 4, (size_t)p->n_elite * sizeof(int64_t));
-    return take_device_errors(h);
-}
+// mailbox row of a problem: record, mu* (3N), sigma* (3N), stats (4), then the elite list (int64 [CEM_MAX_ELITE])
+static size_t cem_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 6 * (size_t)h->cfg.N + 4 + CEM_MAX_ELITE; }
 
 // row of a loop's control step: record, mu* (3N), sigma* (3N), stats (4), the elite list (n_elite, int64)
 static size_t cem_loop_row_words(const rovmpc_handle *h, int n_elite) { return (size_t)rovmpc_result_len(h) + 6 * (size_t)h->cfg.N + 4 + (size_t)n_elite; }
@@ -1756,13 +1776,102 @@ extern "C" int32_t rovmpc_cem_row_len(const rovmpc_handle *h, int32_t n_elite) {
     return h && n_elite >= 1 && n_elite <= CEM_MAX_ELITE ? (int32_t)cem_loop_row_words(h, n_elite) : 0;
 }
 
+// The update's launch on problem 0's pointers: one problem (batch null: a single controller, rovmpc_cem_update_device), or
+// the B problems of *batch.  pub: the iteration's publish fields; the elite list of a mailbox row lies behind its stats.
+static int launch_cem_update(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p, const double *mu_in,
+                             const double *sigma_in, double *mu_out, double *sigma_out, long long *elite, double *stats,
+                             void *slab, unsigned *ticket, const PlanIter &pub, const PlanCtl *batch, hipStream_t s) {
+    const CemGeo g = cem_geometry(h->cfg.K);
+    CemUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.J = d_J; a.U = d_U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = 3 * h->cfg.N; a.G = g.G; a.E = p->n_elite; a.Lcap = g.Lcap;
+    a.alpha = p->alpha;
+    for (int i = 0; i < 3; ++i) { a.std[i] = p->std[i]; a.std_min[i] = p->std_min[i]; a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
+    a.mu_in = mu_in; a.sigma_in = sigma_in; a.mu_out = mu_out; a.sigma_out = sigma_out; a.shift = pub.shift;
+    a.elite = elite; a.stats = stats; a.slab = (unsigned long long *)slab; a.ticket = ticket;
+    a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out;
+    if (pub.host_out) a.host_elite = (long long *)(pub.host_out + a.R + 2 * a.C3 + 4);
+    a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
+    a.loop = pub.loop;
+    if (!batch) {
+        LAUNCH_T_QC(cem_update_kernel, h, a.C3 > CEM_NT, dim3(g.G), dim3(CEM_NT), 0, s, a);
+        return launched(h, "CEM update");
+    }
+    const CemUpdateBatchArgs ba = plan_batch_args<CemUpdateBatchArgs>(a, *batch);
+    LAUNCH_T_QC(cem_update_batch_kernel, h, a.C3 > CEM_NT, dim3(g.G, batch->B), dim3(CEM_NT), 0, s, ba);
+    return launched(h, "batched CEM update");
+}
+
+template <typename SA> static SA cem_sample_args(const rovmpc_handle *h, const PlanIter &it, const rovmpc_cem_params *p, const double *mu,
+                                                 const double *sigma) {
+    SA sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.counter = it.counter;
+    for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
+    sa.total = (long long)h->cfg.K * h->cfg.N * 3; sa.N = h->cfg.N; sa.mu = mu; sa.sigma = sigma;
+    return sa;
+}
+
+static int launch_cem_sample(rovmpc_handle *h, const PlanCtl &c, const PlanIter &it, const rovmpc_cem_params *p) {
+    const double *mu = c.plan + it.in_off, *sigma = it.first ? nullptr : c.spread + it.in_off;      // sigma_0 = std
+    const int gx = sampler_grid((long long)h->cfg.K * h->cfg.N * 3);
+    if (c.single) {
+        CemSampleArgs sa = cem_sample_args<CemSampleArgs>(h, it, p, mu, sigma);
+        plan_single_in(sa, c, it);
+        LAUNCH_SAMPLER(cem_sample_kernel, h, dim3(gx), sa, c.U);
+        return launched(h, "CEM sampler");
+    }
+    CemSampleBatchArgs sa = cem_sample_args<CemSampleBatchArgs>(h, it, p, mu, sigma);
+    sa.in = it.in;
+    LAUNCH_SAMPLER(cem_sample_batch_kernel, h, dim3(gx, c.B), sa, c.U);
+    return launched(h, "batched CEM sampler");
+}
+
+// one step of c's problems from host states, or a device loop of loop.T steps; then the mailbox rows into the caller's arrays
+static int cem_run(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds, uint64_t step,
+                   const rovmpc_cem_params *p, double *records_out = nullptr, double *means_out = nullptr, double *stds_out = nullptr,
+                   int64_t *elites_out = nullptr, double *stats_out = nullptr) {
+    int rc = plan_step(h, c, states, loop, seeds, step, p->n_iter,
+                       [&](const PlanIter &it) { return launch_cem_sample(h, c, it, p); },
+                       [&](const PlanIter &it) {
+                           return launch_cem_update(h, c.J, c.U, p, c.plan + it.in_off, it.first ? nullptr : c.spread + it.in_off,
+                                                    c.plan + it.out_off, c.spread + it.out_off, nullptr, nullptr, c.slab, c.tickets, it,
+                                                    c.single ? nullptr : &c, h->stream);
+                       });
+    if (rc) return rc;
+    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h), E = (size_t)p->n_elite;
+    for (size_t b = 0; records_out && b < (size_t)c.B; ++b) {
+        const double *o = c.box.h_out + b * c.row;
+        memcpy(records_out + b * R, o, R * sizeof(double));
+        if (means_out) memcpy(means_out + b * C3, o + R, C3 * sizeof(double));
+        if (stds_out) memcpy(stds_out + b * C3, o + R + C3, C3 * sizeof(double));
+        if (stats_out) memcpy(stats_out + b * 4, o + R + 2 * C3, 4 * sizeof(double));
+        if (elites_out) memcpy(elites_out + b * E, o + R + 2 * C3 + 4, E * sizeof(int64_t));
+    }
+    return take_device_errors(h);
+}
+
+extern "C" int rovmpc_cem_reset(rovmpc_handle *h, const double *mean) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!mean) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_reset: null mean");
+    return plan_reset(h, h->cem, 1, mean, cem_slab_bytes(h) / 8, cem_row_words(h), true);
+}
+
+extern "C" int rovmpc_cem_step(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const rovmpc_cem_params *p,
+                               double *record_out, double *mean_out, double *std_out, int64_t *elite_out, double *stats_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!state || !record_out) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_step: null pointer");
+    int rc = cem_check_params(h, p);
+    if (rc || (rc = plan_single_ready(h, h->cem, "step"))) return rc;
+    return cem_run(h, h->cem, state, PlanLoop{}, &seed, step, p, record_out, mean_out, std_out, elite_out, stats_out);
+}
+
 extern "C" int rovmpc_cem_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, int32_t feedback, uint64_t seed,
                                              uint64_t step0, const rovmpc_cem_params *p, double *d_rows) {
     if (!h) return ROVMPC_ERR_INVALID;
     int rc = plan_loop_check(h, "rovmpc_cem_closed_loop_device", d_exo, T, feedback, d_rows);
-    if (rc || (rc = cem_check_params(h, p))) return rc;
-    if ((rc = cem_run(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, cem_loop_row_words(h, p->n_elite)}, seed, step0, p))) return rc;
-    return take_device_errors(h);
+    if (rc || (rc = cem_check_params(h, p)) || (rc = plan_single_ready(h, h->cem, "closed_loop_device"))) return rc;
+    return cem_run(h, h->cem, nullptr, PlanLoop{d_exo, T, feedback, d_rows, cem_loop_row_words(h, p->n_elite)}, &seed, step0, p);
 }
 
 extern "C" int rovmpc_cem_last(rovmpc_handle *h, void *U_out, void *J_out) {
@@ -1778,263 +1887,27 @@ extern "C" int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const
     int rc = cem_check_params(h, p);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = slab_alloc(h, h->cem.slab_x, cem_slab_bytes(h)))) return rc;
+    Slab &x = h->cem_slab_x;
+    if ((rc = slab_alloc(h, x, cem_slab_bytes(h)))) return rc;
     return launch_cem_update(h, d_J, d_U, p, d_mean_in, d_std_in, d_mean_out, d_std_out, (long long *)d_elite_out, d_stats,
-                             h->cem.slab_x, PlanIter{}, nullptr, (hipStream_t)stream);
+                             x.rows, x.ticket, PlanIter{}, nullptr, (hipStream_t)stream);
 }
-
-// ---- batched MPPI and CEM: B independent plans advanced by one call, three launches per iteration for the whole batch ----
-static const int PLAN_BATCH_MAX = 1024;
-
-static int check_batch_size(rovmpc_handle *h, const char *fn, int B) {
-    if (B < 1 || B > PLAN_BATCH_MAX) FAIL(h, ROVMPC_ERR_INVALID, "%s: B must be in 1..%d (got %d)", fn, PLAN_BATCH_MAX, B);
-    return ROVMPC_OK;
-}
-
-// rovmpc_*_reset_batch: buffers for B problems (kept when B is the one they were made for), the plans into half 0
-static int plan_reset_batch(rovmpc_handle *h, PlanBatch &c, int B, const double *plans, size_t slab_words, size_t row_words,
-                            bool with_spread) {
-    int rc;
-    if ((rc = check_single_gpu(h, c.name))) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (B != c.B) {
-        PlanBatch fresh{c.name, c.abi};
-        if ((rc = plan_batch_alloc(h, fresh, B, slab_words, row_words, with_spread))) return rc;
-        if (B > 1 && (rc = ensure_batch(h, B))) { plan_batch_free(fresh); return rc; }     // the batched rollout's workspace
-        HIPCHK(h, hipDeviceSynchronize());           // nothing may still be using the old buffers
-        plan_batch_free(c);
-        c = fresh;
-    }
-    HIPCHK(h, hipMemcpyAsync(c.plan, plans, (size_t)B * 3 * h->cfg.N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    c.cur = 0;
-    return ROVMPC_OK;
-}
-
-static int plan_last_batch(rovmpc_handle *h, PlanBatch &c, void *U_out, void *J_out) {
-    if (c.steps == 0) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_%s_last_batch: no batched %s step yet", c.abi, c.name);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (U_out) HIPCHK(h, hipMemcpy(U_out, c.U, (size_t)c.B * h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
-    if (J_out) HIPCHK(h, hipMemcpy(J_out, c.J, (size_t)c.B * h->cfg.K * h->esz, hipMemcpyDeviceToHost));
-    return ROVMPC_OK;
-}
-
-// What the loop hands the two launches of iteration i of a batched step (PlanIter's counterpart)
-struct PlanBatchIter {
-    PlanBatchIn in;                        // stage set in iteration 0 only
-    uint64_t counter = 0;
-    size_t in_off = 0, out_off = 0;        // offsets of the halves of plan (and spread): [B][3N] each
-    bool first = false, last = false;      // of its step
-    bool publish = false;                  // last, and the step has a mailbox: a single step, or the last step of a loop
-    unsigned long long done_seq = 0;
-    PlanHandoff loop = {};                 // a loop's steps (last iteration): the rows in device memory and the next states
-};
-
-// The checks of a batched step that need no parameters, before anything is launched
-// (null_arg: one of the entry's required pointers, which `args` names, is null)
-static int plan_batch_ready(rovmpc_handle *h, PlanBatch &c, const char *fn, int B, bool null_arg, const char *args) {
-    int rc;
-    if ((rc = check_batch_size(h, fn, B))) return rc;
-    if (null_arg) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (%s)", fn, args);
-    if ((rc = check_single_gpu(h, c.name))) return rc;
-    if (c.B == 0) FAIL(h, ROVMPC_ERR_INVALID, "%s before rovmpc_%s_reset_batch", fn, c.abi);
-    if (B != c.B) FAIL(h, ROVMPC_ERR_INVALID, "%s: B = %d but rovmpc_%s_reset_batch made %d problems", fn, B, c.abi, c.B);
-    return ROVMPC_OK;
-}
-
-// rovmpc_*_step_batch and rovmpc_*_closed_loop_batch_device: seeds (and, for a single step, states) into the staging block,
-// loop.T x n_iter x (sample, batched rollout, update) on the handle's stream without a host round trip, then one wait for
-// the whole batch's mailbox, which the last step's last update fills.  In a loop (states null) the first sampler takes the
-// states from row 0 of each problem's exo trajectory and every later step finds them where its predecessor left them.
-template <typename Sample, typename Update>
-static int plan_step_batch(rovmpc_handle *h, PlanBatch &c, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds,
-                           uint64_t step, int n_iter, Sample sample, Update update) {
-    int rc;
-    if ((rc = check_ready(h))) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
-    const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N;
-    if (states) memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
-    memcpy(c.h_stage + B * ROVMPC_STATE_LEN, seeds, B * sizeof(uint64_t));
-    const size_t exo_stride = (size_t)loop.T * ROVMPC_STATE_LEN;
-    const unsigned long long seq = ++c.box.seq;
-    int cur = c.cur;
-    for (long long t = 0; t < loop.T; ++t) {
-        const bool last_step = t + 1 == loop.T;
-        for (int i = 0; i < n_iter; ++i) {
-            PlanBatchIter it;
-            it.in = PlanBatchIn{i == 0 && t == 0 ? c.d_stage : nullptr, c.state, c.seeds, c.B, loop.d_exo, exo_stride};
-            it.counter = (step + (uint64_t)t) * (uint64_t)n_iter + (uint64_t)i;
-            it.in_off = cur * half; it.out_off = (cur ^ 1) * half; it.first = i == 0; it.last = i + 1 == n_iter; it.done_seq = seq;
-            it.publish = it.last && last_step;
-            if (it.last && loop.d_rows)
-                it.loop = PlanHandoff{loop.d_rows + (size_t)t * B * loop.W, last_step ? nullptr : loop.d_exo + (size_t)(t + 1) * ROVMPC_STATE_LEN,
-                                      c.state, loop.feedback, loop.W, exo_stride};
-            if ((rc = sample(it))) return rc;
-            const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
-            h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
-            rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream, c.B);
-            h->arg_J = nullptr;
-            h->last_batch = last_batch;
-            if (rc) return rc;
-            if ((rc = update(it))) return rc;
-            cur ^= 1;
-        }
-    }
-    c.cur = cur;
-    c.steps += (unsigned long long)loop.T;
-    return mailbox_wait(h, c.box, seq, c.name);
-}
-
-extern "C" int rovmpc_mppi_reset_batch(rovmpc_handle *h, int32_t B, const double *nominals) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    int rc = check_batch_size(h, "rovmpc_mppi_reset_batch", B);
-    if (rc) return rc;
-    if (!nominals) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_reset_batch: null nominals");
-    return plan_reset_batch(h, h->mppi_b, B, nominals, mppi_slab_bytes(h) / 8, mppi_row_words(h), false);
-}
-
-// one step of the batch from host states, or a device loop of loop.T steps
-static int mppi_run_batch(rovmpc_handle *h, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds, uint64_t step,
-                          const rovmpc_mppi_params *p) {
-    PlanBatch &c = h->mppi_b;
-    const int B = c.B;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    const long long total = (long long)h->cfg.K * h->cfg.N * 3;
-    return plan_step_batch(h, c, states, loop, seeds, step, p->n_iter,
-                         [&](const PlanBatchIter &it) {
-                             MppiSampleBatchArgs sa;
-                             memset(&sa, 0, sizeof(sa));
-                             sa.in = it.in; sa.counter = it.counter;
-                             for (int i = 0; i < 3; ++i) sa.std[i] = p->std[i];
-                             sa.total = total; sa.N = h->cfg.N; sa.nu = c.plan + it.in_off;
-                             const dim3 grid(sampler_grid(total), B), bs(SAMPLER_NT);
-                             if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(mppi_sample_batch_kernel<double>, grid, bs, 0, h->stream, sa, (double *)c.U);
-                             else hipLaunchKernelGGL(mppi_sample_batch_kernel<float>, grid, bs, 0, h->stream, sa, (float *)c.U);
-                             return launched(h, "batched MPPI sampler");
-                         },
-                         [&](const PlanBatchIter &it) {
-                             const MppiGeo g = mppi_geometry(h->cfg.K);
-                             MppiUpdateBatchArgs ba;
-                             memset(&ba, 0, sizeof(ba));
-                             MppiUpdateArgs &a = ba.a;
-                             a.J = c.J; a.U = c.U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = (int)C3; a.G = g.G; a.lambda = p->lambda;
-                             a.nu_in = c.plan + it.in_off; a.nu_out = c.plan + it.out_off; a.slab = (double *)c.slab; a.ticket = c.tickets;
-                             a.R = (int)R;
-                             ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = B;
-                             if (it.last) { a.shift = 1; a.record = c.record; a.loop = it.loop; }
-                             if (it.publish) {
-                                 a.host_out = c.box.d_out; a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
-                                 ba.step_ticket = c.tickets + B;
-                             }
-                             LAUNCH_T_QC(mppi_update_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, B), dim3(MPPI_NT), 0, h->stream, ba);
-                             return launched(h, "batched MPPI update");
-                         });
-}
-
-extern "C" int rovmpc_mppi_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
-                                      const rovmpc_mppi_params *p, double *records_out, double *nominals_out, double *stats_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    PlanBatch &c = h->mppi_b;
-    int rc = plan_batch_ready(h, c, "rovmpc_mppi_step_batch", B, !states || !seeds || !records_out, "states, seeds or records_out");
-    if (rc || (rc = mppi_check_params(h, p))) return rc;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    if ((rc = mppi_run_batch(h, states, PlanLoop{}, seeds, step, p))) return rc;
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        const double *o = c.box.h_out + b * c.row;
-        memcpy(records_out + b * R, o, R * sizeof(double));
-        if (nominals_out) memcpy(nominals_out + b * C3, o + R, C3 * sizeof(double));
-        if (stats_out) memcpy(stats_out + b * 4, o + R + C3, 4 * sizeof(double));
-    }
-    return take_device_errors(h);
-}
-
-extern "C" int rovmpc_mppi_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
-                                                    const uint64_t *seeds, uint64_t step0, const rovmpc_mppi_params *p, double *d_rows) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    int rc = plan_batch_ready(h, h->mppi_b, "rovmpc_mppi_closed_loop_batch_device", B, !d_exo || !seeds || !d_rows, "d_exo, seeds or d_rows");
-    if (rc || (rc = plan_loop_check(h, "rovmpc_mppi_closed_loop_batch_device", d_exo, T, feedback, d_rows)) || (rc = mppi_check_params(h, p))) return rc;
-    if ((rc = mppi_run_batch(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, mppi_row_words(h)}, seeds, step0, p))) return rc;
-    return take_device_errors(h);
-}
-
-extern "C" int rovmpc_mppi_last_batch(rovmpc_handle *h, void *U_out, void *J_out) {
-    return h ? plan_last_batch(h, h->mppi_b, U_out, J_out) : ROVMPC_ERR_INVALID;
-}
-
-// mailbox row of a problem: record, mu* (3N), sigma* (3N), stats (4), then the elite list (int64 [CEM_MAX_ELITE])
-static size_t cem_row_words(const rovmpc_handle *h) { return (size_t)rovmpc_result_len(h) + 6 * (size_t)h->cfg.N + 4 + CEM_MAX_ELITE; }
 
 extern "C" int rovmpc_cem_reset_batch(rovmpc_handle *h, int32_t B, const double *means) {
     if (!h) return ROVMPC_ERR_INVALID;
     int rc = check_batch_size(h, "rovmpc_cem_reset_batch", B);
     if (rc) return rc;
     if (!means) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_cem_reset_batch: null means");
-    return plan_reset_batch(h, h->cem_b, B, means, cem_slab_bytes(h) / 8, cem_row_words(h), true);
-}
-
-// one step of the batch from host states, or a device loop of loop.T steps
-static int cem_run_batch(rovmpc_handle *h, const rovmpc_state *states, const PlanLoop &loop, const uint64_t *seeds, uint64_t step,
-                         const rovmpc_cem_params *p) {
-    PlanBatch &c = h->cem_b;
-    const int B = c.B;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    const long long total = (long long)h->cfg.K * h->cfg.N * 3;
-    return plan_step_batch(h, c, states, loop, seeds, step, p->n_iter,
-                         [&](const PlanBatchIter &it) {                           // sigma_0 = std
-                             CemSampleBatchArgs sa;
-                             memset(&sa, 0, sizeof(sa));
-                             sa.in = it.in; sa.counter = it.counter;
-                             for (int i = 0; i < 3; ++i) { sa.std[i] = p->std[i]; sa.lo[i] = p->lo[i]; sa.hi[i] = p->hi[i]; }
-                             sa.total = total; sa.N = h->cfg.N; sa.mu = c.plan + it.in_off; sa.sigma = it.first ? nullptr : c.spread + it.in_off;
-                             const dim3 grid(sampler_grid(total), B), bs(SAMPLER_NT);
-                             if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(cem_sample_batch_kernel<double>, grid, bs, 0, h->stream, sa, (double *)c.U);
-                             else hipLaunchKernelGGL(cem_sample_batch_kernel<float>, grid, bs, 0, h->stream, sa, (float *)c.U);
-                             return launched(h, "batched CEM sampler");
-                         },
-                         [&](const PlanBatchIter &it) {
-                             const CemGeo g = cem_geometry(h->cfg.K);
-                             CemUpdateBatchArgs ba;
-                             memset(&ba, 0, sizeof(ba));
-                             CemUpdateArgs &a = ba.a;
-                             a.J = c.J; a.U = c.U; a.K = h->cfg.K; a.slice = g.slice; a.C3 = (int)C3; a.G = g.G; a.E = p->n_elite; a.Lcap = g.Lcap;
-                             a.alpha = p->alpha;
-                             for (int i = 0; i < 3; ++i) { a.std[i] = p->std[i]; a.std_min[i] = p->std_min[i]; a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
-                             a.mu_in = c.plan + it.in_off; a.sigma_in = it.first ? nullptr : c.spread + it.in_off;
-                             a.mu_out = c.plan + it.out_off; a.sigma_out = c.spread + it.out_off;
-                             a.slab = (unsigned long long *)c.slab; a.ticket = c.tickets; a.R = (int)R;
-                             ba.slab_stride = c.slab_stride; ba.host_stride = c.row; ba.B = B;
-                             if (it.last) { a.shift = 1; a.record = c.record; a.loop = it.loop; }
-                             if (it.publish) {
-                                 a.host_out = c.box.d_out;
-                                 a.host_elite = (long long *)(c.box.d_out + R + 2 * C3 + 4);
-                                 a.done_flag = c.box.d_done; a.done_seq = it.done_seq;
-                                 ba.step_ticket = c.tickets + B;
-                             }
-                             LAUNCH_T_QC(cem_update_batch_kernel, h, a.C3 > CEM_NT, dim3(g.G, B), dim3(CEM_NT), 0, h->stream, ba);
-                             return launched(h, "batched CEM update");
-                         });
+    return plan_reset(h, h->cem_b, B, means, cem_slab_bytes(h) / 8, cem_row_words(h), true);
 }
 
 extern "C" int rovmpc_cem_step_batch(rovmpc_handle *h, int32_t B, const rovmpc_state *states, const uint64_t *seeds, uint64_t step,
                                      const rovmpc_cem_params *p, double *records_out, double *means_out, double *stds_out,
                                      int64_t *elites_out, double *stats_out) {
     if (!h) return ROVMPC_ERR_INVALID;
-    PlanBatch &c = h->cem_b;
-    int rc = plan_batch_ready(h, c, "rovmpc_cem_step_batch", B, !states || !seeds || !records_out, "states, seeds or records_out");
+    int rc = plan_batch_ready(h, h->cem_b, "rovmpc_cem_step_batch", B, !states || !seeds || !records_out, "states, seeds or records_out");
     if (rc || (rc = cem_check_params(h, p))) return rc;
-    const size_t C3 = 3 * (size_t)h->cfg.N, R = (size_t)rovmpc_result_len(h);
-    if ((rc = cem_run_batch(h, states, PlanLoop{}, seeds, step, p))) return rc;
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        const double *o = c.box.h_out + b * c.row;
-        memcpy(records_out + b * R, o, R * sizeof(double));
-        if (means_out) memcpy(means_out + b * C3, o + R, C3 * sizeof(double));
-        if (stds_out) memcpy(stds_out + b * C3, o + R + C3, C3 * sizeof(double));
-        if (stats_out) memcpy(stats_out + b * 4, o + R + 2 * C3, 4 * sizeof(double));
-        if (elites_out) memcpy(elites_out + b * (size_t)p->n_elite, o + R + 2 * C3 + 4, (size_t)p->n_elite * sizeof(int64_t));
-    }
-    return take_device_errors(h);
+    return cem_run(h, h->cem_b, states, PlanLoop{}, seeds, step, p, records_out, means_out, stds_out, elites_out, stats_out);
 }
 
 extern "C" int rovmpc_cem_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
@@ -2042,12 +1915,11 @@ extern "C" int rovmpc_cem_closed_loop_batch_device(rovmpc_handle *h, int32_t B, 
     if (!h) return ROVMPC_ERR_INVALID;
     int rc = plan_batch_ready(h, h->cem_b, "rovmpc_cem_closed_loop_batch_device", B, !d_exo || !seeds || !d_rows, "d_exo, seeds or d_rows");
     if (rc || (rc = plan_loop_check(h, "rovmpc_cem_closed_loop_batch_device", d_exo, T, feedback, d_rows)) || (rc = cem_check_params(h, p))) return rc;
-    if ((rc = cem_run_batch(h, nullptr, PlanLoop{d_exo, T, feedback, d_rows, cem_loop_row_words(h, p->n_elite)}, seeds, step0, p))) return rc;
-    return take_device_errors(h);
+    return cem_run(h, h->cem_b, nullptr, PlanLoop{d_exo, T, feedback, d_rows, cem_loop_row_words(h, p->n_elite)}, seeds, step0, p);
 }
 
 extern "C" int rovmpc_cem_last_batch(rovmpc_handle *h, void *U_out, void *J_out) {
-    return h ? plan_last_batch(h, h->cem_b, U_out, J_out) : ROVMPC_ERR_INVALID;
+    return h ? plan_last(h, h->cem_b, U_out, J_out) : ROVMPC_ERR_INVALID;
 }
 
 // ---- timing ---------------------------------------------------------------------------------

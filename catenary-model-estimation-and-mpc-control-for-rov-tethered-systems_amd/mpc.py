@@ -164,9 +164,27 @@ def _run_on_device(engine, rows: np.ndarray, W: int, lead: tuple, call) -> np.nd
     return out.cpu().numpy()
 
 
+def _stats_dict(names, stats: np.ndarray) -> dict:
+    """``last_stats`` from stats (4,) of a single controller (scalars) or (B, 4) of a batched one (columns); n_finite counts."""
+    if stats.ndim == 1:
+        return {k: int(v) if k == "n_finite" else float(v) for k, v in zip(names, stats)}
+    return {k: stats[:, i].astype(np.int64) if k == "n_finite" else stats[:, i].copy() for i, k in enumerate(names)}
+
+
+def _default_std(std) -> np.ndarray:
+    return np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
+
+
+def _config_value(cfg, overrides: dict, name: str) -> int:
+    """N or K of the engine a controller is about to make, for the checks that come before it exists."""
+    return int(overrides[name]) if name in overrides else getattr(cfg if cfg is not None else MPCConfig(), name)
+
+
 class _PlanController:
-    """What MPPI and CEM share: an engine of their own, the seed and step counter of the draws, the plan's shape and the
-    result of the last step."""
+    """What the four controllers share: an engine of their own, the seed and step counter of the draws, the plan's shape
+    and the result of the last step.  The single-problem form; _BatchedPlanController overrides what a batch changes."""
+
+    _batch = ""         # "_batch": the engine's batched entries
 
     def __init__(self, cfg, model, seed: int, overrides: dict):
         self.seed = int(seed)
@@ -174,8 +192,11 @@ class _PlanController:
         self.cfg = self.engine.cfg
         self._default_mean = np.asarray(default_model().mean[3:6], dtype=np.float64)
         self.step_count = 0
-        self.last: Optional[StepResult] = None
-        self.last_stats: Optional[dict] = None
+        self.last = self.last_stats = None       # StepResult (batched: a list of them), dict
+
+    def _entry(self, name: str):
+        """engine.mppi_step, engine.cem_reset_batch, ..."""
+        return getattr(self.engine, f"{self._kind}_{name}{self._batch}")
 
     def _plan(self, value, name: str) -> np.ndarray:
         """(N, 3) from (N, 3), from (3,) repeated on every node, or from None (the scaler mean of x3..x5)."""
@@ -187,17 +208,115 @@ class _PlanController:
             raise ValueError(f"{name} must have shape ({N}, 3) or (3,), got {plan.shape}")
         return plan
 
+    def _seeds(self):
+        return self.seed
+
+    def _states(self, state):
+        return state
+
+    def _loop_rows(self, rows) -> np.ndarray:
+        return loop_rows(rows)
+
     def _took_step(self, rec, stats: dict) -> np.ndarray:
         self.step_count += 1
         self.last = StepResult.from_record(rec, self.cfg.N)
         self.last_stats = stats
         return self.last.u
 
+    def _run(self, rows, feedback) -> PlanLoopResult:
+        """The loop of ``run``; leaves everything but the plan as T calls of ``step`` would."""
+        r, fb = self._loop_rows(rows), loop_feedback(feedback)
+        e, T = self.engine, r.shape[-2]
+        loop = getattr(e, f"{self._kind}_closed_loop{self._batch}_device")
+        out = _run_on_device(e, r, self._row_len(), (T,) + r.shape[:-2], lambda d_exo, d_rows: loop(
+            d_exo, T, fb, self._seeds(), self.step_count, self.params, d_rows))
+        res = self._split(out)
+        self._took_step(res.records[-1].copy(), _stats_dict(self._stats, res.stats[-1]))
+        self.step_count += T - 1
+        return res
+
     def close(self):
         self.engine.close()
 
 
-class MPPI(_PlanController):
+class _MPPILaw:
+    """What MPPI and BatchedMPPI share: the parameters, the engine's mppi_* entries and the layout of a loop's row."""
+
+    _kind, _stats = "mppi", ("rho", "eta", "ess", "J0")
+
+    def _row_len(self) -> int:
+        return self.engine.mppi_row_len()
+
+    def _split(self, rows) -> PlanLoopResult:
+        return split_rows(rows, self.engine.result_len, self.cfg.N)
+
+    def _set_params(self, lam, std, n_iter):
+        self.std = _default_std(std)
+        self.params = _lib.MPPIParams.make(n_iter, lam, self.std)        # ValueError before the library is called
+        self.lam, self.n_iter = float(lam), int(n_iter)
+        self.nominal: Optional[np.ndarray] = None
+
+    def reset(self, nominal=None):
+        """Set the nominal plan ((N, 3), or (3,) repeated on every node; batched: (B, N, 3) too; default: the scaler mean)."""
+        nu = self._plan(nominal, "nominal")
+        self._entry("reset")(nu)
+        self.nominal = nu.copy()
+
+    def step(self, state) -> np.ndarray:
+        rec, self.nominal, stats = self._entry("step")(self._states(state), self._seeds(), self.step_count, self.params)
+        return self._took_step(rec, _stats_dict(self._stats, stats))
+
+    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
+        """T = len(rows) control steps by one library call, the plant update on the GPU (rovmpc_mppi_closed_loop_device):
+        ``rows`` (T, 16) measured states; ``feedback``: from the second step on (theta, gamma) are the model's own first
+        predicted node.  Row i is what ``step`` would return on the state the plant rule gives; ``step`` and ``run``
+        interleave (the step counter advances by T).  Batched (rovmpc_mppi_closed_loop_batch_device): ``rows`` (B, T, 16), or
+        (T, 16) given to every problem; the arrays are (T, B, ...), problem b's those of ``MPPI(seed=seeds[b],
+        nominal=nominal[b]).run(rows[b])``."""
+        res = self._run(rows, feedback)
+        self.nominal = res.plans[-1].copy()
+        return res
+
+
+class _CEMLaw:
+    """What CEM and BatchedCEM share: the parameters, the engine's cem_* entries and the layout of a loop's row."""
+
+    _kind, _stats = "cem", ("J_best", "J_worst_elite", "n_finite", "J0")
+
+    def _row_len(self) -> int:
+        return self.engine.cem_row_len(self.n_elite)
+
+    def _split(self, rows) -> PlanLoopResult:
+        return split_rows(rows, self.engine.result_len, self.cfg.N, self.n_elite)
+
+    def _set_params(self, cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved):
+        K = _config_value(cfg, overrides, "K")
+        if n_elite is None:
+            n_elite = max(K // 64, 1)
+        if isinstance(n_elite, bool) or int(n_elite) != n_elite or int(n_elite) > K:
+            raise ValueError(f"n_elite must be an integer <= K = {K} (got {n_elite!r})")
+        self.params = _lib.CEMParams.make(n_iter, n_elite, alpha, _default_std(std), std_min, lo, hi, reserved)   # ValueError before the library is called
+        self.n_iter, self.n_elite, self.alpha = int(n_iter), int(n_elite), float(alpha)
+        self.mean = self.std = self.elites = None
+
+    def reset(self, mean=None):
+        """Set the mean plan ((N, 3), or (3,) repeated on every node; batched: (B, N, 3) too; default: the scaler mean)."""
+        mu = self._plan(mean, "mean")
+        self._entry("reset")(mu)
+        self.mean = mu.copy()
+
+    def step(self, state) -> np.ndarray:
+        rec, self.mean, self.std, self.elites, stats = self._entry("step")(self._states(state), self._seeds(), self.step_count, self.params)
+        return self._took_step(rec, _stats_dict(self._stats, stats))
+
+    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
+        """T control steps by one library call (rovmpc_cem_closed_loop_device / _batch_device); see ``MPPI.run``."""
+        res = self._run(rows, feedback)
+        self.mean, self.std, self.elites = res.plans[-1].copy(), res.spreads[-1].copy(), res.elites[-1].copy()
+        return res
+
+
+class MPPI(_MPPILaw, _PlanController):
     """``mppi = MPPI(N=20, K=4096, lam=1.0); u = mppi.step(state)``: model-predictive path integral control.
 
     The handle keeps a nominal plan (N, 3); each step samples K candidates around it on the GPU (candidate 0 = the nominal),
@@ -209,40 +328,12 @@ class MPPI(_PlanController):
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, lam: float = 1.0, std=None,
                  n_iter: int = 1, seed: int = 20250523, nominal=None, **overrides):
-        self.std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
-        self.params = _lib.MPPIParams.make(n_iter, lam, self.std)        # ValueError before the library is called
-        self.lam, self.n_iter = float(lam), int(n_iter)
+        self._set_params(lam, std, n_iter)
         super().__init__(cfg, model, seed, overrides)
-        self.nominal: Optional[np.ndarray] = None
         self.reset(nominal)
 
-    def reset(self, nominal=None):
-        """Set the nominal plan ((N, 3), or (3,) repeated on every node; default: the scaler mean of x3..x5)."""
-        nu = self._plan(nominal, "nominal")
-        self.engine.mppi_reset(nu)
-        self.nominal = nu.copy()
 
-    def step(self, state) -> np.ndarray:
-        rec, self.nominal, stats = self.engine.mppi_step(state, self.seed, self.step_count, self.params)
-        return self._took_step(rec, {"rho": float(stats[0]), "eta": float(stats[1]), "ess": float(stats[2]), "J0": float(stats[3])})
-
-    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
-        """T = len(rows) control steps by one library call, the plant update on the GPU (rovmpc_mppi_closed_loop_device):
-        ``rows`` (T, 16) measured states; ``feedback``: from the second step on (theta, gamma) are the model's own first
-        predicted node.  Row i is what ``step`` would return on the state the plant rule gives; ``step`` and ``run``
-        interleave (the step counter advances by T)."""
-        r, fb = loop_rows(rows), loop_feedback(feedback)
-        e, T = self.engine, len(r)
-        out = _run_on_device(e, r, e.mppi_row_len(), (T,), lambda d_exo, d_rows: e.mppi_closed_loop_device(
-            d_exo, T, fb, self.seed, self.step_count, self.params, d_rows))
-        res = split_rows(out, e.result_len, self.cfg.N)
-        self.nominal = res.plans[-1].copy()
-        self._took_step(res.records[-1], dict(zip(("rho", "eta", "ess", "J0"), map(float, res.stats[-1]))))
-        self.step_count += T - 1
-        return res
-
-
-class CEM(_PlanController):
+class CEM(_CEMLaw, _PlanController):
     """``cem = CEM(N=20, K=4096, n_elite=64); u = cem.step(state)``: the cross-entropy method.
 
     The handle keeps a mean plan (N, 3); each step samples K candidates on the GPU around it with a per-node spread, clamped
@@ -258,42 +349,9 @@ class CEM(_PlanController):
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, n_elite: Optional[int] = None,
                  n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0), lo=(-np.inf,) * 3, hi=(np.inf,) * 3,
                  seed: int = 20250523, mean=None, reserved: int = 0, **overrides):
-        K = int(overrides["K"]) if "K" in overrides else (cfg.K if cfg is not None else MPCConfig().K)
-        if n_elite is None:
-            n_elite = max(K // 64, 1)
-        if isinstance(n_elite, bool) or int(n_elite) != n_elite or int(n_elite) > K:
-            raise ValueError(f"n_elite must be an integer <= K = {K} (got {n_elite!r})")
-        std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
-        self.params = _lib.CEMParams.make(n_iter, n_elite, alpha, std, std_min, lo, hi, reserved)   # ValueError before the library is called
-        self.n_iter, self.n_elite, self.alpha = int(n_iter), int(n_elite), float(alpha)
+        self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
         super().__init__(cfg, model, seed, overrides)
-        self.mean: Optional[np.ndarray] = None
-        self.std: Optional[np.ndarray] = None
-        self.elites: Optional[np.ndarray] = None
         self.reset(mean)
-
-    def reset(self, mean=None):
-        """Set the mean plan ((N, 3), or (3,) repeated on every node; default: the scaler mean of x3..x5)."""
-        mu = self._plan(mean, "mean")
-        self.engine.cem_reset(mu)
-        self.mean = mu.copy()
-
-    def step(self, state) -> np.ndarray:
-        rec, self.mean, self.std, self.elites, stats = self.engine.cem_step(state, self.seed, self.step_count, self.params)
-        return self._took_step(rec, {"J_best": float(stats[0]), "J_worst_elite": float(stats[1]), "n_finite": int(stats[2]),
-                                     "J0": float(stats[3])})
-
-    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
-        """T = len(rows) control steps by one library call (rovmpc_cem_closed_loop_device); see ``MPPI.run``."""
-        r, fb = loop_rows(rows), loop_feedback(feedback)
-        e, T = self.engine, len(r)
-        out = _run_on_device(e, r, e.cem_row_len(self.n_elite), (T,), lambda d_exo, d_rows: e.cem_closed_loop_device(
-            d_exo, T, fb, self.seed, self.step_count, self.params, d_rows))
-        res = split_rows(out, e.result_len, self.cfg.N, self.n_elite)
-        self.mean, self.std, self.elites, st = res.plans[-1].copy(), res.spreads[-1].copy(), res.elites[-1].copy(), res.stats[-1]
-        self._took_step(res.records[-1], {"J_best": float(st[0]), "J_worst_elite": float(st[1]), "n_finite": int(st[2]), "J0": float(st[3])})
-        self.step_count += T - 1
-        return res
 
 
 BATCH_MAX = 1024      # problems of a batched controller (PLAN_BATCH_MAX of the library)
@@ -327,10 +385,6 @@ def batch_states(states, B: int) -> np.ndarray:
     return st
 
 
-def _config_N(cfg, overrides) -> int:
-    return int(overrides["N"]) if "N" in overrides else (cfg.N if cfg is not None else MPCConfig().N)
-
-
 def check_batch(B, seed: int, seeds, plan, N: int, name: str):
     """B, the seeds and the shape of the plans of a batched controller, checked before an engine exists (ValueError);
     returns (B, seeds (B,) uint64)."""
@@ -346,23 +400,38 @@ def check_batch(B, seed: int, seeds, plan, N: int, name: str):
 class _BatchedPlanController(_PlanController):
     """What BatchedMPPI and BatchedCEM share on top of _PlanController: B, the seeds and the per-problem results."""
 
+    _batch = "_batch"
+
     def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict):
-        self.B, self.seeds = check_batch(B, seed, seeds, plan, _config_N(cfg, overrides), name)
+        self.B, self.seeds = check_batch(B, seed, seeds, plan, _config_value(cfg, overrides, "N"), name)
         super().__init__(cfg, model, int(self.seeds[0]), overrides)
         self.records: Optional[np.ndarray] = None
 
-    def _plans(self, value, name: str) -> np.ndarray:
+    def _seeds(self):
+        return self.seeds
+
+    def _plan(self, value, name: str) -> np.ndarray:
         return batch_plans(value, self.B, self.cfg.N, self._default_mean, name)
 
-    def _took_steps(self, records, stats: dict) -> np.ndarray:
+    def _states(self, states) -> np.ndarray:
+        return batch_states(states, self.B)
+
+    def _loop_rows(self, rows) -> np.ndarray:
+        return loop_rows_batch(rows, self.B)
+
+    def _took_step(self, records, stats: dict) -> np.ndarray:
         self.step_count += 1
         self.records = records
         self.last = [StepResult.from_record(r, self.cfg.N) for r in records]
         self.last_stats = stats
         return records[:, 2:5].copy()
 
+    def candidates(self):
+        """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
+        return self._entry("last")()
 
-class BatchedMPPI(_BatchedPlanController):
+
+class BatchedMPPI(_MPPILaw, _BatchedPlanController):
     """``ctl = BatchedMPPI(B=64, N=20, K=4096, lam=1.0); u = ctl.step(states)``: B independent MPPI plans, each with its own
     state, seed (default ``seed + b``) and warm-started nominal, advanced by one library call per control step; lam, std and
     n_iter are shared.  Problem b's results are bit for bit those of ``MPPI(seed=seeds[b], nominal=nominal[b])`` on its own
@@ -372,44 +441,12 @@ class BatchedMPPI(_BatchedPlanController):
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int, lam: float = 1.0,
                  std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, **overrides):
-        self.std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
-        self.params = _lib.MPPIParams.make(n_iter, lam, self.std)        # ValueError before the library is called
-        self.lam, self.n_iter = float(lam), int(n_iter)
+        self._set_params(lam, std, n_iter)
         super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides)
-        self.nominal: Optional[np.ndarray] = None
         self.reset(nominal)
 
-    def reset(self, nominal=None):
-        nu = self._plans(nominal, "nominal")
-        self.engine.mppi_reset_batch(nu)
-        self.nominal = nu.copy()
 
-    def step(self, states) -> np.ndarray:
-        st = batch_states(states, self.B)
-        rec, self.nominal, stats = self.engine.mppi_step_batch(st, self.seeds, self.step_count, self.params)
-        return self._took_steps(rec, {"rho": stats[:, 0].copy(), "eta": stats[:, 1].copy(), "ess": stats[:, 2].copy(),
-                                      "J0": stats[:, 3].copy()})
-
-    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
-        """T control steps of all B problems by one library call (rovmpc_mppi_closed_loop_batch_device): ``rows`` (B, T, 16),
-        a trajectory per problem, or (T, 16) given to every problem.  The result's arrays are (T, B, ...); problem b's are
-        those of ``MPPI(seed=seeds[b], nominal=nominal[b]).run(rows[b])``."""
-        r, fb = loop_rows_batch(rows, self.B), loop_feedback(feedback)
-        e, T = self.engine, r.shape[1]
-        out = _run_on_device(e, r, e.mppi_row_len(), (T, self.B), lambda d_exo, d_rows: e.mppi_closed_loop_batch_device(
-            d_exo, T, fb, self.seeds, self.step_count, self.params, d_rows))
-        res = split_rows(out, e.result_len, self.cfg.N)
-        self.nominal, st = res.plans[-1].copy(), res.stats[-1]
-        self._took_steps(res.records[-1].copy(), {"rho": st[:, 0].copy(), "eta": st[:, 1].copy(), "ess": st[:, 2].copy(), "J0": st[:, 3].copy()})
-        self.step_count += T - 1
-        return res
-
-    def candidates(self):
-        """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
-        return self.engine.mppi_last_batch()
-
-
-class BatchedCEM(_BatchedPlanController):
+class BatchedCEM(_CEMLaw, _BatchedPlanController):
     """``ctl = BatchedCEM(B=64, N=20, K=4096, n_elite=64); u = ctl.step(states)``: B independent CEM plans, each with its own
     state, seed (default ``seed + b``) and warm-started mean, advanced by one library call per control step; the parameters
     of ``CEM`` are shared.  Problem b's results are bit for bit those of ``CEM(seed=seeds[b], mean=mean[b])`` on its own
@@ -419,47 +456,9 @@ class BatchedCEM(_BatchedPlanController):
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int,
                  n_elite: Optional[int] = None, n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0),
                  lo=(-np.inf,) * 3, hi=(np.inf,) * 3, seed: int = 20250523, seeds=None, mean=None, reserved: int = 0, **overrides):
-        K = int(overrides["K"]) if "K" in overrides else (cfg.K if cfg is not None else MPCConfig().K)
-        if n_elite is None:
-            n_elite = max(K // 64, 1)
-        if isinstance(n_elite, bool) or int(n_elite) != n_elite or int(n_elite) > K:
-            raise ValueError(f"n_elite must be an integer <= K = {K} (got {n_elite!r})")
-        std = np.asarray(std if std is not None else default_model().scale[3:6], dtype=np.float64)
-        self.params = _lib.CEMParams.make(n_iter, n_elite, alpha, std, std_min, lo, hi, reserved)   # ValueError before the library is called
-        self.n_iter, self.n_elite, self.alpha = int(n_iter), int(n_elite), float(alpha)
+        self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
         super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides)
-        self.mean: Optional[np.ndarray] = None
-        self.std: Optional[np.ndarray] = None
-        self.elites: Optional[np.ndarray] = None
         self.reset(mean)
-
-    def reset(self, mean=None):
-        mu = self._plans(mean, "mean")
-        self.engine.cem_reset_batch(mu)
-        self.mean = mu.copy()
-
-    def step(self, states) -> np.ndarray:
-        st = batch_states(states, self.B)
-        rec, self.mean, self.std, self.elites, stats = self.engine.cem_step_batch(st, self.seeds, self.step_count, self.params)
-        return self._took_steps(rec, {"J_best": stats[:, 0].copy(), "J_worst_elite": stats[:, 1].copy(),
-                                      "n_finite": stats[:, 2].astype(np.int64), "J0": stats[:, 3].copy()})
-
-    def run(self, rows, feedback: bool = False) -> PlanLoopResult:
-        """T control steps of all B problems by one library call (rovmpc_cem_closed_loop_batch_device); see ``BatchedMPPI.run``."""
-        r, fb = loop_rows_batch(rows, self.B), loop_feedback(feedback)
-        e, T = self.engine, r.shape[1]
-        out = _run_on_device(e, r, e.cem_row_len(self.n_elite), (T, self.B), lambda d_exo, d_rows: e.cem_closed_loop_batch_device(
-            d_exo, T, fb, self.seeds, self.step_count, self.params, d_rows))
-        res = split_rows(out, e.result_len, self.cfg.N, self.n_elite)
-        self.mean, self.std, self.elites, st = res.plans[-1].copy(), res.spreads[-1].copy(), res.elites[-1].copy(), res.stats[-1]
-        self._took_steps(res.records[-1].copy(), {"J_best": st[:, 0].copy(), "J_worst_elite": st[:, 1].copy(),
-                                                  "n_finite": st[:, 2].astype(np.int64), "J0": st[:, 3].copy()})
-        self.step_count += T - 1
-        return res
-
-    def candidates(self):
-        """Host copies of the last iteration's candidates U (B, K, N, 3) and costs J (B, K)."""
-        return self.engine.cem_last_batch()
 
 
 def synthetic_problem(K: int, N: int, seed: int = 20250523, dtype=np.float64):

@@ -397,8 +397,9 @@ int rovmpc_step_device(rovmpc_handle *h, const double *d_state, const void *d_U,
  * of the reference's per-frame loop over independent states (catenary_from_data.py:40-50), and the way to fill the
  * chip when one problem (K = 4096) is only one workgroup per CU.  Problem b's record is bit-identical to
  * rovmpc_step_device on (d_states[b], d_U[b]).  rovmpc_batch_costs_device returns the device pointer of the costs
- * J[B][K] of the last batched launch (reals of cfg.dtype; valid until the next launch on the handle).  The batched MPPI and
- * CEM steps write their costs into buffers of their own (rovmpc_*_last_batch) and do not change what it returns. */
+ * J[B][K] of the last batched launch (reals of cfg.dtype; valid until the next launch on the handle).  The MPPI and CEM
+ * steps and loops, single (rovmpc_*_step, rovmpc_*_closed_loop_device) and batched, write their costs into buffers of their
+ * own (rovmpc_*_last, rovmpc_*_last_batch) and do not change what it returns. */
 int rovmpc_step_batch_device(rovmpc_handle *h, int32_t B, const double *d_states, const void *d_U,
                              double *d_results, void *stream);
 int rovmpc_batch_costs_device(rovmpc_handle *h, const void **d_J);

@@ -44,3 +44,16 @@ def defaults(rv, N):
 def colmax(U, shape):
     K = U.shape[0]
     return np.abs(np.asarray(U, dtype=np.float64)).reshape(K, -1).max(axis=0).reshape(shape)
+
+
+def batch_costs_after_step_batch(engine, state, U):
+    """rovmpc_step_batch_device with B = 2 on the engine, then where rovmpc_batch_costs_device says its costs lie."""
+    import torch
+    dev = torch.device("cuda", engine.cfg.device)
+    st = torch.tensor(np.tile(state, (2, 1)), device=dev)
+    dU = torch.tensor(np.stack([U, U]).astype(engine.cfg.np_dtype), device=dev)
+    res = torch.empty((2, engine.result_len), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    engine.step_batch_device(2, st.data_ptr(), dU.data_ptr(), res.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    return engine.batch_costs_ptr()

@@ -10,7 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_cem_host import cem_clamp, cem_elites, cem_sample_ref, cem_update_ref, shift_mean  # noqa: E402
-from plan_controller_helpers import colmax, defaults, oracle_J, orc, rv  # noqa: E402,F401
+from plan_controller_helpers import batch_costs_after_step_batch, colmax, defaults, oracle_J, orc, rv  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -309,6 +309,9 @@ def test_cem_does_not_disturb_other_steps(rv, force_interp):
     assert np.array_equal(a.sampled_candidates(), b.sampled_candidates())
     for x, y in zip(a.mppi_last(), b.mppi_last()):
         assert np.array_equal(x, y, equal_nan=True)
+    costs = batch_costs_after_step_batch(a, state, Ub)
+    a.cem_step(state, 1, 300, cp)
+    assert a.batch_costs_ptr() == costs           # the controller's rollout wrote its own J, not the batched launch's
     a.close(); b.close()
 
 

@@ -10,7 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_mppi_host import mppi_sample_ref, mppi_update_ref, shift_nominal  # noqa: E402
-from plan_controller_helpers import colmax, defaults, oracle_J, orc, rv  # noqa: E402,F401
+from plan_controller_helpers import batch_costs_after_step_batch, colmax, defaults, oracle_J, orc, rv  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -268,6 +268,9 @@ def test_mppi_does_not_disturb_other_steps(rv, force_interp):
         assert sa_.index == sb_.index and sa_.cost == sb_.cost and np.array_equal(sa_.traj, sb_.traj)
         assert np.array_equal(a.rollout_costs(state, Ub), b.rollout_costs(state, Ub))
     assert np.array_equal(a.sampled_candidates(), b.sampled_candidates())
+    costs = batch_costs_after_step_batch(a, state, Ub)
+    a.mppi_step(state, 1, 200, params)
+    assert a.batch_costs_ptr() == costs           # the controller's rollout wrote its own J, not the batched launch's
     a.close(); b.close()
 
 

@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from plan_controller_helpers import defaults, oracle_J, orc, rv  # noqa: E402,F401
+from plan_golden_cases import plans_for, problems, seeds_for  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -30,28 +31,6 @@ def same(a, b):
 
 def same_stats(a, b):
     return np.array_equal(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), equal_nan=True)
-
-
-def problems(rv, B, K, N, s):
-    """States (B, 16) of control step s: every problem and every step its own."""
-    base, _ = rv.synthetic_problem(K, N)
-    st = np.tile(base, (B, 1))
-    b = np.arange(B, dtype=np.float64)
-    st[:, 12] += 0.01 * s + 0.003 * b
-    st[:, 13] -= 0.005 * s + 0.002 * b
-    st[:, 3:6] *= (1.0 + 0.05 * s + 0.02 * b)[:, None]
-    st[:, 14:16] = st[:, 12:14] - 1e-3 * (1.0 + b)[:, None]
-    return st
-
-
-def plans_for(rv, B, N):
-    mean, std = defaults(rv, N)
-    rng = np.random.default_rng(B * 1000 + N)
-    return mean[None] + 0.05 * std * rng.standard_normal((B, N, 3)), std
-
-
-def seeds_for(B):
-    return [1000003 * (b + 1) + 17 for b in range(B)]
 
 
 def lam_of(rv, cfg_kw, model, std, state, nominal):
