@@ -225,7 +225,8 @@ RV_DEV void raise_error(unsigned *err, unsigned bit) {
 // In-kernel phase stamps exist only in the diagnostic library (make diag, -DROVMPC_STAMPS); the
 // product library contains none of this code.
 #ifdef ROVMPC_STAMPS
-#define RV_NSTAMP 24     // slots per workgroup: 0..15 the phases of every workgroup, 16.. the sweeping workgroup's tail
+#define RV_NSTAMP 48     // slots per workgroup: 0..15 the phases of every workgroup, 16..20 the sweeping workgroup's tail, 21 the theta
+                         // chain's end; per wave w of the workgroup 24+w its phase-4a list done, 32+w its arrival at the join, 40+w its start
 #define RV_STAMP(i) do { if (threadIdx.x == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)] = wall_clock64(); } while (0)
 #define RV_STAMP_W(i) do { if ((threadIdx.x & 63) == 0 && a.stamps) a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * RV_NSTAMP + (i)] = wall_clock64(); } while (0)   // lane 0 of the calling wave
 // slot i <- SIMD of every wave of the workgroup: nibble w = 8 | SIMD_ID of wave w (HW_ID bits 5:4)
@@ -1190,6 +1191,40 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
     // catenary parameter + tension of the straight geometry (main_fun.py:292-293, 303-305),
     // tautness and control terms of the cost.
     // work list of one thread: optionally one own item first, then items begin + first + k stride
+    //
+    // Work list of a pool thread where an early batch is taken (not chasing): pool_slot(p, E, stride) returns `first` and sets
+    // `stride` for pool thread p of P = stride threads (whole waves: NT is a multiple of 64), the early wave being pool
+    // threads [E, E + 64).
+    //  * The early wave has its own items' phase 4b to do before the join and takes no other item through phase 4a (an empty
+    //    list: first = N CK).
+    //  * The other items go to the remaining P - 64 threads, `per` = ceil(items / threads) to a thread at the most, and to no
+    //    more waves than that takes (`takers` threads; the rest get empty lists).
+    //  * Order in which the waves are filled: from the wave behind the early one upwards, then round to the waves in front
+    //    of it (compiled-in model: the gamma wave), and wave 4 of the workgroup last of all.  Wave 4 shares the theta wave's
+    //    SIMD (waves w and w + 4 land on one SIMD): an item takes it 2.4 us instead of 1.3.  On both model paths one wave
+    //    integrates (nint = 64), so wave 4 is pool threads 192..255.
+    //  phase-4a items per thread, N = 20, CK = 16 (320 items, early = 64), compiled-in model (E = 64; wave 1 = gamma wave):
+    //    NT   wave 1  wave 2 (early)  wave 3  wave 4  waves 5..7     first / stride of a taker
+    //    256    2       own            2       -       -             wave 3: tid & 63, wave 1: 64 + (tid & 63) / 128
+    //    320    2       own            2       0       -             the same / 128
+    //    512    0       own            1       0       1, 1, 1       waves 3, 5, 6, 7: 0, 64, 128, 192 + (tid & 63) / 256
+    //  hiprtc path (E = 0), NT = 320: wave 1 own, waves 2 and 3 two each (first 0.., 64.. / 128), wave 4 none.
+    //  P == 64: the early wave is the whole pool and keeps every item.
+    // (The two loops stand for two divisions by run-time values; they run once per pool thread, off the theta wave's path.)
+    auto pool_slot = [&](int p, int E, int &stride) {
+        const int P = stride;
+        if (P <= 64) return p;
+        const int others = P - 64, items = N * CK - early;
+        int per = 1, takers = 64;
+        while (per * others < items) ++per;                    // ceil(items / others)
+        while (takers * per < items) takers += 64;             // ceil(items / per), in whole waves
+        stride = takers;
+        if (p >= E && p < E + 64) return N * CK;
+        int rank = p < E ? p - E + others : p - E - 64;        // place in the filling order, wave 4 not yet moved
+        const int rank4 = 128 - E;                             // wave 4's place (pool threads 192..255)
+        if (P > 192 && rank >= rank4) rank = rank < rank4 + 64 ? others - 64 + (rank - rank4) : rank - 64;
+        return rank < takers ? rank : N * CK;
+    };
     auto geometry_a = [&](int own_item, int first, int stride, int begin) {
         const int total = (a.debug & 2) ? 0 : N * CK;
         bool pending_own = own_item >= 0;
@@ -1387,6 +1422,7 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
         if (tid < nint) {
             __builtin_amdgcn_s_setprio(3);           // the workgroup's critical path
             theta_path();
+            RV_STAMP_W(21);
             __builtin_amdgcn_s_setprio(0);
         }
         // Phase 4a pool = every thread that does not integrate theta (all threads when narrow).
@@ -1397,7 +1433,11 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
         // still running; the join then leaves a multiple of 256.
         const int j = wide ? tid - nint - 64 : -1;
         const bool own = !chase && j >= 0 && j < early && !(a.debug & 2);
-        if (!wide || tid >= nint) geometry_a(own ? j : -1, wide ? tid - nint : tid, wide ? NT - nint : NT, chase ? 0 : early);
+        RV_STAMP_W(40 + (tid >> 6));
+        int pool = wide ? NT - nint : NT, slot = wide ? tid - nint : tid;
+        if (wide && early > 0 && !chase && tid >= nint) slot = pool_slot(slot, 64, pool);
+        if (!wide || tid >= nint) geometry_a(own ? j : -1, slot, pool, chase ? 0 : early);
+        RV_STAMP_W(24 + (tid >> 6));
         // phase 4b before the join: the early batch's item, or -- chasing -- all of this pool thread's items in node order
         int b0 = 0, b1 = 0, bs = 1;
         if (chase) { if (tid >= nint && !(a.debug & 2)) { b0 = tid - nint; b1 = N * CK; bs = NT - nint; } }
@@ -1410,6 +1450,7 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
                    __hip_atomic_load(&s_prog[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < N) __builtin_amdgcn_s_sleep(4);
             geometry_b_item(n, i & ckm);
         }
+        RV_STAMP_W(32 + (tid >> 6));
         if (chase) early = N * CK;                    // nothing is left for the round after the join
     } else {
         // bytecode model: CK lanes of wave 0 integrate; the other waves take phase 4a
@@ -2058,15 +2099,21 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             if (MODEL == MODEL_JIT) { if (fmap == ROVMPC_FEATURES_GEN3) integrate_dd_jit(); else integrate_jit(); }
             else { if (fmap == ROVMPC_FEATURES_GEN3) integrate_dd(); else integrate(); }
             if (tid == 0) __hip_atomic_store(&s_prog[1], N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (also when no step ran)
+            RV_STAMP_W(21);
         }
         const int j = (wide && MODEL == MODEL_JIT) ? tid - nint : -1;
         const bool own = j >= 0 && j < early && !(a.debug & 2);
-        if (!wide || tid >= nint) geometry_a(own ? j : -1, wide ? tid - nint : tid, wide ? NT - nint : NT, wide ? early : 0);
+        RV_STAMP_W(40 + (tid >> 6));
+        int pool = wide ? NT - nint : NT, slot = wide ? tid - nint : tid;
+        if (wide && early > 0 && tid >= nint) slot = pool_slot(slot, 0, pool);
+        if (!wide || tid >= nint) geometry_a(own ? j : -1, slot, pool, wide ? early : 0);
+        RV_STAMP_W(24 + (tid >> 6));
         if (own) {
             const int n = j >> cks;
             while (__hip_atomic_load(&s_prog[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < n + 1) __builtin_amdgcn_s_sleep(8);
             geometry_b_item(n, j & ckm);
         }
+        RV_STAMP_W(32 + (tid >> 6));
     }
     __syncthreads();
 

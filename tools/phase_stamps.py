@@ -56,7 +56,7 @@ t0 = st[:, 0].min()
 names = ["start", "U in LDS", None, "features done", "integration done", "geometry done", "outputs stored", "ticket drawn",
          "gamma wave: chain starts", "gamma wave: chain done", "gamma wave: sines done", None, "phase 2a done (wave 0)", "phase 2a barrier passed", "phase 5: block arg-min done", "phase 5: barrier passed",
          "sweep: all cost granules seen", "sweep: block reduce done", "sweep: winner's trajectory in registers", "sweep: record stored",
-         "sweep: winner's trajectory flag seen", None, None, None]
+         "sweep: winner's trajectory flag seen", "theta chain done (theta wave)", None, None]
 print(f"{nb.value} workgroups; times in us from the first workgroup's start (100 MHz clock)")
 for i, n in enumerate(names):
     if n is None:
@@ -83,6 +83,37 @@ for i, n in enumerate(names):
         continue
     dl = (st[m, i] - st[m, 0]) / 100
     print(f"  {n:32s} {np.median(dl):7.2f} {np.percentile(dl, 10):7.2f} {np.percentile(dl, 90):7.2f}")
+
+# the join behind the integration (slots 24.. of a library that has them): per wave w, 40+w = it reaches the geometry lists,
+# 24+w = its phase-4a list is done, 32+w = its phase 4b before the join is done, i.e. it arrives at the barrier
+waves = [w for w in range(8) if (st[:, 40 + w] > 0).any()] if NSLOT >= 48 else []
+if waves:
+    ok = np.all(st[:, [32 + w for w in waves]] > 0, axis=1) & (st[:, 3] > 0) & (st[:, 4] > 0)
+    s0, feat = st[ok, 0], st[ok, 3]
+    q = lambda v: f"{np.median(v):7.2f} {np.percentile(v, 10):7.2f} {np.percentile(v, 90):7.2f}"
+    print(f"the join, {int(ok.sum())} workgroups, waves {waves}; us after the workgroup's 'features done' (median / p10 / p90):")
+    if (st[ok, 21] > 0).all():
+        print(f"  theta chain done                 {q((st[ok, 21] - feat) / 100)}")
+    arr = np.stack([st[ok, 32 + w] for w in waves], 1)
+    for k, w in enumerate(waves):
+        print(f"  wave {w}: starts {q((st[ok, 40 + w] - feat) / 100)} | 4a list done {q((st[ok, 24 + w] - feat) / 100)} | at the join {q((arr[:, k] - feat) / 100)}")
+    print(f"  join passed ('integration done') {q((st[ok, 4] - feat) / 100)}")
+    last = arr.argmax(1)
+    print("  last wave at the join (share of workgroups): " + "  ".join(f"wave {w}: {100 * np.mean(last == k):.1f} %" for k, w in enumerate(waves)))
+    second = np.sort(arr, 1)[:, -2] if len(waves) > 1 else arr[:, 0]
+    print(f"  the last wave arrives behind the one before it by {q((arr.max(1) - second) / 100)}")
+    print("  duration of a wave's lists, us (median / p10 / p90); an empty list shows what the stamp itself costs:")
+    d4a = {}
+    for w in waves:
+        a4, b4 = (st[ok, 24 + w] - st[ok, 40 + w]) / 100, (st[ok, 32 + w] - st[ok, 24 + w]) / 100
+        d4a[w] = np.median(a4)
+        print(f"    wave {w}: phase-4a list {q(a4)} | phase 4b before the join (with any wait for theta) {q(b4)}")
+    geo = [w for w in waves if d4a[w] > 0.5]
+    if geo:
+        w1 = min(geo, key=lambda w: d4a[w])
+        wb = max(waves, key=lambda w: np.median(st[ok, 32 + w] - st[ok, 24 + w]))
+        print(f"  shortest non-empty phase-4a list: wave {w1}, {d4a[w1]:.2f} us; longest phase 4b before the join: wave {wb}, "
+              f"{np.median(st[ok, 32 + wb] - st[ok, 24 + wb]) / 100:.2f} us")
 
 # residency: which CU ran each workgroup (HW_ID / XCC_ID stamp), how many were alive together
 hw = buf[:nb.value, 2]
