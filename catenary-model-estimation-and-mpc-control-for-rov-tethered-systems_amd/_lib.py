@@ -112,6 +112,33 @@ class CEMParams(C.Structure):
         return p
 
 
+def noise_correlation(beta):
+    """beta of ``rovmpc_set_noise_correlation`` checked before the library sees it: None (white noise), or 3 finite values
+    with 0 <= beta < 1.  Returns None or the list of 3 floats."""
+    if beta is None:
+        return None
+    b = [float(v) for v in beta]
+    if len(b) != 3 or not all(math.isfinite(v) and 0.0 <= v < 1.0 for v in b):
+        raise ValueError(f"beta must be 3 finite values with 0 <= beta < 1 (got {beta!r})")
+    return b
+
+
+def control_box(lo, hi):
+    """lo, hi of ``rovmpc_mppi_set_bounds`` checked before the library sees them: both None (unbounded), or 3 values each, not
+    NaN, lo <= hi (+-inf allowed).  Returns None or (lo, hi) as lists of 3 floats."""
+    if lo is None and hi is None:
+        return None
+    if lo is None or hi is None:
+        raise ValueError(f"lo and hi must both be given or both be None (got {lo!r}, {hi!r})")
+    lo_, hi_ = [float(v) for v in lo], [float(v) for v in hi]
+    for name, t, v in (("lo", lo_, lo), ("hi", hi_, hi)):
+        if len(t) != 3 or any(math.isnan(x) for x in t):
+            raise ValueError(f"{name} must be 3 values, not NaN (got {v!r})")
+    if not all(a <= b for a, b in zip(lo_, hi_)):
+        raise ValueError(f"lo must be <= hi on every channel (got {lo!r}, {hi!r})")
+    return lo_, hi_
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -139,6 +166,8 @@ _SIGNATURES = {
     "rovmpc_cem_reset_batch": (C.c_int, [_P, C.c_int32, _P]),
     "rovmpc_cem_step_batch": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint64, C.POINTER(CEMParams), _P, _P, _P, _P, _P]),
     "rovmpc_cem_last_batch": (C.c_int, [_P, _P, _P]),
+    "rovmpc_set_noise_correlation": (C.c_int, [_P, _P]),
+    "rovmpc_mppi_set_bounds": (C.c_int, [_P, _P, _P]),
     "rovmpc_mppi_row_len": (C.c_int32, [_P]),
     "rovmpc_cem_row_len": (C.c_int32, [_P, C.c_int32]),
     "rovmpc_mppi_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P]),

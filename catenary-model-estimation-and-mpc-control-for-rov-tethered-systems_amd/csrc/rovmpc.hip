@@ -19,6 +19,7 @@
 
 #include "util_kernels.h"
 #include "cem_kernels.h"
+#include "proposal_kernels.h"
 #include "embedded_sources.inc"
 
 using namespace rovmpc;
@@ -126,6 +127,11 @@ struct rovmpc_handle {
     PlanCtl mppi{"MPPI", "mppi", true}, cem{"CEM", "cem", true};
     PlanCtl mppi_b{"MPPI", "mppi", false}, cem_b{"CEM", "cem", false};
     Slab mppi_slab_x, cem_slab_x;                // of rovmpc_*_update_device (allocated at its first call)
+    // shaping of the controllers' proposal (rovmpc_set_noise_correlation, rovmpc_mppi_set_bounds); the defaults launch the
+    // white samplers and the unbounded update
+    double prop_beta[3] = {0.0, 0.0, 0.0}, prop_root[3] = {1.0, 1.0, 1.0};    // root = sqrt((1 - beta)(1 + beta))
+    double mppi_lo[3] = {-INFINITY, -INFINITY, -INFINITY}, mppi_hi[3] = {INFINITY, INFINITY, INFINITY};
+    bool prop_colored = false, mppi_boxed = false;
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -1576,6 +1582,81 @@ template <typename BA, typename A> static BA plan_batch_args(const A &a, const P
         else hipLaunchKernelGGL(kern<float>, grid, dim3(SAMPLER_NT), 0, (h)->stream, sa, (float *)(U));                       \
     } while (0)
 
+// ---- the shaped proposal (proposal_kernels.h): AR(1) noise along the horizon and a box, for MPPI and CEM alike --------
+// A tile is `rows` whole candidates, a multiple of 4: about one Philox block per thread (rows 3N <= 1024 elements), one
+// phase-2 thread per (row, channel) (3 rows <= PROPOSAL_NT), 4 rows where a row alone is longer.  A tile row takes `stride`
+// doubles of LDS, 3N padded up to 3 mod 32 (the bank rule of phase 2): at most 4 x 1027 doubles, 33 KB, per workgroup.
+struct ProposalTile { int rows, stride; };
+static ProposalTile proposal_tile(int N) {
+    const int row3 = 3 * N;
+    int rows = 1024 / row3;
+    if (rows > PROPOSAL_NT / 3) rows = PROPOSAL_NT / 3;
+    rows &= ~3;
+    if (rows < 4) rows = 4;
+    return {rows, row3 + ((3 - row3 % 32) + 32) % 32};
+}
+
+// The draw around `mean` with spread `sigma` (null: std3 on every node) inside [lo3, hi3], for c's problems
+static int launch_proposal_sample(rovmpc_handle *h, const PlanCtl &c, const PlanIter &it, const double *std3, const double *lo3,
+                                  const double *hi3, const double *mean, const double *sigma, const char *what) {
+    const ProposalTile t = proposal_tile(h->cfg.N);
+    ProposalLaw law;
+    memset(&law, 0, sizeof(law));
+    law.counter = it.counter;
+    for (int i = 0; i < 3; ++i) {
+        law.beta[i] = h->prop_beta[i]; law.root[i] = h->prop_root[i]; law.std[i] = std3[i]; law.lo[i] = lo3[i]; law.hi[i] = hi3[i];
+    }
+    law.K = h->cfg.K; law.N = h->cfg.N; law.rows = t.rows; law.stride = t.stride; law.mean = mean; law.sigma = sigma;
+    const int gx = (int)((law.K + t.rows - 1) / t.rows);
+    const size_t lds = (size_t)t.rows * t.stride * sizeof(double);
+    const bool f64 = h->cfg.dtype == ROVMPC_F64;
+    if (c.single) {
+        ProposalSampleArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.law = law;
+        plan_single_in(sa, c, it);
+        if (f64) hipLaunchKernelGGL(proposal_sample_kernel<double>, dim3(gx), dim3(PROPOSAL_NT), lds, h->stream, sa, (double *)c.U);
+        else hipLaunchKernelGGL(proposal_sample_kernel<float>, dim3(gx), dim3(PROPOSAL_NT), lds, h->stream, sa, (float *)c.U);
+        return launched(h, what);
+    }
+    ProposalSampleBatchArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.law = law; sa.in = it.in;
+    if (f64) hipLaunchKernelGGL(proposal_sample_batch_kernel<double>, dim3(gx, c.B), dim3(PROPOSAL_NT), lds, h->stream, sa, (double *)c.U);
+    else hipLaunchKernelGGL(proposal_sample_batch_kernel<float>, dim3(gx, c.B), dim3(PROPOSAL_NT), lds, h->stream, sa, (float *)c.U);
+    return launched(h, what);
+}
+
+extern "C" int rovmpc_set_noise_correlation(rovmpc_handle *h, const double *beta3) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    if (!beta3) beta3 = zero;
+    for (int i = 0; i < 3; ++i)
+        if (!(isfinite(beta3[i]) && beta3[i] >= 0 && beta3[i] < 1))
+            FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_noise_correlation: beta[%d] must be finite and in [0, 1) (got %g)", i, beta3[i]);
+    h->prop_colored = false;
+    for (int i = 0; i < 3; ++i) {
+        h->prop_beta[i] = beta3[i];
+        h->prop_root[i] = sqrt((1.0 - beta3[i]) * (1.0 + beta3[i]));
+        if (beta3[i] != 0) h->prop_colored = true;
+    }
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_mppi_set_bounds(rovmpc_handle *h, const double *lo3, const double *hi3) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!lo3 != !hi3) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_set_bounds: lo and hi must both be given or both be null");
+    for (int i = 0; lo3 && i < 3; ++i)
+        if (!(lo3[i] <= hi3[i])) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_mppi_set_bounds: need lo[%d] <= hi[%d], not NaN (got %g, %g)", i, i, lo3[i], hi3[i]);
+    h->mppi_boxed = false;
+    for (int i = 0; i < 3; ++i) {
+        h->mppi_lo[i] = lo3 ? lo3[i] : -INFINITY;
+        h->mppi_hi[i] = hi3 ? hi3[i] : INFINITY;
+        if (h->mppi_lo[i] != -INFINITY || h->mppi_hi[i] != INFINITY) h->mppi_boxed = true;
+    }
+    return ROVMPC_OK;
+}
+
 // ---- MPPI: sampling around a warm-started nominal, exp(-J/lambda)-weighted update on the GPU -------------------------
 struct MppiGeo { int G; long long slice; };
 static MppiGeo mppi_geometry(long long K) {
@@ -1616,12 +1697,15 @@ static int launch_mppi_update(rovmpc_handle *h, const void *d_J, const void *d_U
     a.nu_in = nu_in; a.nu_out = nu_out; a.shift = pub.shift; a.stats = stats; a.slab = (double *)slab; a.ticket = ticket;
     a.record = pub.record; a.R = rovmpc_result_len(h); a.host_out = pub.host_out; a.done_flag = pub.done_flag; a.done_seq = pub.done_seq;
     a.loop = pub.loop;
+    for (int i = 0; i < 3; ++i) { a.lo[i] = h->mppi_lo[i]; a.hi[i] = h->mppi_hi[i]; }
     if (!batch) {
-        LAUNCH_T_QC(mppi_update_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
+        if (h->mppi_boxed) LAUNCH_T_QC(mppi_update_box_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
+        else LAUNCH_T_QC(mppi_update_kernel, h, a.C3 > MPPI_NT, dim3(g.G), dim3(MPPI_NT), 0, s, a);
         return launched(h, "MPPI update");
     }
     const MppiUpdateBatchArgs ba = plan_batch_args<MppiUpdateBatchArgs>(a, *batch);
-    LAUNCH_T_QC(mppi_update_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, batch->B), dim3(MPPI_NT), 0, s, ba);
+    if (h->mppi_boxed) LAUNCH_T_QC(mppi_update_box_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, batch->B), dim3(MPPI_NT), 0, s, ba);
+    else LAUNCH_T_QC(mppi_update_batch_kernel, h, a.C3 > MPPI_NT, dim3(g.G, batch->B), dim3(MPPI_NT), 0, s, ba);
     return launched(h, "batched MPPI update");
 }
 
@@ -1636,6 +1720,8 @@ template <typename SA> static SA mppi_sample_args(const rovmpc_handle *h, const 
 
 static int launch_mppi_sample(rovmpc_handle *h, const PlanCtl &c, const PlanIter &it, const double *std3) {
     const double *nu = c.plan + it.in_off;
+    if (h->prop_colored || h->mppi_boxed)
+        return launch_proposal_sample(h, c, it, std3, h->mppi_lo, h->mppi_hi, nu, nullptr, c.single ? "MPPI sampler" : "batched MPPI sampler");
     const int gx = sampler_grid((long long)h->cfg.K * h->cfg.N * 3);
     if (c.single) {
         MppiSampleArgs sa = mppi_sample_args<MppiSampleArgs>(h, it, std3, nu);
@@ -1814,6 +1900,8 @@ template <typename SA> static SA cem_sample_args(const rovmpc_handle *h, const P
 
 static int launch_cem_sample(rovmpc_handle *h, const PlanCtl &c, const PlanIter &it, const rovmpc_cem_params *p) {
     const double *mu = c.plan + it.in_off, *sigma = it.first ? nullptr : c.spread + it.in_off;      // sigma_0 = std
+    if (h->prop_colored)
+        return launch_proposal_sample(h, c, it, p->std, p->lo, p->hi, mu, sigma, c.single ? "CEM sampler" : "batched CEM sampler");
     const int gx = sampler_grid((long long)h->cfg.K * h->cfg.N * 3);
     if (c.single) {
         CemSampleArgs sa = cem_sample_args<CemSampleArgs>(h, it, p, mu, sigma);

@@ -200,6 +200,7 @@ struct MppiUpdateArgs {
     // a step of a device loop: the row also goes to loop.row, the state moves on, and only the loop's last step has a
     // mailbox (host_out and done_flag null otherwise)
     PlanHandoff loop;
+    double lo[3], hi[3];                // the box of rovmpc_mppi_set_bounds (read by the bounded instances only)
 };
 
 RV_DEV double wave_min(double v) {
@@ -236,8 +237,9 @@ struct PlanBatchAt {
 };
 
 // The update of one problem by the workgroups blockIdx.x = 0 .. G - 1 (the kernels below: one problem, or blockIdx.y = problem).
-// QC = columns per thread: 1 when 3 N <= MPPI_NT, else 4
-template <typename T, int QC>
+// QC = columns per thread: 1 when 3 N <= MPPI_NT, else 4.  BOX: every nu the update leaves goes through the box [a.lo, a.hi]
+// (fmin(fmax(.)) as cem_clamp), the row it keeps when no cost is finite included; the unbounded instances carry no selects.
+template <typename T, int QC, bool BOX = false>
 RV_DEV void mppi_update_body(const MppiUpdateArgs &a, const PlanBatchAt &at) {
     __shared__ double sS[MPPI_MAX_COLS];                // row-lane partials [R][3N]
     __shared__ double sNu[MPPI_MAX_COLS];               // nu* (combine)
@@ -260,6 +262,7 @@ RV_DEV void mppi_update_body(const MppiUpdateArgs &a, const PlanBatchAt &at) {
     const bool active = r < R;
     const long long k0 = (long long)blockIdx.x * a.slice, k1 = k0 + a.slice < a.K ? k0 + a.slice : a.K;
     const double inf = __builtin_inf();
+    auto box = [&](double v, int c) { return BOX ? ::fmin(::fmax(v, a.lo[c % 3]), a.hi[c % 3]) : v; };
 
     // (1) the workgroup's finite minimum
     double m = inf;
@@ -358,7 +361,7 @@ RV_DEV void mppi_update_body(const MppiUpdateArgs &a, const PlanBatchAt &at) {
     double st0, st1, st2;
     if (!(rho < inf)) {
         // no finite cost: the nominal stays as it is, bit for bit
-        for (int c = tid; c < C3; c += MPPI_NT) sNu[c] = nu_in()[c];
+        for (int c = tid; c < C3; c += MPPI_NT) sNu[c] = box(nu_in()[c], c);
         st0 = __builtin_nan(""); st1 = 0.0; st2 = 0.0;
     } else {
         const double sc = (tid < G && rb < inf) ? ::exp(-(rb - rho) / a.lambda) : 0.0;
@@ -398,12 +401,12 @@ RV_DEV void mppi_update_body(const MppiUpdateArgs &a, const PlanBatchAt &at) {
             if (tid < C3) {
                 double s = sS[tid];
                 for (int q = 1; q < R; ++q) s += sS[q * C3 + tid];
-                sNu[tid] = s / eta_all;
+                sNu[tid] = box(s / eta_all, tid);
             }
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (c0 + q * MPPI_NT < C3) sNu[c0 + q * MPPI_NT] = acc[q] / eta_all;
+                if (c0 + q * MPPI_NT < C3) sNu[c0 + q * MPPI_NT] = box(acc[q] / eta_all, c0 + q * MPPI_NT);
         }
         st0 = rho; st1 = eta_all; st2 = eta_all * eta_all / w2_all;
     }
@@ -436,6 +439,13 @@ mppi_update_kernel(const MppiUpdateArgs a) {
     mppi_update_body<T, QC>(a, PlanBatchAt{});
 }
 
+// the bounded instance (rovmpc_mppi_set_bounds with a finite bound)
+template <typename T, int QC>
+__global__ void __launch_bounds__(MPPI_NT)
+mppi_update_box_kernel(const MppiUpdateArgs a) {
+    mppi_update_body<T, QC, true>(a, PlanBatchAt{});
+}
+
 // Batched form: grid (G, B).  Problem b = blockIdx.y has its own J, U, nominal halves, slab rows, ticket, record and mailbox
 // row, each at the first problem's pointer + b * its stride (PlanBatchAt); within a problem everything is mppi_update_body.
 struct MppiUpdateBatchArgs {
@@ -449,6 +459,12 @@ template <typename T, int QC>
 __global__ void __launch_bounds__(MPPI_NT)
 mppi_update_batch_kernel(const MppiUpdateBatchArgs ba) {
     mppi_update_body<T, QC>(ba.a, PlanBatchAt{blockIdx.y, ba.slab_stride, ba.host_stride, ba.step_ticket, ba.B});
+}
+
+template <typename T, int QC>
+__global__ void __launch_bounds__(MPPI_NT)
+mppi_update_box_batch_kernel(const MppiUpdateBatchArgs ba) {
+    mppi_update_body<T, QC, true>(ba.a, PlanBatchAt{blockIdx.y, ba.slab_stride, ba.host_stride, ba.step_ticket, ba.B});
 }
 
 // model.predict(X) on n already-scaled rows: one lane per row, operand stack in LDS.

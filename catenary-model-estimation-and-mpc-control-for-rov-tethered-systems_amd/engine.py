@@ -252,6 +252,27 @@ class Engine:
         self._check(fn(self._h, _ptr(U), _ptr(J)))
         return U, J
 
+    @staticmethod
+    def _triple(v, name: str):
+        """None, or (3,) float64 as it is (the library checks the values)."""
+        if v is None:
+            return None
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        if a.shape != (3,):
+            raise ValueError(f"{name} must have shape (3,), got {a.shape}")
+        return a
+
+    def set_noise_correlation(self, beta=None):
+        """AR(1) coefficient per control channel of the MPPI / CEM sampling noise along the horizon (rovmpc_set_noise_correlation):
+        3 finite values in [0, 1); None or zeros: white noise, the default.  Holds from the next control step, for every
+        MPPI and CEM entry of this engine."""
+        self._check(self.lib.rovmpc_set_noise_correlation(self._h, _ptr(self._triple(beta, "beta"))))
+
+    def mppi_set_bounds(self, lo=None, hi=None):
+        """Box on the MPPI controls (rovmpc_mppi_set_bounds): candidates, nominal and the returned control are clamped to
+        [lo, hi] per channel (+-inf allowed); both None: unbounded, the default.  Holds from the next control step."""
+        self._check(self.lib.rovmpc_mppi_set_bounds(self._h, _ptr(self._triple(lo, "lo")), _ptr(self._triple(hi, "hi"))))
+
     def mppi_reset(self, nominal):
         """Set the handle's MPPI nominal plan (N, 3); allocates the MPPI buffers on first use."""
         self._plan_reset(self.lib.rovmpc_mppi_reset, nominal, "nominal")

@@ -186,10 +186,15 @@ class _PlanController:
 
     _batch = ""         # "_batch": the engine's batched entries
 
-    def __init__(self, cfg, model, seed: int, overrides: dict):
+    def __init__(self, cfg, model, seed: int, overrides: dict, beta=None, lo=None, hi=None):
         self.seed = int(seed)
+        self.beta, self.box = _lib.noise_correlation(beta), _lib.control_box(lo, hi)      # ValueError before the library is called
         self.engine = Engine(cfg, model, **overrides)
         self.cfg = self.engine.cfg
+        if self.beta is not None:
+            self.engine.set_noise_correlation(self.beta)
+        if self.box is not None:
+            self.engine.mppi_set_bounds(*self.box)
         self._default_mean = np.asarray(default_model().mean[3:6], dtype=np.float64)
         self.step_count = 0
         self.last = self.last_stats = None       # StepResult (batched: a list of them), dict
@@ -324,12 +329,15 @@ class MPPI(_MPPILaw, _PlanController):
     host round trip) and returns its first control.  The law is stated in include/rovmpc.h (rovmpc_mppi_step).
     Defaults: nominal = the scaler mean of x3..x5 on every node, std = its scale.  After ``step``: ``last`` (the record of
     the last rollout, with u = nominal*[0]), ``last_stats`` (rho, eta, ess, J0), ``nominal`` (the plan the step returned).
+    ``beta`` (3 values in [0, 1), default None: white noise) makes the sampling noise AR(1) along the horizon, unit variance
+    and corr(n, m) = beta^|n - m| per channel: smoother candidates.  ``lo``, ``hi`` (default None: unbounded) box the controls:
+    candidates, nominal and the returned control lie inside exactly (rovmpc_set_noise_correlation, rovmpc_mppi_set_bounds).
     """
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, lam: float = 1.0, std=None,
-                 n_iter: int = 1, seed: int = 20250523, nominal=None, **overrides):
+                 n_iter: int = 1, seed: int = 20250523, nominal=None, beta=None, lo=None, hi=None, **overrides):
         self._set_params(lam, std, n_iter)
-        super().__init__(cfg, model, seed, overrides)
+        super().__init__(cfg, model, seed, overrides, beta, lo, hi)
         self.reset(nominal)
 
 
@@ -343,14 +351,14 @@ class CEM(_CEMLaw, _PlanController):
     Defaults: mean = the scaler mean of x3..x5 on every node, std = its scale, std_min = 0, bounds +-inf, alpha = 0,
     n_elite = K / 64 (at least 1).  After ``step``: ``last`` (the record of the last rollout, with u = clamp(mean*[0])),
     ``last_stats`` (J_best, J_worst_elite, n_finite, J0), ``mean`` and ``std`` (the plan and spread the step returned) and
-    ``elites`` (the last iteration's elite indices in rank order, -1 padded).
+    ``elites`` (the last iteration's elite indices in rank order, -1 padded).  ``beta`` as for ``MPPI``: AR(1) sampling noise.
     """
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, n_elite: Optional[int] = None,
                  n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0), lo=(-np.inf,) * 3, hi=(np.inf,) * 3,
-                 seed: int = 20250523, mean=None, reserved: int = 0, **overrides):
+                 seed: int = 20250523, mean=None, reserved: int = 0, beta=None, **overrides):
         self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
-        super().__init__(cfg, model, seed, overrides)
+        super().__init__(cfg, model, seed, overrides, beta)
         self.reset(mean)
 
 
@@ -402,9 +410,9 @@ class _BatchedPlanController(_PlanController):
 
     _batch = "_batch"
 
-    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict):
+    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict, beta=None, lo=None, hi=None):
         self.B, self.seeds = check_batch(B, seed, seeds, plan, _config_value(cfg, overrides, "N"), name)
-        super().__init__(cfg, model, int(self.seeds[0]), overrides)
+        super().__init__(cfg, model, int(self.seeds[0]), overrides, beta, lo, hi)
         self.records: Optional[np.ndarray] = None
 
     def _seeds(self):
@@ -437,12 +445,13 @@ class BatchedMPPI(_MPPILaw, _BatchedPlanController):
     n_iter are shared.  Problem b's results are bit for bit those of ``MPPI(seed=seeds[b], nominal=nominal[b])`` on its own
     (include/rovmpc.h, rovmpc_mppi_step_batch).  ``nominal``: (B, N, 3), or (N, 3) / (3,) repeated; default the scaler mean.
     ``step(states)`` takes (B, 16) or a sequence of B states and returns u (B, 3).  After it: ``records`` (B, result_len),
-    ``last`` (a list of StepResult), ``nominal`` (B, N, 3), ``last_stats`` (rho, eta, ess, J0: arrays of length B)."""
+    ``last`` (a list of StepResult), ``nominal`` (B, N, 3), ``last_stats`` (rho, eta, ess, J0: arrays of length B).
+    ``beta``, ``lo``, ``hi`` as for ``MPPI``, shared by the batch."""
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int, lam: float = 1.0,
-                 std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, **overrides):
+                 std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, beta=None, lo=None, hi=None, **overrides):
         self._set_params(lam, std, n_iter)
-        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides)
+        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides, beta, lo, hi)
         self.reset(nominal)
 
 
@@ -451,13 +460,15 @@ class BatchedCEM(_CEMLaw, _BatchedPlanController):
     state, seed (default ``seed + b``) and warm-started mean, advanced by one library call per control step; the parameters
     of ``CEM`` are shared.  Problem b's results are bit for bit those of ``CEM(seed=seeds[b], mean=mean[b])`` on its own
     (include/rovmpc.h, rovmpc_cem_step_batch).  After ``step``: ``records``, ``last`` (a list of StepResult), ``mean`` and
-    ``std`` (B, N, 3), ``elites`` (B, n_elite), ``last_stats`` (J_best, J_worst_elite, n_finite, J0: arrays of length B)."""
+    ``std`` (B, N, 3), ``elites`` (B, n_elite), ``last_stats`` (J_best, J_worst_elite, n_finite, J0: arrays of length B).
+    ``beta`` as for ``MPPI``, shared by the batch."""
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int,
                  n_elite: Optional[int] = None, n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0),
-                 lo=(-np.inf,) * 3, hi=(np.inf,) * 3, seed: int = 20250523, seeds=None, mean=None, reserved: int = 0, **overrides):
+                 lo=(-np.inf,) * 3, hi=(np.inf,) * 3, seed: int = 20250523, seeds=None, mean=None, reserved: int = 0, beta=None,
+                 **overrides):
         self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
-        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides)
+        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides, beta)
         self.reset(mean)
 
 

@@ -218,8 +218,10 @@ int rovmpc_sample_candidates_device(rovmpc_handle *h, uint64_t seed, uint64_t st
  * rovmpc_step / rovmpc_mpc_step_sampled on the same handle give the same bits with or without MPPI steps in between.
  * Errors: ROVMPC_ERR_INVALID for bad parameters, a struct_size mismatch or a step before the first reset;
  * ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
+ * Control bounds and time-correlated noise: rovmpc_mppi_set_bounds and rovmpc_set_noise_correlation below (the shaped
+ * proposal); the law above is their default.
  * Not provided: sharded MPPI (it needs an all-reduce of the 3 N + 3 partials), sampling folded into the fused sampled
- * rollout kernel, control bounds. */
+ * rollout kernel. */
 typedef struct rovmpc_mppi_params {
     int32_t struct_size;        /* = sizeof(rovmpc_mppi_params), ABI check                  */
     int32_t n_iter;             /* iterations per control step, 1..64                       */
@@ -292,6 +294,37 @@ int rovmpc_cem_last(rovmpc_handle *h, void *U_out, void *J_out);
 int rovmpc_cem_update_device(rovmpc_handle *h, const void *d_J, const void *d_U, const rovmpc_cem_params *p,
                              const double *d_mean_in, const double *d_std_in, double *d_mean_out, double *d_std_out,
                              int64_t *d_elite_out, double *d_stats, void *stream);
+
+/* ---- the shaped proposal of MPPI and CEM: time-correlated sampling noise, and a box on the MPPI controls ---------------
+ * Two settings of the handle, read by every MPPI and CEM entry (step, batched step, device loop, batched device loop):
+ * Noise.  Let z_e be the white stream of the laws above (keyed by (seed, counter), e = (k N + n) 3 + ch), beta[ch] the AR(1)
+ * coefficient and root[ch] = sqrt((1 - beta[ch]) (1 + beta[ch])), computed once on the host in double.  For every candidate
+ * k >= 1 and channel ch, in double whatever T is:
+ *      eps[k][0][ch] = z[k][0][ch],
+ *      eps[k][n][ch] = fma(beta[ch], eps[k][n-1][ch], root[ch] * z[k][n][ch])          n = 1 .. N - 1.
+ * eps is stationary with unit variance and corr(eps_n, eps_m) = beta^|n - m|; with beta[ch] = 0 it is z.
+ * Sampling (step 2 of the laws above), clamp(v) = fmin(fmax(v, lo[ch]), hi[ch]) in double:
+ *      MPPI: U[0] = (T) clamp(nu_i), U[k][n][ch] = (T) clamp(fma(std[ch], eps[k][n][ch], nu_i[n][ch])), the box that of
+ *            rovmpc_mppi_set_bounds (infinite bounds make clamp the identity, bit for bit);
+ *      CEM:  U[k][n][ch] = (T) clamp(fma(sigma_i[n][ch], eps[k][n][ch], mu_i[n][ch])) with the box of its parameters: only z
+ *            becomes eps.
+ * Counters, element order, candidate 0 and the warm-start shift are those of the laws above.
+ * MPPI update under a box (step 4): every nu_{i+1} goes through clamp, the nu_i kept bit for bit when no cost is finite
+ * included.  So nu*, the kept shifted nominal, u = nu*[0] of the record and of a loop's row lie inside the box exactly, not
+ * to rounding; rovmpc_mppi_update_device applies the same box.
+ * Default: beta all zero and no MPPI box.  Then the white samplers and the unbounded update run, and every output of every
+ * entry is bit for bit what it was before the settings existed; a step takes 3 n_iter launches either way.
+ * The equivalence laws hold with shaping on: problem b of a batch is bit for bit its own single controller with the same
+ * settings, and row i of a device loop is bit for bit the host-stepped step.
+ * Scope: the shooting step (rovmpc_mpc_step_sampled, rovmpc_sample_candidates_device) draws white, unbounded noise whatever
+ * these settings are, and gives the same bits with or without them.
+ * Both setters take effect from the next control step, launch nothing, and may be called before or after a reset and again
+ * between steps.  ROVMPC_ERR_INVALID for a null handle or a value outside the ranges below; the previous setting then stays.
+ * Not provided: a per-problem beta or box in a batch, a correlated proposal for the shooting step. */
+/* beta[3]: AR(1) coefficient per control channel, finite, 0 <= beta < 1; NULL or all zero: white noise (the default). */
+int rovmpc_set_noise_correlation(rovmpc_handle *h, const double *beta3);
+/* lo[3], hi[3]: not NaN, lo <= hi, +-inf allowed; both NULL: unbounded (the default); one NULL and the other not: invalid. */
+int rovmpc_mppi_set_bounds(rovmpc_handle *h, const double *lo3, const double *hi3);
 
 /* ---- batched MPPI and CEM: B independent plans, each with its own state, seed and warm-started plan, advanced one control
  * step by one call with one host wait (a fleet of ROVs, an ensemble of state hypotheses, several seeds) --------------------
