@@ -139,6 +139,66 @@ def control_box(lo, hi):
     return lo_, hi_
 
 
+NAV_MAX_SPHERES = 8
+NAV_MAX_ROWS = 1 << 24
+
+
+class NavCost(C.Structure):
+    """Mirror of ``rovmpc_nav_cost``.  ``nav_cost`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("n_spheres", C.c_int32), ("w_pos", C.c_double * 3), ("w_term", C.c_double * 3),
+                ("w_du", C.c_double * 3), ("w_sphere", C.c_double), ("spheres", (C.c_double * 4) * NAV_MAX_SPHERES),
+                ("origin", C.c_uint64)]
+
+
+def nav_cost(tracks, w_pos=0.0, w_term=0.0, w_du=0.0, w_sphere=0.0, spheres=(), origin=0):
+    """The arguments of ``rovmpc_set_nav_cost`` checked before the library sees them: weights finite and >= 0 (a scalar is
+    repeated on the three channels), at most 8 spheres (cx, cy, cz, R) finite with R >= 0, tracks (Tr, 3) or (Bt, Tr, 3)
+    finite with Bt, Tr >= 1 and Bt * Tr <= 2^24, origin an integer (taken mod 2^64).  Returns (NavCost, tracks (Bt, Tr, 3)
+    float64 C-contiguous)."""
+    import numpy as np
+
+    def weight3(name, v):
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape == ():
+            a = np.repeat(a, 3)
+        if a.shape != (3,) or not all(math.isfinite(x) and x >= 0 for x in a):
+            raise ValueError(f"{name} must be a scalar or 3 values, finite and >= 0 (got {v!r})")
+        return [float(x) for x in a]
+    wp, wt, wd = weight3("w_pos", w_pos), weight3("w_term", w_term), weight3("w_du", w_du)
+    ws = float(w_sphere)
+    if not (math.isfinite(ws) and ws >= 0):
+        raise ValueError(f"w_sphere must be finite and >= 0 (got {w_sphere!r})")
+    sp = np.asarray(spheres, dtype=np.float64)
+    if sp.size == 0:
+        sp = np.empty((0, 4))
+    if sp.shape == (4,):
+        sp = sp[None]
+    if sp.ndim != 2 or sp.shape[1] != 4:
+        raise ValueError(f"spheres must have shape (n, 4): cx, cy, cz, R (got {sp.shape})")
+    if len(sp) > NAV_MAX_SPHERES:
+        raise ValueError(f"at most {NAV_MAX_SPHERES} spheres (got {len(sp)})")
+    if not (np.isfinite(sp).all() and (sp[:, 3] >= 0).all()):
+        raise ValueError(f"spheres must be finite with R >= 0 (got {spheres!r})")
+    if isinstance(origin, bool) or int(origin) != origin:
+        raise ValueError(f"origin must be an integer (got {origin!r})")
+    tr = np.asarray(tracks, dtype=np.float64)
+    if tr.ndim == 2:
+        tr = tr[None]
+    if tr.ndim != 3 or tr.shape[2] != 3 or tr.shape[0] < 1 or tr.shape[1] < 1:
+        raise ValueError(f"track must have shape (Tr, 3) or (Bt, Tr, 3) with Bt, Tr >= 1 (got {np.shape(tracks)})")
+    if tr.shape[0] * tr.shape[1] > NAV_MAX_ROWS:
+        raise ValueError(f"track has {tr.shape[0] * tr.shape[1]} rows; at most {NAV_MAX_ROWS}")
+    if not np.isfinite(tr).all():
+        raise ValueError("track must be finite")
+    n = NavCost()
+    n.struct_size, n.n_spheres = C.sizeof(NavCost), len(sp)
+    n.w_pos, n.w_term, n.w_du, n.w_sphere = (C.c_double * 3)(*wp), (C.c_double * 3)(*wt), (C.c_double * 3)(*wd), ws
+    for j, row in enumerate(sp):
+        n.spheres[j] = (C.c_double * 4)(*[float(x) for x in row])
+    n.origin = int(origin) & 0xFFFFFFFFFFFFFFFF
+    return n, np.ascontiguousarray(tr)
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -168,6 +228,8 @@ _SIGNATURES = {
     "rovmpc_cem_last_batch": (C.c_int, [_P, _P, _P]),
     "rovmpc_set_noise_correlation": (C.c_int, [_P, _P]),
     "rovmpc_mppi_set_bounds": (C.c_int, [_P, _P, _P]),
+    "rovmpc_set_nav_cost": (C.c_int, [_P, C.POINTER(NavCost), _P, C.c_int32, C.c_int64]),
+    "rovmpc_nav_cost_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, _P]),
     "rovmpc_mppi_row_len": (C.c_int32, [_P]),
     "rovmpc_cem_row_len": (C.c_int32, [_P, C.c_int32]),
     "rovmpc_mppi_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P]),

@@ -20,6 +20,7 @@
 #include "util_kernels.h"
 #include "cem_kernels.h"
 #include "proposal_kernels.h"
+#include "nav_kernels.h"
 #include "embedded_sources.inc"
 
 using namespace rovmpc;
@@ -132,6 +133,13 @@ struct rovmpc_handle {
     double prop_beta[3] = {0.0, 0.0, 0.0}, prop_root[3] = {1.0, 1.0, 1.0};    // root = sqrt((1 - beta)(1 + beta))
     double mppi_lo[3] = {-INFINITY, -INFINITY, -INFINITY}, mppi_hi[3] = {INFINITY, INFINITY, INFINITY};
     bool prop_colored = false, mppi_boxed = false;
+    // navigation cost of the controllers (rovmpc_set_nav_cost): the setting, its tracks [nav_Bt][nav_Tr][3] and spheres
+    // [ROVMPC_NAV_MAX_SPHERES][4] in device memory; unset: nav_cost_kernel is not launched
+    bool nav_on = false;
+    rovmpc_nav_cost nav = {};
+    double *d_nav_track = nullptr, *d_nav_spheres = nullptr;
+    size_t nav_track_cap = 0;                    // doubles allocated behind d_nav_track
+    int nav_Bt = 0; long long nav_Tr = 0;
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -523,7 +531,8 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     void *ptrs[] = {h->d_U, h->d_J, h->d_traj_all, h->d_state, h->d_blk_traj,
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
-                    h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u};
+                    h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
+                    h->d_nav_track, h->d_nav_spheres};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     mailbox_free(h->samp_box);
@@ -1486,6 +1495,80 @@ static int plan_batch_ready(rovmpc_handle *h, PlanCtl &c, const char *fn, int B,
     return ROVMPC_OK;
 }
 
+struct ProposalTile { int rows, stride; };
+
+// ---- the navigation cost (nav_kernels.h): C_k of the vehicle's predicted path added to J between rollout and update ----
+// One launch for B problems on the tile of the shaped sampler; track_stride: doubles between the problems' tracks.
+static ProposalTile proposal_tile(int N);
+
+static int launch_nav_cost(rovmpc_handle *h, const double *d_state, const void *d_U, void *d_J, double *d_C, uint64_t step, int B,
+                           size_t track_stride, hipStream_t s) {
+    const ProposalTile t = proposal_tile(h->cfg.N);
+    NavArgs a;
+    memset(&a, 0, sizeof(a));
+    a.state = d_state; a.track = h->d_nav_track; a.spheres = h->d_nav_spheres; a.C = d_C;
+    a.c = h->cfg.v_scale * h->cfg.dt;
+    for (int i = 0; i < 3; ++i) { a.w_pos[i] = h->nav.w_pos[i]; a.w_term[i] = h->nav.w_term[i]; a.w_du[i] = h->nav.w_du[i]; }
+    a.w_sphere = h->nav.w_sphere;
+    a.K = h->cfg.K; a.Tr = h->nav_Tr; a.r0 = (long long)(step - h->nav.origin); a.track_stride = track_stride;
+    a.N = h->cfg.N; a.rows = t.rows; a.stride = t.stride; a.n_spheres = h->nav.n_spheres;
+    const dim3 grid((unsigned)((a.K + t.rows - 1) / t.rows), (unsigned)B);
+    const size_t lds = (size_t)t.rows * (t.stride + 3) * sizeof(double);
+    if (h->cfg.dtype == ROVMPC_F64) hipLaunchKernelGGL(nav_cost_kernel<double>, grid, dim3(NAV_NT), lds, s, a, (const double *)d_U, (double *)d_J);
+    else hipLaunchKernelGGL(nav_cost_kernel<float>, grid, dim3(NAV_NT), lds, s, a, (const float *)d_U, (float *)d_J);
+    return launched(h, "navigation cost");
+}
+
+extern "C" int rovmpc_set_nav_cost(rovmpc_handle *h, const rovmpc_nav_cost *nav, const double *tracks, int32_t Bt, int64_t Tr) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_single_gpu(h, "rovmpc_set_nav_cost");
+    if (rc) return rc;
+    if (!nav) { h->nav_on = false; return ROVMPC_OK; }
+    if (nav->struct_size != (int32_t)sizeof(rovmpc_nav_cost))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_nav_cost.struct_size %d != %d (ABI mismatch)", nav->struct_size, (int)sizeof(rovmpc_nav_cost));
+    if (nav->n_spheres < 0 || nav->n_spheres > ROVMPC_NAV_MAX_SPHERES)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_nav_cost: n_spheres must be in 0..%d (got %d)", ROVMPC_NAV_MAX_SPHERES, nav->n_spheres);
+    if ((rc = check_std3(h, "w_pos", nav->w_pos)) || (rc = check_std3(h, "w_term", nav->w_term)) || (rc = check_std3(h, "w_du", nav->w_du))) return rc;
+    if (!(isfinite(nav->w_sphere) && nav->w_sphere >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "w_sphere must be finite and >= 0 (got %g)", nav->w_sphere);
+    for (int j = 0; j < nav->n_spheres; ++j) {
+        const double *sp = nav->spheres[j];
+        if (!(isfinite(sp[0]) && isfinite(sp[1]) && isfinite(sp[2]) && isfinite(sp[3]) && sp[3] >= 0))
+            FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_nav_cost: sphere %d must be finite with R >= 0 (got %g, %g, %g, %g)", j, sp[0], sp[1], sp[2], sp[3]);
+    }
+    if (!tracks) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_nav_cost: null tracks");
+    if (Bt < 1 || Tr < 1 || Tr > (1 << 24) || (long long)Bt * Tr > (1 << 24))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_nav_cost: need Bt >= 1, Tr >= 1 and Bt * Tr <= %d (got %d, %lld)", 1 << 24, Bt, (long long)Tr);
+    const size_t n = (size_t)Bt * (size_t)Tr * 3;
+    for (size_t i = 0; i < n; ++i)
+        if (!isfinite(tracks[i])) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_nav_cost: tracks[%zu][%zu][%zu] is not finite", i / (3 * (size_t)Tr), i / 3 % (size_t)Tr, i % 3);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));             // no step of the handle is reading the buffers about to change
+    if (!h->d_nav_spheres) HIPCHK(h, hipMalloc((void **)&h->d_nav_spheres, sizeof(nav->spheres)));
+    if (n > h->nav_track_cap) {
+        double *fresh = nullptr;
+        HIPCHK(h, hipMalloc((void **)&fresh, n * sizeof(double)));
+        dev_free(h->d_nav_track);
+        h->d_nav_track = fresh; h->nav_track_cap = n;
+        h->nav_on = false;                                  // until the copies below have succeeded
+    }
+    hipError_t e = hipMemcpy(h->d_nav_track, tracks, n * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->d_nav_spheres, nav->spheres, sizeof(nav->spheres), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { h->nav_on = false; FAIL(h, ROVMPC_ERR_HIP, "rovmpc_set_nav_cost: copying the tracks: %s", hipGetErrorString(e)); }
+    h->nav = *nav; h->nav_Bt = Bt; h->nav_Tr = Tr; h->nav_on = true;
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_nav_cost_device(rovmpc_handle *h, const double *d_state, const void *d_U, uint64_t step, double *d_C, void *d_J,
+                                      void *stream) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_single_gpu(h, "rovmpc_nav_cost_device");
+    if (rc) return rc;
+    if (!h->nav_on) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_nav_cost_device: no navigation cost is set (rovmpc_set_nav_cost)");
+    if (!d_state || !d_U) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_nav_cost_device: null pointer (d_state or d_U)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return launch_nav_cost(h, d_state, d_U, d_J, d_C, step, 1, 0, (hipStream_t)stream);
+}
+
 // What the loop hands the two launches of iteration i.  The last group is set in the last iteration of a step only (the
 // update then also shifts the plan by one node, passes the rollout's record on and, where the step has a mailbox, fills
 // it); *_update_device passes PlanIter{}.
@@ -1515,6 +1598,9 @@ static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, c
                      uint64_t step, int n_iter, Sample sample, Update update) {
     int rc;
     if ((rc = check_ready(h))) return rc;
+    if (h->nav_on && !c.single && h->nav_Bt != 1 && h->nav_Bt != c.B)
+        FAIL(h, ROVMPC_ERR_INVALID, "batched %s: B = %d but the navigation cost has %d tracks (rovmpc_set_nav_cost: one per problem, or one for all)",
+             c.name, c.B, h->nav_Bt);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
     const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N, exo_stride = (size_t)loop.T * ROVMPC_STATE_LEN;
@@ -1550,6 +1636,8 @@ static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, c
             h->arg_J = nullptr;
             h->last_batch = last_batch;
             if (rc) return rc;
+            if (h->nav_on && (rc = launch_nav_cost(h, c.state, c.U, c.J, nullptr, step + (uint64_t)t, c.B,
+                                                   !c.single && h->nav_Bt == c.B ? 3 * (size_t)h->nav_Tr : 0, h->stream))) return rc;
             if ((rc = update(it))) return rc;
             cur ^= 1;
         }
@@ -1586,7 +1674,6 @@ template <typename BA, typename A> static BA plan_batch_args(const A &a, const P
 // A tile is `rows` whole candidates, a multiple of 4: about one Philox block per thread (rows 3N <= 1024 elements), one
 // phase-2 thread per (row, channel) (3 rows <= PROPOSAL_NT), 4 rows where a row alone is longer.  A tile row takes `stride`
 // doubles of LDS, 3N padded up to 3 mod 32 (the bank rule of phase 2): at most 4 x 1027 doubles, 33 KB, per workgroup.
-struct ProposalTile { int rows, stride; };
 static ProposalTile proposal_tile(int N) {
     const int row3 = 3 * N;
     int rows = 1024 / row3;

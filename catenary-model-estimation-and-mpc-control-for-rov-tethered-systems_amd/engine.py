@@ -273,6 +273,42 @@ class Engine:
         [lo, hi] per channel (+-inf allowed); both None: unbounded, the default.  Holds from the next control step."""
         self._check(self.lib.rovmpc_mppi_set_bounds(self._h, _ptr(self._triple(lo, "lo")), _ptr(self._triple(hi, "hi"))))
 
+    def set_nav_cost(self, nav=None, tracks=None):
+        """The navigation cost of every MPPI and CEM entry of this engine (rovmpc_set_nav_cost): ``nav`` a ``_lib.NavCost`` and
+        ``tracks`` (Bt, Tr, 3) float64, both as ``_lib.nav_cost(...)`` returns them; ``nav`` None: clear.  Holds from the next
+        control step."""
+        if nav is None:
+            self._check(self.lib.rovmpc_set_nav_cost(self._h, None, None, 0, 0))
+            return
+        if not isinstance(nav, _lib.NavCost):
+            raise TypeError("nav must be a _lib.NavCost (_lib.nav_cost(...))")
+        tr = np.ascontiguousarray(tracks, dtype=np.float64)
+        if tr.ndim != 3 or tr.shape[2] != 3:
+            raise ValueError(f"tracks must have shape (Bt, Tr, 3), got {tr.shape}")
+        self._check(self.lib.rovmpc_set_nav_cost(self._h, C.byref(nav), _ptr(tr), tr.shape[0], tr.shape[1]))
+
+    def nav_cost(self, state, U, step: int, J=None):
+        """C (K,) float64 of the navigation cost alone for candidates U (K, N, 3) at control step ``step`` on track 0, through
+        the device entry (rovmpc_nav_cost_device).  With ``J`` (K,), also J' of the law: returns (C, J')."""
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        d_state = torch.tensor(state_array(state), device=dev)
+        d_U = torch.tensor(self._U(U), device=dev)
+        d_C = torch.empty(self.cfg.K, dtype=torch.float64, device=dev)
+        d_J = None
+        if J is not None:
+            Jh = np.ascontiguousarray(J, dtype=self.cfg.np_dtype)
+            if Jh.shape != (self.cfg.K,):
+                raise ValueError(f"J must have shape ({self.cfg.K},), got {Jh.shape}")
+            d_J = torch.tensor(Jh, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_nav_cost_device(self._h, d_state.data_ptr(), d_U.data_ptr(), int(step) & 0xFFFFFFFFFFFFFFFF,
+                                                    d_C.data_ptr(), d_J.data_ptr() if d_J is not None else None,
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.synchronize(dev)
+        C_out = d_C.cpu().numpy()
+        return C_out if d_J is None else (C_out, d_J.cpu().numpy())
+
     def mppi_reset(self, nominal):
         """Set the handle's MPPI nominal plan (N, 3); allocates the MPPI buffers on first use."""
         self._plan_reset(self.lib.rovmpc_mppi_reset, nominal, "nominal")

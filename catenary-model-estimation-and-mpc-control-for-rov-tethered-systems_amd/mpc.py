@@ -180,24 +180,66 @@ def _config_value(cfg, overrides: dict, name: str) -> int:
     return int(overrides[name]) if name in overrides else getattr(cfg if cfg is not None else MPCConfig(), name)
 
 
+class NavCost:
+    """``NavCost(track, w_pos=..., w_term=..., w_du=..., w_sphere=..., spheres=..., origin=0)``: the navigation cost of the
+    plan controllers (include/rovmpc.h, rovmpc_set_nav_cost).  ``track`` (Tr, 3), or (B, Tr, 3) for a batched controller: row
+    j is where the vehicle's P1 should be, in metres, at control step ``origin + j`` (the controller's ``step_count``); before
+    the origin the first row holds, past the end the last one, and a single row is a waypoint.  Each candidate's predicted
+    path P_{n+1} = P_n + v_scale dt U_n adds to its cost: ``w_pos`` times the squared distance to the track on every node,
+    ``w_term`` on the last node, ``w_du`` times the squared control increments along the horizon and ``w_sphere`` times the
+    squared penetration into each of up to 8 ``spheres`` (cx, cy, cz, R).  A scalar weight is repeated on the three channels.
+    The values are checked here (ValueError), before any library call."""
+
+    def __init__(self, track, w_pos=0.0, w_term=0.0, w_du=0.0, w_sphere=0.0, spheres=(), origin=0):
+        self.c_nav, self.tracks = _lib.nav_cost(track, w_pos, w_term, w_du, w_sphere, spheres, origin)
+        self.w_pos, self.w_term, self.w_du = (np.array(v) for v in (self.c_nav.w_pos, self.c_nav.w_term, self.c_nav.w_du))
+        self.w_sphere, self.origin = float(self.c_nav.w_sphere), int(self.c_nav.origin)
+        self.spheres = np.array(self.c_nav.spheres).reshape(-1, 4)[:self.c_nav.n_spheres].copy()
+
+
+def check_nav(nav, B: int, batched: bool):
+    """nav of a controller with B problems, before the library is called: None or a NavCost with 1 or (batched) B tracks."""
+    if nav is None:
+        return None
+    if not isinstance(nav, NavCost):
+        raise TypeError("nav must be a rovmpc.NavCost or None")
+    Bt = nav.tracks.shape[0]
+    if Bt != 1 and not (batched and Bt == B):
+        raise ValueError(f"the track must be (Tr, 3){f' or ({B}, Tr, 3)' if batched else ''}, got {nav.tracks.shape}")
+    return nav
+
+
 class _PlanController:
     """What the four controllers share: an engine of their own, the seed and step counter of the draws, the plan's shape
     and the result of the last step.  The single-problem form; _BatchedPlanController overrides what a batch changes."""
 
     _batch = ""         # "_batch": the engine's batched entries
 
-    def __init__(self, cfg, model, seed: int, overrides: dict, beta=None, lo=None, hi=None):
+    def __init__(self, cfg, model, seed: int, overrides: dict, beta=None, lo=None, hi=None, nav=None):
         self.seed = int(seed)
         self.beta, self.box = _lib.noise_correlation(beta), _lib.control_box(lo, hi)      # ValueError before the library is called
+        self.nav = check_nav(nav, getattr(self, "B", 1), bool(self._batch))
         self.engine = Engine(cfg, model, **overrides)
         self.cfg = self.engine.cfg
         if self.beta is not None:
             self.engine.set_noise_correlation(self.beta)
         if self.box is not None:
             self.engine.mppi_set_bounds(*self.box)
+        if self.nav is not None:
+            self.engine.set_nav_cost(self.nav.c_nav, self.nav.tracks)
         self._default_mean = np.asarray(default_model().mean[3:6], dtype=np.float64)
         self.step_count = 0
         self.last = self.last_stats = None       # StepResult (batched: a list of them), dict
+
+    def set_nav(self, nav):
+        """Set (a ``NavCost``) or clear (None) the navigation cost; it holds from the next ``step`` or ``run``, whose
+        ``step_count`` is the control step the track is read at."""
+        nav = check_nav(nav, getattr(self, "B", 1), bool(self._batch))
+        if nav is None:
+            self.engine.set_nav_cost(None)
+        else:
+            self.engine.set_nav_cost(nav.c_nav, nav.tracks)
+        self.nav = nav
 
     def _entry(self, name: str):
         """engine.mppi_step, engine.cem_reset_batch, ..."""
@@ -332,12 +374,14 @@ class MPPI(_MPPILaw, _PlanController):
     ``beta`` (3 values in [0, 1), default None: white noise) makes the sampling noise AR(1) along the horizon, unit variance
     and corr(n, m) = beta^|n - m| per channel: smoother candidates.  ``lo``, ``hi`` (default None: unbounded) box the controls:
     candidates, nominal and the returned control lie inside exactly (rovmpc_set_noise_correlation, rovmpc_mppi_set_bounds).
+    ``nav`` (a ``NavCost``, default None) adds path-tracking, rate and keep-out costs of the vehicle's predicted path; the
+    track is read at ``step_count``, which ``step`` advances by 1 and ``run`` by T (``set_nav`` changes or clears it).
     """
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, lam: float = 1.0, std=None,
-                 n_iter: int = 1, seed: int = 20250523, nominal=None, beta=None, lo=None, hi=None, **overrides):
+                 n_iter: int = 1, seed: int = 20250523, nominal=None, beta=None, lo=None, hi=None, nav=None, **overrides):
         self._set_params(lam, std, n_iter)
-        super().__init__(cfg, model, seed, overrides, beta, lo, hi)
+        super().__init__(cfg, model, seed, overrides, beta, lo, hi, nav)
         self.reset(nominal)
 
 
@@ -351,14 +395,15 @@ class CEM(_CEMLaw, _PlanController):
     Defaults: mean = the scaler mean of x3..x5 on every node, std = its scale, std_min = 0, bounds +-inf, alpha = 0,
     n_elite = K / 64 (at least 1).  After ``step``: ``last`` (the record of the last rollout, with u = clamp(mean*[0])),
     ``last_stats`` (J_best, J_worst_elite, n_finite, J0), ``mean`` and ``std`` (the plan and spread the step returned) and
-    ``elites`` (the last iteration's elite indices in rank order, -1 padded).  ``beta`` as for ``MPPI``: AR(1) sampling noise.
+    ``elites`` (the last iteration's elite indices in rank order, -1 padded).  ``beta`` as for ``MPPI``: AR(1) sampling noise;
+    ``nav`` as for ``MPPI``: the navigation cost.
     """
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, n_elite: Optional[int] = None,
                  n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0), lo=(-np.inf,) * 3, hi=(np.inf,) * 3,
-                 seed: int = 20250523, mean=None, reserved: int = 0, beta=None, **overrides):
+                 seed: int = 20250523, mean=None, reserved: int = 0, beta=None, nav=None, **overrides):
         self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
-        super().__init__(cfg, model, seed, overrides, beta)
+        super().__init__(cfg, model, seed, overrides, beta, nav=nav)
         self.reset(mean)
 
 
@@ -410,9 +455,9 @@ class _BatchedPlanController(_PlanController):
 
     _batch = "_batch"
 
-    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict, beta=None, lo=None, hi=None):
+    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict, beta=None, lo=None, hi=None, nav=None):
         self.B, self.seeds = check_batch(B, seed, seeds, plan, _config_value(cfg, overrides, "N"), name)
-        super().__init__(cfg, model, int(self.seeds[0]), overrides, beta, lo, hi)
+        super().__init__(cfg, model, int(self.seeds[0]), overrides, beta, lo, hi, nav)
         self.records: Optional[np.ndarray] = None
 
     def _seeds(self):
@@ -446,12 +491,13 @@ class BatchedMPPI(_MPPILaw, _BatchedPlanController):
     (include/rovmpc.h, rovmpc_mppi_step_batch).  ``nominal``: (B, N, 3), or (N, 3) / (3,) repeated; default the scaler mean.
     ``step(states)`` takes (B, 16) or a sequence of B states and returns u (B, 3).  After it: ``records`` (B, result_len),
     ``last`` (a list of StepResult), ``nominal`` (B, N, 3), ``last_stats`` (rho, eta, ess, J0: arrays of length B).
-    ``beta``, ``lo``, ``hi`` as for ``MPPI``, shared by the batch."""
+    ``beta``, ``lo``, ``hi`` as for ``MPPI``, shared by the batch; ``nav`` too, its track (Tr, 3) shared or (B, Tr, 3) per problem."""
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int, lam: float = 1.0,
-                 std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, beta=None, lo=None, hi=None, **overrides):
+                 std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, beta=None, lo=None, hi=None, nav=None,
+                 **overrides):
         self._set_params(lam, std, n_iter)
-        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides, beta, lo, hi)
+        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides, beta, lo, hi, nav)
         self.reset(nominal)
 
 
@@ -461,14 +507,14 @@ class BatchedCEM(_CEMLaw, _BatchedPlanController):
     of ``CEM`` are shared.  Problem b's results are bit for bit those of ``CEM(seed=seeds[b], mean=mean[b])`` on its own
     (include/rovmpc.h, rovmpc_cem_step_batch).  After ``step``: ``records``, ``last`` (a list of StepResult), ``mean`` and
     ``std`` (B, N, 3), ``elites`` (B, n_elite), ``last_stats`` (J_best, J_worst_elite, n_finite, J0: arrays of length B).
-    ``beta`` as for ``MPPI``, shared by the batch."""
+    ``beta`` and ``nav`` as for ``BatchedMPPI``."""
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int,
                  n_elite: Optional[int] = None, n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0),
                  lo=(-np.inf,) * 3, hi=(np.inf,) * 3, seed: int = 20250523, seeds=None, mean=None, reserved: int = 0, beta=None,
-                 **overrides):
+                 nav=None, **overrides):
         self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
-        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides, beta)
+        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides, beta, nav=nav)
         self.reset(mean)
 
 

@@ -382,7 +382,9 @@ int rovmpc_cem_last_batch(rovmpc_handle *h, void *U_out, void *J_out);
  *   of step i - 1.
  * record[7], record[8] are the first predicted node of the cheapest candidate of step i - 1's LAST rollout.  That is the
  * existing loop's rule; it is not a model step under the control the step returns (u = nu*[0] or clamp(mu*[0])), which with
- * n_iter >= 2 is never rolled out.  A one-node plant rollout under the applied control is not provided.
+ * n_iter >= 2 is never rolled out.  A one-node plant rollout under the applied control is not provided.  With a navigation
+ * cost (rovmpc_set_nav_cost below) the record is still the rollout's own fused arg-min -- the cheapest candidate by the
+ * rollout cost J alone, not by J' = J + C -- so with feedback == 1 a loop keeps feeding back that candidate's first node.
  * After the call the handle is in the state T calls of rovmpc_<ctl>_step would have left it in: the same kept shifted plan,
  * the CEM spread restarting from std, rovmpc_*_last / _last_batch returning the last iteration's U and J, the mailbox
  * holding the last step's row; a following rovmpc_<ctl>_step gives the same bits either way.
@@ -411,6 +413,67 @@ int rovmpc_mppi_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const doub
                                          const uint64_t *seeds, uint64_t step0, const rovmpc_mppi_params *p, double *d_rows);
 int rovmpc_cem_closed_loop_batch_device(rovmpc_handle *h, int32_t B, const double *d_exo, int64_t T, int32_t feedback,
                                         const uint64_t *seeds, uint64_t step0, const rovmpc_cem_params *p, double *d_rows);
+
+/* ---- the navigation cost of MPPI and CEM: path tracking, control rate and keep-out spheres on the control plan ------------
+ * The rollout's cost holds the tether angles, effort, tension, tautness and the floor; it has no term that says where the
+ * vehicle should be.  In this project's plant rule the position obeys P_{n+1} = P_n + (v_scale dt) U_n, so the vehicle's
+ * predicted path depends on (P1, U[k]) alone, and one launch between the rollout and the update adds its cost to J[K].
+ * Settings of the handle, read by every MPPI and CEM entry (step, batched step, device loop, batched device loop): a
+ * navigation cost `nav` (the weights, spheres and `origin` of rovmpc_nav_cost) and a track ref[Bt][Tr][3] in metres, kept in
+ * device memory by the handle.  Row j of the track is where the vehicle's P1 should be when control step origin + j
+ * measures its state.
+ * Law.  Everything in double, whatever cfg.dtype T is.  Control step with counter `step` (the argument of every entry;
+ * step0 + i in a loop), state x, candidate k:
+ *      c = cfg.v_scale * cfg.dt, formed once on the host in double;
+ *      P_0 = x.P1,  P_{n+1}[ch] = fma(c, (double) U[k][n][ch], P_n[ch])                        n = 0 .. N - 1;
+ *      r(n) = clamp((int64)(step - origin) + n, 0, Tr - 1)  for n = 1 .. N: the subtraction in uint64 (it wraps), then read
+ *             as signed; the sum saturates, it does not wrap.  Before the origin the first row holds; past the end the
+ *             last row holds (the vehicle hovers at the final waypoint);
+ *      e_n = P_n - ref[b'][r(n)],  b' = b if Bt == B, b' = 0 if Bt == 1;
+ *      C_k = position  sum_{n=1..N} sum_ch w_pos[ch] e_n[ch]^2
+ *          + terminal  sum_ch w_term[ch] e_N[ch]^2
+ *          + rate      sum_{n=1..N-1} sum_ch w_du[ch] ((double) U[k][n][ch] - (double) U[k][n-1][ch])^2      (absent at N = 1)
+ *          + spheres   w_sphere sum_{n=1..N} sum_{j < n_spheres} max(0, R_j - |P_n - c_j|)^2;
+ *      J'_k = (T) ((double) J_k + C_k) where J_k is finite; a non-finite J_k is left bit for bit.  A non-finite C_k (overflow)
+ *      makes J'_k non-finite, and the update then ignores the candidate as the laws above say.
+ * The order of the additions inside C_k is the implementation's, but the bits of C_k are a function of (x.P1, U[k], step,
+ * nav, the track rows) alone: not of K, B, the problem's index, the candidate's place in a workgroup's tile, nor of the
+ * entry the step came through.  No float atomics.  So both equivalence laws hold with a navigation cost: problem b of a
+ * batch is bit for bit its own single controller (with track b, or the shared one), and row i of a device loop is bit for
+ * bit the host-stepped step.
+ * Step 4 of the MPPI and CEM laws then reads J': rho, w, ESS, the elites and J_0 of the stats include C, and rovmpc_*_last
+ * returns J'.  The record keeps [J*, k*, u, traj] of the rollout's own fused arg-min: the cheapest candidate by the
+ * rollout cost alone (see the closed-loop section above for what that means under feedback == 1).
+ * Launches: with a navigation cost a control step takes 4 n_iter launches; without one (the default, and after clearing)
+ * 3 n_iter, and every output of every entry is bit for bit what it was before the setting existed.
+ * Single controllers use track 0.  A batched entry whose B is neither Bt nor paired with Bt == 1 fails with
+ * ROVMPC_ERR_INVALID before anything is launched.
+ * rovmpc_set_nav_cost takes effect from the next control step and may be called before or after a reset and again between
+ * steps.  It copies the track into a device buffer of the handle (synchronising the handle's stream first); on
+ * ROVMPC_ERR_INVALID (a null handle, a struct_size mismatch, a value outside the ranges below) the previous setting stays.
+ * ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.
+ * Scope: the shooting step (rovmpc_step, rovmpc_mpc_step_sampled) does not read the setting and gives the same bits with
+ * or without it.
+ * Not provided: a rate term against the previously applied control (the rate term starts at U[k][1] - U[k][0]); a
+ * per-problem nav (the weights and spheres are shared by a batch, the tracks are per problem); a time-varying theta_ref /
+ * gamma_ref (those live in the rollout kernel); the shooting step; anything after rovmpc_comm_init. */
+#define ROVMPC_NAV_MAX_SPHERES 8
+typedef struct rovmpc_nav_cost {
+    int32_t struct_size;             /* = sizeof(rovmpc_nav_cost), ABI check                             */
+    int32_t n_spheres;               /* 0..ROVMPC_NAV_MAX_SPHERES                                        */
+    double  w_pos[3], w_term[3], w_du[3];   /* finite, >= 0                                              */
+    double  w_sphere;                /* finite, >= 0                                                     */
+    double  spheres[ROVMPC_NAV_MAX_SPHERES][4];   /* cx, cy, cz, R: finite, R >= 0; rows >= n_spheres ignored */
+    uint64_t origin;                 /* control step that row 0 of the track belongs to                  */
+} rovmpc_nav_cost;
+/* nav NULL: clear (tracks ignored).  tracks[Bt][Tr][3] host doubles, all finite; Bt >= 1, Tr >= 1, Bt*Tr <= 1<<24. */
+int rovmpc_set_nav_cost(rovmpc_handle *h, const rovmpc_nav_cost *nav, const double *tracks, int32_t Bt, int64_t Tr);
+/* The term alone on caller device buffers, asynchronously on `stream`: d_state[16], d_U[K][N][3] (reals of cfg.dtype),
+ * track 0; d_C[K] double or NULL receives C_k; d_J[K] (reals of cfg.dtype) or NULL is updated in place by the law.
+ * ROVMPC_ERR_INVALID without a navigation cost or for a null d_state or d_U.  A call must have finished before the next
+ * rovmpc_set_nav_cost. */
+int rovmpc_nav_cost_device(rovmpc_handle *h, const double *d_state, const void *d_U, uint64_t step,
+                           double *d_C, void *d_J, void *stream);
 
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
