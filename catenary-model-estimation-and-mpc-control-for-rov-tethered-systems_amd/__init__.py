@@ -21,7 +21,7 @@ from .features import extract_features, extract_features_arrays, features_dd, fe
 from .lagrangian import euler_lagrange, el_residuals, lagrangian_rollout, differentiate, EulerLagrange
 from .trajgen import generate_rov_trajectories, trajectory_csv
 from ._lib import MPPIParams, CEMParams
-from .mpc import MPC, MPPI, CEM, BatchedMPPI, BatchedCEM, NavCost, PlanLoopResult, GaussianSampler, DeviceGaussianSampler, synthetic_problem
+from .mpc import MPC, MPPI, CEM, BatchedMPPI, BatchedCEM, NavCost, TetherCost, PlanLoopResult, GaussianSampler, DeviceGaussianSampler, synthetic_problem
 from .closed_loop import run_plan_closed_loop
 
 __version__ = "0.1.0"

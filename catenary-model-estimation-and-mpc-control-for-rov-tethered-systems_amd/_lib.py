@@ -199,6 +199,40 @@ def nav_cost(tracks, w_pos=0.0, w_term=0.0, w_du=0.0, w_sphere=0.0, spheres=(), 
     return n, np.ascontiguousarray(tr)
 
 
+TETHER_MAX_SPHERES = 8
+
+
+class TetherCost(C.Structure):
+    """Mirror of ``rovmpc_tether_cost``.  ``tether_cost`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("n_spheres", C.c_int32), ("w", C.c_double), ("margin", C.c_double),
+                ("spheres", (C.c_double * 4) * TETHER_MAX_SPHERES)]
+
+
+def tether_cost(spheres, w, margin=0.0):
+    """The arguments of ``rovmpc_set_tether_cost`` checked before the library sees them: 1 to 8 spheres (cx, cy, cz, R) finite
+    with R >= 0, w and margin finite and >= 0.  Returns a TetherCost."""
+    import numpy as np
+    for name, v in (("w", w), ("margin", margin)):
+        if isinstance(v, (str, bytes)) or not np.isscalar(v):
+            raise TypeError(f"{name} must be a number (got {v!r})")
+        if not (math.isfinite(float(v)) and float(v) >= 0):
+            raise ValueError(f"{name} must be finite and >= 0 (got {v!r})")
+    sp = np.asarray(spheres, dtype=np.float64)
+    if sp.shape == (4,):
+        sp = sp[None]
+    if sp.ndim != 2 or sp.shape[1] != 4:
+        raise ValueError(f"spheres must have shape (n, 4): cx, cy, cz, R (got {sp.shape})")
+    if not 1 <= len(sp) <= TETHER_MAX_SPHERES:
+        raise ValueError(f"1 to {TETHER_MAX_SPHERES} spheres (got {len(sp)})")
+    if not (np.isfinite(sp).all() and (sp[:, 3] >= 0).all()):
+        raise ValueError(f"spheres must be finite with R >= 0 (got {spheres!r})")
+    t = TetherCost()
+    t.struct_size, t.n_spheres, t.w, t.margin = C.sizeof(TetherCost), len(sp), float(w), float(margin)
+    for j, row in enumerate(sp):
+        t.spheres[j] = (C.c_double * 4)(*[float(x) for x in row])
+    return t
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -230,6 +264,8 @@ _SIGNATURES = {
     "rovmpc_mppi_set_bounds": (C.c_int, [_P, _P, _P]),
     "rovmpc_set_nav_cost": (C.c_int, [_P, C.POINTER(NavCost), _P, C.c_int32, C.c_int64]),
     "rovmpc_nav_cost_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, _P]),
+    "rovmpc_set_tether_cost": (C.c_int, [_P, C.POINTER(TetherCost)]),
+    "rovmpc_tether_cost_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "rovmpc_mppi_row_len": (C.c_int32, [_P]),
     "rovmpc_cem_row_len": (C.c_int32, [_P, C.c_int32]),
     "rovmpc_mppi_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P]),

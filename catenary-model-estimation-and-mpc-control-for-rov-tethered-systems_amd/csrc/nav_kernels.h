@@ -42,6 +42,29 @@ RV_DEV long long nav_track_row(long long r0, int n, long long Tr) {
     return r < 0 ? 0 : (r < Tr ? r : Tr - 1);
 }
 
+// Phase 1 of a tile, shared with the tether kernel (tether_kernels.h): the tile's `nel` controls, rows of `row3` elements, in
+// element order (coalesced) into LDS rows of stride S as doubles; (r, col) of element l advance with l by NT per pass.
+template <typename T, int NT>
+RV_DEV void nav_load_tile(const T *__restrict__ Ub, double *sE, int nel, int row3, int S, int tid) {
+    const int dr = NT / row3, dc = NT - dr * row3;
+    int r = tid / row3, col = tid - r * row3;
+    for (int l0 = tid; l0 < nel; l0 += 4 * NT) {
+        double u[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) u[i] = l0 + i * NT < nel ? (double)Ub[l0 + i * NT] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (l0 + i * NT < nel) sE[r * S + col] = u[i];
+            r += dr; col += dc;
+            if (col >= row3) { col -= row3; ++r; }
+        }
+    }
+}
+
+// One node of the vehicle's path, P_{n+1} = fma(c, U_n, P_n): the one statement of it, for both kernels whose laws promise
+// the same path bit for bit.
+RV_DEV double nav_path_step(double c, double u, double P) { return ::fma(c, u, P); }
+
 template <typename T>
 __global__ void __launch_bounds__(NAV_NT)
 nav_cost_kernel(const NavArgs a, const T *__restrict__ U, T *__restrict__ J) {
@@ -55,22 +78,8 @@ nav_cost_kernel(const NavArgs a, const T *__restrict__ U, T *__restrict__ J) {
     const int nel = rows * row3;                                            // <= 4096
     const T *Ub = U + (b * (size_t)a.K + (size_t)k0) * row3;
 
-    // (1) the tile's controls in element order; (r, col) of element l advance with l by NAV_NT per pass
-    {
-        const int dr = NAV_NT / row3, dc = NAV_NT - dr * row3;
-        int r = tid / row3, col = tid - r * row3;
-        for (int l0 = tid; l0 < nel; l0 += 4 * NAV_NT) {
-            double u[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) u[i] = l0 + i * NAV_NT < nel ? (double)Ub[l0 + i * NAV_NT] : 0.0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (l0 + i * NAV_NT < nel) sE[r * S + col] = u[i];
-                r += dr; col += dc;
-                if (col >= row3) { col -= row3; ++r; }
-            }
-        }
-    }
+    // (1) the tile's controls in element order
+    nav_load_tile<T, NAV_NT>(Ub, sE, nel, row3, S, tid);
     __syncthreads();
 
     // (2) one (row, channel) per thread along n: slot n of the row ends up holding P_{n+1}
@@ -92,7 +101,7 @@ nav_cost_kernel(const NavArgs a, const T *__restrict__ U, T *__restrict__ J) {
 #pragma unroll
             for (int i = 0; i < NAV_CHUNK; ++i) {
                 if (n0 + i >= N) break;
-                P = ::fma(a.c, u[i], P);
+                P = nav_path_step(a.c, u[i], P);
                 e = P - rf[i];
                 s_pos = ::fma(wp, e * e, s_pos);
                 if (n0 + i > 0) { const double d = u[i] - up; s_du = ::fma(wd, d * d, s_du); }

@@ -21,6 +21,7 @@
 #include "cem_kernels.h"
 #include "proposal_kernels.h"
 #include "nav_kernels.h"
+#include "tether_kernels.h"
 #include "embedded_sources.inc"
 
 using namespace rovmpc;
@@ -140,6 +141,14 @@ struct rovmpc_handle {
     double *d_nav_track = nullptr, *d_nav_spheres = nullptr;
     size_t nav_track_cap = 0;                    // doubles allocated behind d_nav_track
     int nav_Bt = 0; long long nav_Tr = 0;
+    // tether keep-out cost of the controllers (rovmpc_set_tether_cost): the setting, its spheres in device memory and the
+    // buffer [tether_cap][K][N+1][2] the rollout stores its trajectories in; unset: tether_cost_kernel is not launched and
+    // the rollout gets no trajectory buffer
+    bool tether_on = false;
+    rovmpc_tether_cost tether = {};
+    double *d_tether_spheres = nullptr;
+    void *d_tether_traj = nullptr;
+    int tether_cap = 0;                          // problems d_tether_traj holds
     // batched launches: workspace for `batch_cap` problems
     int batch_cap = 0, last_batch = 1;
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
@@ -532,7 +541,7 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     void *ptrs[] = {h->d_U, h->d_J, h->d_traj_all, h->d_state, h->d_blk_traj,
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
                     h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
-                    h->d_nav_track, h->d_nav_spheres};
+                    h->d_nav_track, h->d_nav_spheres, h->d_tether_spheres, h->d_tether_traj};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     mailbox_free(h->samp_box);
@@ -1569,6 +1578,97 @@ extern "C" int rovmpc_nav_cost_device(rovmpc_handle *h, const double *d_state, c
     return launch_nav_cost(h, d_state, d_U, d_J, d_C, step, 1, 0, (hipStream_t)stream);
 }
 
+// ---- the tether keep-out cost (tether_kernels.h): C_k of the cable's predicted shapes added to J after the navigation cost ----
+// The tile: TETHER_ROWS candidates with the LDS row stride of the shaped sampler, and as many nodes per chunk as fit into
+// 64 KB beside it (0: not even one).
+static int tether_chunk(const rovmpc_config &c, size_t *lds_out) {
+    const ProposalTile t = proposal_tile(c.N);
+    const size_t tile = (size_t)TETHER_ROWS * t.stride * sizeof(double);
+    const size_t node = (size_t)TETHER_ROWS * (TETHER_PAR + 3 * (size_t)c.n_shape_pts) * sizeof(double);
+    if (tile + node > 64 * 1024) return 0;
+    size_t nc = (64 * 1024 - tile) / node;
+    if (nc > (size_t)c.N) nc = (size_t)c.N;
+    if (lds_out) *lds_out = tile + nc * node;
+    return (int)nc;
+}
+
+static int launch_tether_cost(rovmpc_handle *h, const double *d_state, const void *d_U, const void *d_traj, void *d_J, double *d_C,
+                              double *d_D, int B, hipStream_t s) {
+    const rovmpc_config &c = h->cfg;
+    const bool f64 = c.dtype == ROVMPC_F64;
+    size_t lds = 0;
+    TetherArgs a;
+    memset(&a, 0, sizeof(a));
+    a.state = d_state; a.spheres = h->d_tether_spheres; a.C = d_C; a.D = d_D;
+    a.c = c.v_scale * c.dt;
+    a.w = h->tether.w; a.margin = h->tether.margin;
+    a.L = f64 ? c.L : (double)(float)c.L; a.c_lo = f64 ? c.c_lo : (double)(float)c.c_lo; a.c_hi = f64 ? c.c_hi : (double)(float)c.c_hi;
+    a.up = c.frame == ROVMPC_ENU ? 1.0 : -1.0;
+    a.K = c.K; a.N = c.N; a.M = c.n_shape_pts; a.rows = TETHER_ROWS; a.stride = proposal_tile(c.N).stride;
+    a.nc = tether_chunk(c, &lds); a.n_spheres = h->tether.n_spheres;
+    const dim3 grid((unsigned)((a.K + a.rows - 1) / a.rows), (unsigned)B);
+    if (f64) hipLaunchKernelGGL(tether_cost_kernel<double>, grid, dim3(TETHER_NT), lds, s, a, (const double *)d_U, (const double *)d_traj, (double *)d_J);
+    else hipLaunchKernelGGL(tether_cost_kernel<float>, grid, dim3(TETHER_NT), lds, s, a, (const float *)d_U, (const float *)d_traj, (float *)d_J);
+    return launched(h, "tether cost");
+}
+
+// the trajectory buffer for B problems; a larger one is made before the old one is let go
+static int ensure_tether_traj(rovmpc_handle *h, int B) {
+    if (B <= h->tether_cap) return ROVMPC_OK;
+    void *fresh = nullptr;
+    hipError_t e = hipMalloc(&fresh, (size_t)B * h->cfg.K * (h->cfg.N + 1) * 2 * h->esz);
+    if (e == hipSuccess) e = hipDeviceSynchronize();        // nothing may still be using the old buffer
+    if (e != hipSuccess) {
+        if (fresh) (void)hipFree(fresh);
+        (void)hipGetLastError();
+        FAIL(h, ROVMPC_ERR_HIP, "tether cost: trajectory buffer for %d problems: %s", B, hipGetErrorString(e));
+    }
+    dev_free(h->d_tether_traj);
+    h->d_tether_traj = fresh; h->tether_cap = B;
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_set_tether_cost(rovmpc_handle *h, const rovmpc_tether_cost *tc) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_single_gpu(h, "rovmpc_set_tether_cost");
+    if (rc) return rc;
+    if (!tc) { h->tether_on = false; return ROVMPC_OK; }
+    if (tc->struct_size != (int32_t)sizeof(rovmpc_tether_cost))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_tether_cost.struct_size %d != %d (ABI mismatch)", tc->struct_size, (int)sizeof(rovmpc_tether_cost));
+    if (tc->n_spheres < 1 || tc->n_spheres > ROVMPC_TETHER_MAX_SPHERES)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_tether_cost: n_spheres must be in 1..%d (got %d)", ROVMPC_TETHER_MAX_SPHERES, tc->n_spheres);
+    if (!(isfinite(tc->w) && tc->w >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_tether_cost: w must be finite and >= 0 (got %g)", tc->w);
+    if (!(isfinite(tc->margin) && tc->margin >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_tether_cost: margin must be finite and >= 0 (got %g)", tc->margin);
+    for (int j = 0; j < tc->n_spheres; ++j) {
+        const double *sp = tc->spheres[j];
+        if (!(isfinite(sp[0]) && isfinite(sp[1]) && isfinite(sp[2]) && isfinite(sp[3]) && sp[3] >= 0))
+            FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_tether_cost: sphere %d must be finite with R >= 0 (got %g, %g, %g, %g)", j, sp[0], sp[1], sp[2], sp[3]);
+    }
+    if (tether_chunk(h->cfg, nullptr) < 1)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_set_tether_cost: N = %d with n_shape_pts = %d does not leave room for one node in 64 KB of LDS", h->cfg.N, h->cfg.n_shape_pts);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));             // no step of the handle is reading the spheres about to change
+    int B = 1;
+    for (const PlanCtl *c : {&h->mppi_b, &h->cem_b}) if (c->B > B) B = c->B;
+    if ((rc = ensure_tether_traj(h, B))) return rc;
+    if (!h->d_tether_spheres) HIPCHK(h, hipMalloc((void **)&h->d_tether_spheres, sizeof(tc->spheres)));
+    hipError_t e = hipMemcpy(h->d_tether_spheres, tc->spheres, sizeof(tc->spheres), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { h->tether_on = false; FAIL(h, ROVMPC_ERR_HIP, "rovmpc_set_tether_cost: copying the spheres: %s", hipGetErrorString(e)); }
+    h->tether = *tc; h->tether_on = true;
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_tether_cost_device(rovmpc_handle *h, const double *d_state, const void *d_U, const void *d_traj, double *d_C,
+                                         double *d_D, void *d_J, void *stream) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    int rc = check_single_gpu(h, "rovmpc_tether_cost_device");
+    if (rc) return rc;
+    if (!h->tether_on) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_tether_cost_device: no tether cost is set (rovmpc_set_tether_cost)");
+    if (!d_state || !d_U || !d_traj) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_tether_cost_device: null pointer (d_state, d_U or d_traj)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return launch_tether_cost(h, d_state, d_U, d_traj, d_J, d_C, d_D, 1, (hipStream_t)stream);
+}
+
 // What the loop hands the two launches of iteration i.  The last group is set in the last iteration of a step only (the
 // update then also shifts the plan by one node, passes the rollout's record on and, where the step has a mailbox, fills
 // it); *_update_device passes PlanIter{}.
@@ -1603,6 +1703,8 @@ static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, c
              c.name, c.B, h->nav_Bt);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
+    if (h->tether_on && (rc = ensure_tether_traj(h, c.B))) return rc;      // the batch grew after the setting was made
+    void *const traj_all = h->tether_on ? h->d_tether_traj : nullptr;
     const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N, exo_stride = (size_t)loop.T * ROVMPC_STATE_LEN;
     if (!c.single) {
         if (states) memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
@@ -1632,12 +1734,13 @@ static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, c
             if ((rc = sample(it))) return rc;
             const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
             h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
-            rc = enqueue_step(h, c.state, c.U, nullptr, c.record, 0, nullptr, 0, 1, h->stream, c.B);
+            rc = enqueue_step(h, c.state, c.U, traj_all, c.record, 0, nullptr, 0, 1, h->stream, c.B);
             h->arg_J = nullptr;
             h->last_batch = last_batch;
             if (rc) return rc;
             if (h->nav_on && (rc = launch_nav_cost(h, c.state, c.U, c.J, nullptr, step + (uint64_t)t, c.B,
                                                    !c.single && h->nav_Bt == c.B ? 3 * (size_t)h->nav_Tr : 0, h->stream))) return rc;
+            if (traj_all && (rc = launch_tether_cost(h, c.state, c.U, traj_all, c.J, nullptr, nullptr, c.B, h->stream))) return rc;
             if ((rc = update(it))) return rc;
             cur ^= 1;
         }

@@ -309,6 +309,46 @@ class Engine:
         C_out = d_C.cpu().numpy()
         return C_out if d_J is None else (C_out, d_J.cpu().numpy())
 
+    def set_tether_cost(self, tether=None):
+        """The tether keep-out cost of every MPPI and CEM entry of this engine (rovmpc_set_tether_cost): ``tether`` a
+        ``_lib.TetherCost`` as ``_lib.tether_cost(...)`` returns it; None: clear.  Holds from the next control step."""
+        if tether is None:
+            self._check(self.lib.rovmpc_set_tether_cost(self._h, None))
+            return
+        if not isinstance(tether, _lib.TetherCost):
+            raise TypeError("tether must be a _lib.TetherCost (_lib.tether_cost(...))")
+        self._check(self.lib.rovmpc_set_tether_cost(self._h, C.byref(tether)))
+
+    def tether_cost(self, state, U, traj, J=None):
+        """(C (K,), D (K, N)) float64 of the tether cost alone for candidates U (K, N, 3) whose rollout stored the angles
+        ``traj`` (K, N + 1, 2), through the device entry (rovmpc_tether_cost_device): C_k of the law and the signed clearance
+        of every node's cable from the nearest sphere surface grown by the margin (NaN at a non-finite node).  With ``J``
+        (K,), also J' of the law: returns (C, D, J')."""
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        K, N = self.cfg.K, self.cfg.N
+        tr = np.ascontiguousarray(traj, dtype=self.cfg.np_dtype)
+        if tr.shape != (K, N + 1, 2):
+            raise ValueError(f"traj must have shape ({K}, {N + 1}, 2), got {tr.shape}")
+        d_state = torch.tensor(state_array(state), device=dev)
+        d_U = torch.tensor(self._U(U), device=dev)
+        d_traj = torch.tensor(tr, device=dev)
+        d_C = torch.empty(K, dtype=torch.float64, device=dev)
+        d_D = torch.empty((K, N), dtype=torch.float64, device=dev)
+        d_J = None
+        if J is not None:
+            Jh = np.ascontiguousarray(J, dtype=self.cfg.np_dtype)
+            if Jh.shape != (K,):
+                raise ValueError(f"J must have shape ({K},), got {Jh.shape}")
+            d_J = torch.tensor(Jh, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_tether_cost_device(self._h, d_state.data_ptr(), d_U.data_ptr(), d_traj.data_ptr(),
+                                                       d_C.data_ptr(), d_D.data_ptr(), d_J.data_ptr() if d_J is not None else None,
+                                                       torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.synchronize(dev)
+        out = (d_C.cpu().numpy(), d_D.cpu().numpy())
+        return out if d_J is None else out + (d_J.cpu().numpy(),)
+
     def mppi_reset(self, nominal):
         """Set the handle's MPPI nominal plan (N, 3); allocates the MPPI buffers on first use."""
         self._plan_reset(self.lib.rovmpc_mppi_reset, nominal, "nominal")

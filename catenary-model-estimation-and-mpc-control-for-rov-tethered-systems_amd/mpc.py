@@ -209,14 +209,35 @@ def check_nav(nav, B: int, batched: bool):
     return nav
 
 
+class TetherCost:
+    """``TetherCost(spheres, w, margin=0.0)``: the tether keep-out cost of the plan controllers (include/rovmpc.h,
+    rovmpc_set_tether_cost).  ``spheres`` (n, 4), 1 <= n <= 8: (cx, cy, cz, R) in metres.  At every predicted node the
+    cable's shape -- the augmented catenary from the anchor P0 to the vehicle's predicted position under the node's
+    predicted (theta, gamma), ``n_shape_pts`` samples joined by segments -- adds ``w`` times its squared penetration into
+    each sphere grown by ``margin``.  The values are checked here (ValueError / TypeError), before any library call."""
+
+    def __init__(self, spheres, w, margin=0.0):
+        self.c_tether = _lib.tether_cost(spheres, w, margin)
+        self.w, self.margin = float(self.c_tether.w), float(self.c_tether.margin)
+        self.spheres = np.array(self.c_tether.spheres).reshape(-1, 4)[:self.c_tether.n_spheres].copy()
+
+
+def check_tether(tether):
+    """tether of a controller, before the library is called: None or a TetherCost."""
+    if tether is not None and not isinstance(tether, TetherCost):
+        raise TypeError("tether must be a rovmpc.TetherCost or None")
+    return tether
+
+
 class _PlanController:
     """What the four controllers share: an engine of their own, the seed and step counter of the draws, the plan's shape
     and the result of the last step.  The single-problem form; _BatchedPlanController overrides what a batch changes."""
 
     _batch = ""         # "_batch": the engine's batched entries
 
-    def __init__(self, cfg, model, seed: int, overrides: dict, beta=None, lo=None, hi=None, nav=None):
+    def __init__(self, cfg, model, seed: int, overrides: dict, beta=None, lo=None, hi=None, nav=None, tether=None):
         self.seed = int(seed)
+        self.tether = check_tether(tether)
         self.beta, self.box = _lib.noise_correlation(beta), _lib.control_box(lo, hi)      # ValueError before the library is called
         self.nav = check_nav(nav, getattr(self, "B", 1), bool(self._batch))
         self.engine = Engine(cfg, model, **overrides)
@@ -227,6 +248,8 @@ class _PlanController:
             self.engine.mppi_set_bounds(*self.box)
         if self.nav is not None:
             self.engine.set_nav_cost(self.nav.c_nav, self.nav.tracks)
+        if self.tether is not None:
+            self.engine.set_tether_cost(self.tether.c_tether)
         self._default_mean = np.asarray(default_model().mean[3:6], dtype=np.float64)
         self.step_count = 0
         self.last = self.last_stats = None       # StepResult (batched: a list of them), dict
@@ -240,6 +263,12 @@ class _PlanController:
         else:
             self.engine.set_nav_cost(nav.c_nav, nav.tracks)
         self.nav = nav
+
+    def set_tether(self, tether):
+        """Set (a ``TetherCost``) or clear (None) the tether keep-out cost; it holds from the next ``step`` or ``run``."""
+        tether = check_tether(tether)
+        self.engine.set_tether_cost(None if tether is None else tether.c_tether)
+        self.tether = tether
 
     def _entry(self, name: str):
         """engine.mppi_step, engine.cem_reset_batch, ..."""
@@ -376,12 +405,14 @@ class MPPI(_MPPILaw, _PlanController):
     candidates, nominal and the returned control lie inside exactly (rovmpc_set_noise_correlation, rovmpc_mppi_set_bounds).
     ``nav`` (a ``NavCost``, default None) adds path-tracking, rate and keep-out costs of the vehicle's predicted path; the
     track is read at ``step_count``, which ``step`` advances by 1 and ``run`` by T (``set_nav`` changes or clears it).
+    ``tether`` (a ``TetherCost``, default None) keeps the predicted cable shapes out of spheres (``set_tether``).
     """
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, lam: float = 1.0, std=None,
-                 n_iter: int = 1, seed: int = 20250523, nominal=None, beta=None, lo=None, hi=None, nav=None, **overrides):
+                 n_iter: int = 1, seed: int = 20250523, nominal=None, beta=None, lo=None, hi=None, nav=None, tether=None,
+                 **overrides):
         self._set_params(lam, std, n_iter)
-        super().__init__(cfg, model, seed, overrides, beta, lo, hi, nav)
+        super().__init__(cfg, model, seed, overrides, beta, lo, hi, nav, tether)
         self.reset(nominal)
 
 
@@ -396,14 +427,14 @@ class CEM(_CEMLaw, _PlanController):
     n_elite = K / 64 (at least 1).  After ``step``: ``last`` (the record of the last rollout, with u = clamp(mean*[0])),
     ``last_stats`` (J_best, J_worst_elite, n_finite, J0), ``mean`` and ``std`` (the plan and spread the step returned) and
     ``elites`` (the last iteration's elite indices in rank order, -1 padded).  ``beta`` as for ``MPPI``: AR(1) sampling noise;
-    ``nav`` as for ``MPPI``: the navigation cost.
+    ``nav`` and ``tether`` as for ``MPPI``: the navigation and the tether keep-out cost.
     """
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, n_elite: Optional[int] = None,
                  n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0), lo=(-np.inf,) * 3, hi=(np.inf,) * 3,
-                 seed: int = 20250523, mean=None, reserved: int = 0, beta=None, nav=None, **overrides):
+                 seed: int = 20250523, mean=None, reserved: int = 0, beta=None, nav=None, tether=None, **overrides):
         self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
-        super().__init__(cfg, model, seed, overrides, beta, nav=nav)
+        super().__init__(cfg, model, seed, overrides, beta, nav=nav, tether=tether)
         self.reset(mean)
 
 
@@ -455,9 +486,10 @@ class _BatchedPlanController(_PlanController):
 
     _batch = "_batch"
 
-    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict, beta=None, lo=None, hi=None, nav=None):
+    def __init__(self, cfg, model, B, seed: int, seeds, plan, name: str, overrides: dict, beta=None, lo=None, hi=None, nav=None,
+                 tether=None):
         self.B, self.seeds = check_batch(B, seed, seeds, plan, _config_value(cfg, overrides, "N"), name)
-        super().__init__(cfg, model, int(self.seeds[0]), overrides, beta, lo, hi, nav)
+        super().__init__(cfg, model, int(self.seeds[0]), overrides, beta, lo, hi, nav, tether)
         self.records: Optional[np.ndarray] = None
 
     def _seeds(self):
@@ -491,13 +523,13 @@ class BatchedMPPI(_MPPILaw, _BatchedPlanController):
     (include/rovmpc.h, rovmpc_mppi_step_batch).  ``nominal``: (B, N, 3), or (N, 3) / (3,) repeated; default the scaler mean.
     ``step(states)`` takes (B, 16) or a sequence of B states and returns u (B, 3).  After it: ``records`` (B, result_len),
     ``last`` (a list of StepResult), ``nominal`` (B, N, 3), ``last_stats`` (rho, eta, ess, J0: arrays of length B).
-    ``beta``, ``lo``, ``hi`` as for ``MPPI``, shared by the batch; ``nav`` too, its track (Tr, 3) shared or (B, Tr, 3) per problem."""
+    ``beta``, ``lo``, ``hi`` as for ``MPPI``, shared by the batch; ``nav`` too, its track (Tr, 3) shared or (B, Tr, 3) per problem; ``tether`` shared by the batch."""
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int, lam: float = 1.0,
                  std=None, n_iter: int = 1, seed: int = 20250523, seeds=None, nominal=None, beta=None, lo=None, hi=None, nav=None,
-                 **overrides):
+                 tether=None, **overrides):
         self._set_params(lam, std, n_iter)
-        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides, beta, lo, hi, nav)
+        super().__init__(cfg, model, B, seed, seeds, nominal, "nominal", overrides, beta, lo, hi, nav, tether)
         self.reset(nominal)
 
 
@@ -507,14 +539,14 @@ class BatchedCEM(_CEMLaw, _BatchedPlanController):
     of ``CEM`` are shared.  Problem b's results are bit for bit those of ``CEM(seed=seeds[b], mean=mean[b])`` on its own
     (include/rovmpc.h, rovmpc_cem_step_batch).  After ``step``: ``records``, ``last`` (a list of StepResult), ``mean`` and
     ``std`` (B, N, 3), ``elites`` (B, n_elite), ``last_stats`` (J_best, J_worst_elite, n_finite, J0: arrays of length B).
-    ``beta`` and ``nav`` as for ``BatchedMPPI``."""
+    ``beta``, ``nav`` and ``tether`` as for ``BatchedMPPI``."""
 
     def __init__(self, cfg: Optional[MPCConfig] = None, model: Optional[DynamicsModel] = None, *, B: int,
                  n_elite: Optional[int] = None, n_iter: int = 1, alpha: float = 0.0, std=None, std_min=(0.0, 0.0, 0.0),
                  lo=(-np.inf,) * 3, hi=(np.inf,) * 3, seed: int = 20250523, seeds=None, mean=None, reserved: int = 0, beta=None,
-                 nav=None, **overrides):
+                 nav=None, tether=None, **overrides):
         self._set_params(cfg, overrides, n_elite, n_iter, alpha, std, std_min, lo, hi, reserved)
-        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides, beta, nav=nav)
+        super().__init__(cfg, model, B, seed, seeds, mean, "mean", overrides, beta, nav=nav, tether=tether)
         self.reset(mean)
 
 

@@ -475,6 +475,73 @@ int rovmpc_set_nav_cost(rovmpc_handle *h, const rovmpc_nav_cost *nav, const doub
 int rovmpc_nav_cost_device(rovmpc_handle *h, const double *d_state, const void *d_U, uint64_t step,
                            double *d_C, void *d_J, void *stream);
 
+/* ---- the tether keep-out cost of MPPI and CEM: the augmented catenary cable of every predicted node against spheres --------
+ * The navigation cost keeps the VEHICLE out of spheres and the rollout's floor term keeps the cable's lowest point above a
+ * plane; neither keeps the CABLE away from an obstacle.  This setting of the handle, read by every MPPI and CEM entry (step,
+ * batched step, device loop, batched device loop), adds the squared penetration of the cable's sampled shape into up to 8
+ * spheres, with a safety margin, to the costs J[K] by one launch between the rollout (and the navigation cost) and the update.
+ * Law.  Everything in double, whatever cfg.dtype T is, on the T-rounded values the kernels hold: U and the rollout's stored
+ * (theta, gamma) are reals of T, and L = (T) cfg.L, c_lo = (T) cfg.c_lo, c_hi = (T) cfg.c_hi as in the rollout; the state is
+ * double.  Control step with state x, candidate k, A = x.P0, M = cfg.n_shape_pts, up = +1 (ENU) or -1 (NED) from cfg.frame:
+ *      vehicle path: the navigation cost's, bit for bit: c = cfg.v_scale * cfg.dt formed once on the host in double,
+ *             P_0 = x.P1,  P_{n+1}[ch] = fma(c, (double) U[k][n][ch], P_n[ch])                  n = 0 .. N - 1;
+ *      angles: (theta_n, gamma_n) = (double) traj[k][n][0..1] for n = 1 .. N, the values the rollout stored for this
+ *             candidate (node 0 is the measured state, the same for every candidate, and is not used);
+ *      cable points X_{n,m}, m = 0 .. M - 1, the samples of transform_catenary (main_fun.py:38-111) with this build's root:
+ *             rel = P_n - A; theta axis = normalize(xy(rel)) x z and gamma axis = rel / |rel| (main_fun.py:75-89, 102-103,
+ *             with the 1e-9 fallbacks); B' = rod(rel, theta axis, theta_n); l' = |B'_xy|; dH' = up B'_z;
+ *             C' = the root of main_fun.py:418-431 on (l', dH', L) inside [c_lo, c_hi]; x0 = l'/2 - atanh(dH'/L) / C';
+ *             t_m = m / (M - 1);  q_m = (t_m B'_x, t_m B'_y, up (cosh(C'(l' t_m - x0)) - cosh(C' x0)) / C');
+ *             q_m turned by -theta_n about the theta axis, then by gamma_n about the gamma axis;  X_{n,m} = A + q_m;
+ *      no root in the bracket (a taut cable, or a root outside [c_lo, c_hi]): the chord, X_{n,m} = A + t_m rel.  This is
+ *             build-defined: the reference substitutes the two-point segment [start, end] (main_fun.py:67-69), and the
+ *             chord's ends are those two points.  In particular a very slack cable whose root lies beyond c_hi is treated
+ *             as its chord;
+ *      distance: d_{n,j} = min over the M - 1 segments [X_{n,m}, X_{n,m+1}] of the point-to-segment distance from c_j, with
+ *             t* = clamp(((c_j - a).(b - a)) / |b - a|^2, 0, 1) and t* = 0 for a zero-length segment;
+ *      cost:  pen_{n,j} = max(0, (R_j + margin) - d_{n,j});
+ *             C_k = w sum_{n=1..N} sum_{j < n_spheres} pen_{n,j}^2, added in node order, then sphere order;
+ *      non-finite: a node whose theta_n, gamma_n or gamma axis (rel = 0) is non-finite has non-finite points, on the chord
+ *             too (the reference turns the chord's end by the same rotations).  If any X_{n,m} of candidate k is
+ *             non-finite, C_k = +inf, and the update ignores the candidate as the MPPI and CEM laws say;
+ *      J'_k = (T) ((double) J_k + C_k) where J_k is finite; a non-finite J_k is left bit for bit.  With a navigation cost
+ *             also set, that cost is applied first and the tether cost on its J': each step rounds to T, so the order is
+ *             part of the law.
+ * The bits of C_k are a function of (x.P0, x.P1, U[k], traj[k], the setting, the config) alone: not of K, B, the problem's
+ * index, the candidate's place in a workgroup's tile, nor of the entry the step came through.  No float atomics.  So both
+ * equivalence laws hold with a tether cost: problem b of a batch is bit for bit its own single controller, and row i of a
+ * device loop is bit for bit the host-stepped step.
+ * Step 4 of the MPPI and CEM laws then reads J'.  The record keeps [J*, k*, u, traj] of the rollout's own fused arg-min, the
+ * same limitation as with a navigation cost.
+ * Launches: with a tether cost the rollout also stores all K trajectories into a buffer [B][K][N+1][2] of the handle (made
+ * when the setting is made, grown with the batch, freed with the handle), which puts it on the tail it takes for
+ * rovmpc_rollout_costs with traj_all; its costs and record keep their bits (for the compiled-in model, a model compiled
+ * by hiprtc and the interpreter alike).  A control step then takes one more launch per iteration.  Without the setting
+ * (the default, and after clearing) every entry issues the launches it issued before the setting existed and returns the
+ * same bits.
+ * rovmpc_set_tether_cost takes effect from the next control step; on ROVMPC_ERR_INVALID (a null handle, a struct_size
+ * mismatch, a value outside the ranges below, a horizon and n_shape_pts whose node does not fit the kernel's LDS) the previous
+ * setting stays.  ROVMPC_ERR_UNSUPPORTED once rovmpc_comm_init has run.  The spheres and weight are shared by a batch.
+ * Scope: the shooting step (rovmpc_step, rovmpc_mpc_step_sampled) does not read the setting.
+ * Not provided: boxes or other shapes, moving obstacles, a per-problem setting, cable self-contact. */
+#define ROVMPC_TETHER_MAX_SPHERES 8
+typedef struct rovmpc_tether_cost {
+    int32_t struct_size;             /* = sizeof(rovmpc_tether_cost), ABI check                          */
+    int32_t n_spheres;               /* 1..ROVMPC_TETHER_MAX_SPHERES                                     */
+    double  w;                       /* finite, >= 0                                                     */
+    double  margin;                  /* metres, finite, >= 0                                             */
+    double  spheres[ROVMPC_TETHER_MAX_SPHERES][4];   /* cx, cy, cz, R: finite, R >= 0; rows >= n_spheres ignored */
+} rovmpc_tether_cost;
+/* tc NULL: clear. */
+int rovmpc_set_tether_cost(rovmpc_handle *h, const rovmpc_tether_cost *tc);
+/* The term alone on caller device buffers, asynchronously on `stream`: d_state[16], d_U[K][N][3] and d_traj[K][N+1][2]
+ * (reals of cfg.dtype; node 0 of d_traj is not read); d_C[K] double or NULL receives C_k; d_D[K][N] double or NULL the
+ * signed clearance min_j (d_{n,j} - (R_j + margin)) of node n + 1, NaN at a non-finite node; d_J[K] (reals of cfg.dtype) or
+ * NULL is updated in place by the law.  ROVMPC_ERR_INVALID without a tether cost or for a null d_state, d_U or d_traj.  A
+ * call must have finished before the next rovmpc_set_tether_cost. */
+int rovmpc_tether_cost_device(rovmpc_handle *h, const double *d_state, const void *d_U, const void *d_traj,
+                              double *d_C, double *d_D, void *d_J, void *stream);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
