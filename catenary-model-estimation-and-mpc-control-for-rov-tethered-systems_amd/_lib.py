@@ -22,6 +22,14 @@ ERR_NAMES = {0: "OK", -1: "ROVMPC_ERR_INVALID", -2: "ROVMPC_ERR_HIP", -3: "ROVMP
              -4: "ROVMPC_ERR_UNSUPPORTED"}
 
 
+# rovmpc_probe_fn of include/rovmpc.h, in the header's order
+PROBE_FN = {name: i for i, name in enumerate((
+    "SIN", "SIN_PINNED", "SIN_BOUNDED", "SINCOS", "SINCOS_PINNED", "RCP", "DIV", "DIVQ", "DIVX", "SQRTQ", "SQRT", "MIN_RAW",
+    "EXP_INC", "EXP_INC_TINY", "SINH_POS", "SINHC_M1_SMALL", "COSH_M1_SMALL"))}
+PROBE_TWO_OPERANDS = ("DIV", "DIVQ", "DIVX", "MIN_RAW")
+PROBE_TWO_RESULTS = ("SINCOS", "SINCOS_PINNED")
+
+
 class RovmpcError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {message}")
@@ -296,6 +304,7 @@ _SIGNATURES = {
     "rovmpc_closed_loop_form": (C.c_int32, [_P]),
     "rovmpc_timing_enable": (C.c_int, [_P, C.c_int32]),
     "rovmpc_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "rovmpc_math_probe": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P]),
     "rovmpc_predict": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     "rovmpc_eval_expression": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P]),
     "rovmpc_lagrangian_rollout": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P]),

@@ -28,7 +28,10 @@ template <typename X, typename Y> struct RvCond<false, X, Y> { typedef Y type; }
 // Cody-Waite reduction r = x - k (pi/2)_hi - k (pi/2)_lo is exact to < 1 ulp of r and the
 // fdlibm minimax kernels (k_sin.c / k_cos.c, degree 13 / 14) give sin and cos of r to < 1 ulp:
 // ~35 instructions for the pair.  Larger arguments take the library path (a branch no rollout
-// on physical data ever enters).
+// on physical data ever enters).  Measured against 50 digits (tests/test_device_math_gpu.py): sin 1.23, cos 1.27 ulp at
+// most, in units of ulp(result) + (|x| / (pi/2)) ulp(pio2_lo) / 2 -- the second term is the rounding of pio2_lo itself, the one
+// error that grows with the argument, and shows next to a multiple of pi/2 only.  sin(-0.0) is +0.0 (k = -0: (+0) pio2_hi +
+// (-0) = +0), here and in the three kernels below; include/rovmpc.h states it.
 // Out-of-line so the six call sites of the sequential phase do not each inline ~150
 // instructions of Payne-Hanek reduction they never execute.
 __device__ __attribute__((noinline)) double2 slow_sincos_f64(double x) { double s, c; ::sincos(x, &s, &c); return make_double2(s, c); }
@@ -80,7 +83,11 @@ RV_DEV void fast_sincos_f64(double x, double *s, double *c) { fast_sincos_k(x, t
 // sin alone: k = rint(x / pi), r = x - k pi in [-pi/2, pi/2] (two FMAs), odd polynomial to r^17 interpolating
 // (sin r / r - 1) / r^2 at the Chebyshev nodes of [0, (pi/2)^2] (fitted with 60-digit arithmetic; 3.7e-17 relative with the
 // coefficients rounded to double -- the Taylor polynomial needs r^23 for the same), sign (-1)^k.  ~19 instructions instead
-// of ~38 for the sincos pair; < 1 ulp against a 40-digit reference for |x| < 1e6.
+// of ~38 for the sincos pair.  2.02 ulp at most against a 50-digit reference over the whole fast path (unit as above, with pi
+// and pi_lo), 1.7 % of the arguments in [-pi/2, pi/2] above 1 ulp, the largest next to |r| = pi/2: there r z p is a third of
+// the result and carries the roundings of z, r z and the Estrin levels (half an ulp of a value in [2, 4) each), on top of the
+// last fma's own half ulp -- the price of one polynomial over the whole of [-pi/2, pi/2]; the pair, which reduces to
+// [-pi/4, pi/4], stays at 1.3.  The correctly rounded restatement of these lines gives the same 2.02.
 struct SinK { double inv_pi, pi_hi, pi_lo, c[8]; };
 RV_DEV SinK sin_constants(bool pin) {
     SinK k = {0.31830988618379067154, 3.14159265358979311600e+00, 1.22464679914735317723e-16,
@@ -114,8 +121,8 @@ RV_DEV double fast_sin_k(double x, const SinK &K) {
 // fp32 (BASELINE config 3).  The device library's sinf / sincosf inline a Payne-Hanek reduction beside every call and
 // evaluate both polynomials for either result: ~40 instructions and six mask operations on the hot path, twice the fp64
 // chain's own sine.  Same construction as above in single precision: k = rint(x / pi), r = x - k pi by two FMAs (exact
-// product, |k| < 2^14 below the limit), odd polynomial to r^9 fitted on [-pi/2, pi/2] (1.9 ulp measured against fp64 over
-// 2e5 points), sign (-1)^k -- 13 instructions, no branch; the pair reduces by pi/2 and uses the fdlibm single-precision
+// product, |k| < 2^14 below the limit), odd polynomial to r^9 fitted on [-pi/2, pi/2] (1.86 ulp at most against 50 digits;
+// the pair 1.38), sign (-1)^k -- 13 instructions, no branch; the pair reduces by pi/2 and uses the fdlibm single-precision
 // kernels (k_sinf.c / k_cosf.c).  Larger arguments (and NaN) take the library, out of line.
 constexpr float TRIGF_FAST_LIMIT = 32768.0f;
 __device__ __attribute__((noinline)) float slow_sinf_f32(float x) { return ::sinf(x); }
@@ -195,7 +202,7 @@ RV_DEV float  m_exp(float x)  { return ::expf(x); }
 RV_DEV double m_log(double x) { return ::log(x); }
 RV_DEV float  m_log(float x)  { return ::logf(x); }
 RV_DEV double m_sqrt(double x) { return ::sqrt(x); }
-RV_DEV float  m_sqrt(float x)  { return __builtin_amdgcn_sqrtf(x); }   // v_sqrt_f32: 1 ulp, no fix-up sequence
+RV_DEV float  m_sqrt(float x)  { return __builtin_amdgcn_sqrtf(x); }   // v_sqrt_f32: 1 ulp (0.88 measured), no fix-up sequence; a denormal x reads as 0
 RV_DEV double m_pow(double x, double y) { return ::pow(x, y); }
 RV_DEV float  m_pow(float x, float y)  { return ::powf(x, y); }
 RV_DEV double m_fma(double a, double b, double c) { return ::fma(a, b, c); }
@@ -213,14 +220,14 @@ RV_DEV float  m_min_raw(float a, float b)  { float r; asm("v_min_f32 %0, %1, %2"
 RV_DEV bool m_finite(double x) { return ::isfinite(x); }
 RV_DEV bool m_finite(float x)  { return ::isfinite(x); }
 
-// 1/x for finite positive x away from the denormals: v_rcp_f64 (~26 bits) + two Newton steps, ~1 ulp, 5
+// 1/x for finite positive x away from the denormals: v_rcp_f64 (~26 bits) + two Newton steps, 1 ulp (0.50 measured), 5
 // instructions instead of the ~18 of an IEEE division.  Not for x that may be 0 or inf (0 * inf = NaN).
 RV_DEV double fast_rcp(double x) {
     double r = __builtin_amdgcn_rcp(x);
     r = ::fma(r, ::fma(-x, r, 1.0), r);
     return ::fma(r, ::fma(-x, r, 1.0), r);
 }
-RV_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }      // v_rcp_f32: 1 ulp
+RV_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }      // v_rcp_f32: 1 ulp (0.79 measured)
 // a / b on the geometry chains: in fp64 the nine-instruction quotient of m_divq below; in fp32 (parity rule: same arg-min or
 // |dJ|/J < 1e-4) one v_rcp_f32 and a multiplication instead of the ten-instruction division sequence
 RV_DEV double m_divq(double a, double b);
@@ -247,19 +254,29 @@ RV_DEV double m_divx(double a, double b) {
     return m_divq(a, b);
 }
 RV_DEV float m_divx(float a, float b) { return a / b; }
-// sqrt of a squared norm on the integrating wave (|v|^2, |v x u|^2: zero or comfortably inside the exponent range): v_rsq_f64
-// with one Goldschmidt step and one residual correction (1 ulp), without the operand scaling and the second correction of
-// the compiler's sequence -- eleven instructions instead of seventeen.  0 and inf map to themselves, NaN and negatives to NaN.
+// sqrt of a squared norm on the integrating wave (|v|^2, |v x u|^2): v_rsq_f64 with one Goldschmidt step and one residual
+// correction, without the second correction of the compiler's sequence.  0 and inf map to themselves, NaN and negatives to NaN.
+// 1 ulp for every x (0.50 measured against 50 digits: denormals, 2^-1022 and DBL_MAX included).
+// A denormal x needs care in one place only: the residual x - g^2 would be a multiple of 2^-1074 with a handful of bits or
+// none, and the result the uncorrected Goldschmidt iterate (10.7 ulp, measured).  So the residual is formed 2^128 up for those
+// lanes: X = 2^128 x and G = 2^128 g run beside g through the same step (the scalings are exact, so r is the same number), H
+// carries 2^-128, and fma(fma(-g, G, X), H, g) is the same correction without the underflow.  For every other x the scale is
+// 1 and X, G, H are x, g, h bit for bit, so no normal result changes.  The extra operations hang off x and y beside the
+// chain x -> y -> g -> r -> g -> residual -> g, not on it: +0.02 us of 13.5 on the default rollout, inside the spread, where
+// the compiler's scaling of x and of the result (two operations on the chain) cost +0.06 and a wave-uniform branch to ::sqrt
+// +0.19 (profiles/sqrtq_denormal_ab.txt).
 RV_DEV double m_sqrtq(double x) {
+    const bool den = x < 0x1p-1022;      // denormal (0 and the negatives too: 0 scales to 0, the negatives end as NaN either way)
     const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = 0.5 * y;
-    const double r = ::fma(-h, g, 0.5);
-    g = ::fma(g, r, g); h = ::fma(h, r, h);
-    g = ::fma(::fma(-g, g, x), h, g);
+    const double X = __builtin_amdgcn_ldexp(x, den ? 128 : 0);
+    double g = x * y, G = X * y, H = (den ? 0x1p-129 : 0.5) * y;
+    const double r = ::fma(-H, G, 0.5);
+    g = ::fma(g, r, g); G = ::fma(G, r, G); H = ::fma(H, r, H);
+    g = ::fma(::fma(-g, G, X), H, g);
     return (x == 0.0 || x == __builtin_inf()) ? x : g;
 }
 RV_DEV float m_sqrtq(float x) { return m_sqrt(x); }
-RV_DEV float  m_div(float a, float b)  { return a * __builtin_amdgcn_rcpf(b); }
+RV_DEV float  m_div(float a, float b)  { return a * __builtin_amdgcn_rcpf(b); }      // 2 ulp (1.62 measured)
 
 template <typename T> RV_DEV T m_eps();
 template <> RV_DEV double m_eps<double>() { return 2.220446049250313e-16; }
@@ -322,7 +339,8 @@ template <typename T> RV_DEV T catenary_f(T C, T l, T L2mH2) {
 }
 
 // sinh(x)/x - 1 and cosh(x) - 1 for 0 <= x < 0.5 without cancellation (8 series terms,
-// truncation < 1e-19 relative at x = 0.5).
+// truncation < 1e-19 relative at x = 0.5).  Relative error 1.90 and 1.38 ulp at most in fp64 (1.90, 1.42 in fp32), one rounding
+// per level of the nest.
 template <typename T> RV_DEV T sinhc_m1_small(T x2) {
     return x2 * T(1.0 / 6) * (T(1) + x2 * T(1.0 / 20) * (T(1) + x2 * T(1.0 / 42) * (T(1) + x2 * T(1.0 / 72) *
            (T(1) + x2 * T(1.0 / 110) * (T(1) + x2 * T(1.0 / 156) * (T(1) + x2 * T(1.0 / 210) * (T(1) + x2 * T(1.0 / 272))))))));
@@ -332,7 +350,8 @@ template <typename T> RV_DEV T cosh_m1_small(T x2) {
            (T(1) + x2 * T(1.0 / 90) * (T(1) + x2 * T(1.0 / 132) * (T(1) + x2 * T(1.0 / 182) * (T(1) + x2 * T(1.0 / 240))))))));
 }
 
-// sinh(x) for x >= 0: series below 0.5, (e^x - e^-x)/2 above (relative error ~1 ulp either way).
+// sinh(x) for x >= 0: series below 0.5 (1.23 ulp measured in fp64, 1.36 in fp32), (e^x - e^-x)/2 above (1.18 / 1.48 ulp;
+// the form's first-order bound is 3.5 ulp just above ln 2, where e has four times the ulp of the result).
 template <typename T> RV_DEV T sinh_pos(T x) {
     if (x < T(0.5)) return x * (T(1) + sinhc_m1_small(x * x));
     const T e = m_exp(x);

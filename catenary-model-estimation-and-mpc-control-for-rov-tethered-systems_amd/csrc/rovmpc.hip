@@ -2292,6 +2292,46 @@ extern "C" int rovmpc_eval_expression(rovmpc_handle *h, const int32_t *code, int
     return ROVMPC_OK;
 }
 
+template <typename T>
+static int math_probe_run(rovmpc_handle *h, int32_t fn, const double *x, const double *y, int64_t n, double *out0, double *out1) {
+    std::vector<T> hx(x, x + n), hy, ho((size_t)n), ho1;          // (plain conversion to T)
+    if (y) hy.assign(y, y + n);
+    DevBuf dX, dY, dO, dO1;
+    const size_t bytes = (size_t)n * sizeof(T);
+    UPLOAD(h, dX, hx.data(), bytes);
+    if (y) UPLOAD(h, dY, hy.data(), bytes);
+    HIPCHK(h, dO.alloc(bytes));
+    if (out1) HIPCHK(h, dO1.alloc(bytes));
+    hipLaunchKernelGGL(math_probe_kernel<T>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (int)fn, dX.as<T>(),
+                       y ? dY.as<T>() : (const T *)nullptr, (long long)n, dO.as<T>(), out1 ? dO1.as<T>() : (T *)nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(ho.data(), dO.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (out1) { ho1.resize((size_t)n); HIPCHK(h, hipMemcpyAsync(ho1.data(), dO1.p, bytes, hipMemcpyDeviceToHost, h->stream)); }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < n; ++i) out0[i] = (double)ho[i];
+    if (out1) for (int64_t i = 0; i < n; ++i) out1[i] = (double)ho1[i];
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_math_probe(rovmpc_handle *h, int32_t fn, int32_t dtype, const double *x, const double *y, int64_t n,
+                                 double *out0, double *out1) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    const bool two_in = fn == ROVMPC_PROBE_DIV || fn == ROVMPC_PROBE_DIVQ || fn == ROVMPC_PROBE_DIVX || fn == ROVMPC_PROBE_MIN_RAW;
+    if (fn < 0 || fn >= ROVMPC_PROBE_COUNT || (dtype != ROVMPC_F64 && dtype != ROVMPC_F32) || n < 0 || n > (int64_t)1 << 24 ||
+        (n > 0 && (!x || !out0 || (two_in && !y))))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_math_probe: bad argument");
+    if (fn == ROVMPC_PROBE_SIN_BOUNDED)                      // the unchecked sine is undefined outside its limit
+        for (int64_t i = 0; i < n; ++i) {
+            const double v = dtype == ROVMPC_F32 ? (double)(float)x[i] : x[i];
+            if (!(fabs(v) < (dtype == ROVMPC_F32 ? (double)TRIGF_FAST_LIMIT : TRIG_FAST_LIMIT)))
+                FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_math_probe: input %lld (%g) is outside the bounded sine's domain", (long long)i, x[i]);
+        }
+    if (n == 0) return ROVMPC_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!two_in) y = nullptr;
+    return dtype == ROVMPC_F32 ? math_probe_run<float>(h, fn, x, y, n, out0, out1) : math_probe_run<double>(h, fn, x, y, n, out0, out1);
+}
+
 extern "C" int rovmpc_lagrangian_rollout(rovmpc_handle *h, const int32_t *code_th, int32_t n_th, const int32_t *code_ga, int32_t n_ga,
                                          const double *consts, int32_t n_consts, const double *time, int64_t T, const double *y0,
                                          int64_t B, double *out) {

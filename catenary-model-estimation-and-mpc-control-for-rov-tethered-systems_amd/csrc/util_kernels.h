@@ -986,4 +986,39 @@ __global__ void probe_raise_kernel(unsigned long long *flag, unsigned long long 
     if (threadIdx.x == 0) __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- rovmpc_math_probe: one primitive of device_math.h by itself (diagnostic) --------------------------------------------
+// Element i on global thread i of 256-thread blocks: elements 64 w .. 64 w + 63 are the lanes of wave w, which is what
+// decides the wave-uniform large-argument branch of the trig kernels.  The functions are called as the kernels call them;
+// fn is uniform over the launch.  Threads past n leave before the call, so the last wave runs with a partial exec mask.
+template <typename T>
+__global__ void __launch_bounds__(256)
+math_probe_kernel(int fn, const T *__restrict__ x, const T *__restrict__ y, long long n, T *__restrict__ out0, T *__restrict__ out1) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const T a = x[i], b = y ? y[i] : T(0);
+    T r0 = T(0), r1 = T(0);
+    switch (fn) {
+        case ROVMPC_PROBE_SIN: r0 = m_sin(a); break;
+        case ROVMPC_PROBE_SIN_PINNED: { const Trig<T> tg(true); r0 = tg.sin(a); break; }
+        case ROVMPC_PROBE_SIN_BOUNDED: { const Trig<T> tg(true); r0 = tg.sin_bounded(a); break; }
+        case ROVMPC_PROBE_SINCOS: m_sincos(a, &r0, &r1); break;
+        case ROVMPC_PROBE_SINCOS_PINNED: { const Trig<T> tg(true); tg.sincos(a, &r0, &r1); break; }
+        case ROVMPC_PROBE_RCP: r0 = fast_rcp(a); break;
+        case ROVMPC_PROBE_DIV: r0 = m_div(a, b); break;
+        case ROVMPC_PROBE_DIVQ: r0 = m_divq(a, b); break;
+        case ROVMPC_PROBE_DIVX: r0 = m_divx(a, b); break;
+        case ROVMPC_PROBE_SQRTQ: r0 = m_sqrtq(a); break;
+        case ROVMPC_PROBE_SQRT: r0 = m_sqrt(a); break;
+        case ROVMPC_PROBE_MIN_RAW: r0 = m_min_raw(a, b); break;
+        case ROVMPC_PROBE_EXP_INC: r0 = exp_increment(a); break;
+        case ROVMPC_PROBE_EXP_INC_TINY: r0 = exp_increment_tiny(a); break;
+        case ROVMPC_PROBE_SINH_POS: r0 = sinh_pos(a); break;
+        case ROVMPC_PROBE_SINHC_M1_SMALL: r0 = sinhc_m1_small(a); break;
+        case ROVMPC_PROBE_COSH_M1_SMALL: r0 = cosh_m1_small(a); break;
+        default: break;
+    }
+    out0[i] = r0;
+    if (out1) out1[i] = r1;
+}
+
 }  // namespace rovmpc

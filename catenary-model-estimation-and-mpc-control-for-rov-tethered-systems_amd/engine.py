@@ -632,6 +632,27 @@ class Engine:
         self._check(self.lib.rovmpc_timing_read(self._h, C.byref(avg), C.byref(mn), C.byref(n)))
         return avg.value, mn.value, n.value
 
+    def math_probe(self, fn, x, y=None, dtype: str = "f64"):
+        """Diagnostic (``rovmpc_math_probe``): the device math primitive ``fn`` (a name of ``_lib.PROBE_FN``) on every element
+        of x (and y, for the two-operand ones); element i runs on global thread i of 256-thread blocks.  ``dtype`` "f64" or
+        "f32" (inputs converted with a plain float32 cast, results widened).  Returns one float64 array, or (sin, cos) for the pairs."""
+        if fn not in _lib.PROBE_FN:
+            raise ValueError(f"unknown probe function {fn!r}")
+        if dtype not in ("f64", "f32"):
+            raise ValueError(f"dtype must be 'f64' or 'f32' (got {dtype!r})")
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if (y is not None) != (fn in _lib.PROBE_TWO_OPERANDS):
+            raise ValueError(f"{fn} takes {'two operands' if fn in _lib.PROBE_TWO_OPERANDS else 'one operand'}")
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+            if y.shape != x.shape:
+                raise ValueError("x and y must have the same length")
+        out0 = np.empty(x.shape[0])
+        out1 = np.empty(x.shape[0]) if fn in _lib.PROBE_TWO_RESULTS else None
+        self._check(self.lib.rovmpc_math_probe(self._h, _lib.PROBE_FN[fn], _lib.F32 if dtype == "f32" else _lib.F64, _ptr(x), _ptr(y),
+                                               x.shape[0], _ptr(out0), _ptr(out1)))
+        return out0 if out1 is None else (out0, out1)
+
     # -- batched helper mirrors ------------------------------------------------------------
     def predict(self, Xs, which: int) -> np.ndarray:
         Xs = np.ascontiguousarray(Xs, dtype=np.float64)

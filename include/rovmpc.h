@@ -88,7 +88,11 @@ extern "C" {
  * (arg << 8) | opcode.  arg = feature index (PUSH_F), constant index (PUSH_C) or integer
  * exponent (POWI).  Operator vocabulary = every operator the reference's PySR runs use
  * (simply.py:65-66, PySRTrainingScript.py:53-54, cluster_run/train_dynamics.py:28-46,
- * dynamic_eq_theta_cluster.py:35-43). */
+ * dynamic_eq_theta_cluster.py:35-43).
+ * Values are what NumPy gives for the reference's lambdified rows to a few ulp (DESIGN.md section 3 has the bound of each
+ * primitive), special operands included, with ONE deviation: sin(-0.0) is +0.0 where NumPy gives -0.0 (the argument
+ * reduction computes (+0) * pi + (-0) = +0), so an expression such as 1 / sin(x) is +inf there and not -inf.  Every other
+ * zero, every non-zero argument and cos(-0.0) = 1 agree in sign; tests/test_device_math_gpu.py pins this behaviour. */
 enum rovmpc_opcode {
     ROVMPC_OP_PUSH_C = 0, ROVMPC_OP_PUSH_F = 1,
     ROVMPC_OP_ADD = 2, ROVMPC_OP_SUB = 3, ROVMPC_OP_MUL = 4, ROVMPC_OP_DIV = 5,
@@ -659,6 +663,37 @@ int32_t rovmpc_closed_loop_form(const rovmpc_handle *h);
 /* Per-launch timing of the rollout kernel with HIP events on the launch stream. */
 int rovmpc_timing_enable(rovmpc_handle *h, int32_t max_launches);
 int rovmpc_timing_read(rovmpc_handle *h, double *avg_ms, double *min_ms, int32_t *count);
+
+/* Diagnostic: one of the library's own device math primitives (csrc/device_math.h) on n host values, so that a test can hold
+ * each of them against a high-precision reference by itself.  The kernel calls the very functions the rollout, the geometry
+ * chains and the loaded expressions call; it runs 256-thread blocks with element i on global thread i, so elements
+ * 64 w .. 64 w + 63 share wave w (the trig kernels take a wave-uniform branch for large arguments).
+ * fn: a rovmpc_probe_fn; dtype: ROVMPC_F64 | ROVMPC_F32 -- for fp32 the inputs are converted with a plain (float) and the
+ * results widened.  y (second operand) and out1 (second result: the cosine of the pairs) may be NULL where fn has none.
+ * ROVMPC_PROBE_SIN_BOUNDED is the unchecked sine, undefined at or above its limit (2^26 in fp64, 32768 in fp32): any such
+ * input, and any non-finite one, is refused with ROVMPC_ERR_INVALID before anything is launched. */
+typedef enum rovmpc_probe_fn {
+    ROVMPC_PROBE_SIN = 0,             /* m_sin                                           */
+    ROVMPC_PROBE_SIN_PINNED = 1,      /* Trig<T>(true).sin                               */
+    ROVMPC_PROBE_SIN_BOUNDED = 2,     /* Trig<T>(true).sin_bounded                       */
+    ROVMPC_PROBE_SINCOS = 3,          /* m_sincos -> (out0, out1)                        */
+    ROVMPC_PROBE_SINCOS_PINNED = 4,   /* Trig<T>(true).sincos -> (out0, out1)            */
+    ROVMPC_PROBE_RCP = 5,             /* fast_rcp                                        */
+    ROVMPC_PROBE_DIV = 6,             /* m_div(x, y)                                     */
+    ROVMPC_PROBE_DIVQ = 7,            /* m_divq(x, y)                                    */
+    ROVMPC_PROBE_DIVX = 8,            /* m_divx(x, y): `/` of a loaded expression        */
+    ROVMPC_PROBE_SQRTQ = 9,           /* m_sqrtq                                         */
+    ROVMPC_PROBE_SQRT = 10,           /* m_sqrt                                          */
+    ROVMPC_PROBE_MIN_RAW = 11,        /* m_min_raw(x, y)                                 */
+    ROVMPC_PROBE_EXP_INC = 12,        /* exp_increment                                   */
+    ROVMPC_PROBE_EXP_INC_TINY = 13,   /* exp_increment_tiny                              */
+    ROVMPC_PROBE_SINH_POS = 14,       /* sinh_pos                                        */
+    ROVMPC_PROBE_SINHC_M1_SMALL = 15, /* sinhc_m1_small(x): x is the SQUARE of the argument */
+    ROVMPC_PROBE_COSH_M1_SMALL = 16,  /* cosh_m1_small(x): likewise                      */
+    ROVMPC_PROBE_COUNT = 17
+} rovmpc_probe_fn;
+int rovmpc_math_probe(rovmpc_handle *h, int32_t fn, int32_t dtype, const double *x, const double *y, int64_t n,
+                      double *out0, double *out1);
 
 /* ---- batched mirrors of the reference's per-row helpers (host pointers) ---------------- */
 
