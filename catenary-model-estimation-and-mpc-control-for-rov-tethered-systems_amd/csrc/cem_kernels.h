@@ -2,7 +2,7 @@
 // spread, and one launch that selects the n_elite cheapest candidates exactly and refits mean and spread from them.
 // The law is stated in include/rovmpc.h above rovmpc_cem_params.
 #pragma once
-#include "util_kernels.h"
+#include "mppi_kernels.h"
 
 namespace rovmpc {
 

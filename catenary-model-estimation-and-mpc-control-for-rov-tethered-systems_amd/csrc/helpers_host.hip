@@ -1,0 +1,441 @@
+// helpers_host.hip -- the batched helper entries of include/rovmpc.h: host pointers in, host pointers out.
+#include "rovmpc_internal.h"
+
+#include "util_kernels.h"
+
+// ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
+
+namespace {          // (the scaffold's types stay out of the library's dynamic symbols)
+
+// n elements of T in device memory, owned by the HelperCall that handed it out.
+template <typename T> struct DevArray {
+    T *p; size_t n;
+    operator T *() const { return p; }
+};
+
+// One helper call.  Sets the device, hands out device buffers that it frees on every exit path, queues uploads and copies
+// back on h->stream, and finish() ends the call with the launch check and one synchronise.  The first HIP error is kept:
+// every later step of the scaffold does nothing, the entry skips its launches (ok()), and finish() reports that error.
+class HelperCall {
+    rovmpc_handle *h_;
+    std::vector<void *> owned_;
+    hipError_t err_ = hipSuccess;
+    const char *what_ = "";
+    int line_ = 0;
+    bool keep(hipError_t e, const char *what, int line) {
+        if (err_ == hipSuccess && e != hipSuccess) { err_ = e; what_ = what; line_ = line; }
+        return err_ == hipSuccess;
+    }
+    void *alloc(size_t bytes) {          // (never zero bytes: an empty optional input still gets a pointer)
+        void *p = nullptr;
+        if (ok() && keep(hipMalloc(&p, bytes ? bytes : 8), "hipMalloc", __LINE__)) owned_.push_back(p);
+        return p;
+    }
+    void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        if (ok()) keep(hipMemcpyAsync(dst, src, bytes, kind, h_->stream), "hipMemcpyAsync", __LINE__);
+    }
+public:
+    explicit HelperCall(rovmpc_handle *h) : h_(h) { keep(hipSetDevice(h->cfg.device), "hipSetDevice", __LINE__); }
+    ~HelperCall() { for (void *p : owned_) (void)hipFree(p); }
+    HelperCall(const HelperCall &) = delete;
+    HelperCall &operator=(const HelperCall &) = delete;
+    bool ok() const { return err_ == hipSuccess; }
+    template <typename T> DevArray<T> buffer(size_t n) { return {(T *)alloc(n * sizeof(T)), n}; }
+    template <typename T> DevArray<T> upload(const T *src, size_t n) {
+        DevArray<T> d = buffer<T>(n);
+        copy(d.p, src, n * sizeof(T), hipMemcpyHostToDevice);
+        return d;
+    }
+    // the whole buffer back to the host; a null `dst` is an optional output the caller did not ask for
+    template <typename T> void download(T *dst, const DevArray<T> &d) {
+        if (dst) copy(dst, d.p, d.n * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    int finish() {
+        if (ok()) keep(hipGetLastError(), "hipGetLastError()", __LINE__);
+        if (ok()) keep(hipStreamSynchronize(h_->stream), "hipStreamSynchronize(h->stream)", __LINE__);
+        if (ok()) return ROVMPC_OK;
+        FAIL(h_, ROVMPC_ERR_HIP, "%s failed: %s (%s:%d)", what_, hipGetErrorString(err_), __FILE__, line_);
+    }
+};
+
+}  // namespace
+
+static inline int grid_for(long long n, int bs) { return (int)((n + bs - 1) / bs); }
+
+extern "C" int rovmpc_predict(rovmpc_handle *h, const double *Xs, int64_t n, int32_t which, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!h->has_model) FAIL(h, ROVMPC_ERR_NO_MODEL, "rovmpc_set_model has not been called");
+    if (n < 0 || (n > 0 && (!Xs || !out)) || which < 0 || which > 1) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_predict: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dX = c.upload(Xs, (size_t)n * h->n_feat);
+    const auto dO = c.buffer<double>((size_t)n);
+    const int bs = 256;
+    if (c.ok())
+        hipLaunchKernelGGL(predict_kernel, dim3(grid_for(n, bs)), dim3(bs), ROVMPC_MAX_STACK * bs * sizeof(double), h->stream,
+                           dX.p, (long long)n, h->n_feat, which == 0 ? h->d_code_th : h->d_code_ga,
+                           which == 0 ? h->n_th : h->n_ga, h->d_consts64, dO.p);
+    c.download(out, dO);
+    return c.finish();
+}
+
+extern "C" int rovmpc_eval_expression(rovmpc_handle *h, const int32_t *code, int32_t n_code, const double *consts, int32_t n_consts,
+                                      const double *X, int32_t F, int64_t n, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!code || n < 0 || F < 1 || F > ROVMPC_MAX_FEATURES || n_consts < 0 || n_consts > ROVMPC_MAX_CODE || (n_consts > 0 && !consts) ||
+        (n > 0 && (!X || !out)))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_eval_expression: bad argument");
+    if (const char *why = validate_code(code, n_code, F, n_consts)) FAIL(h, ROVMPC_ERR_INVALID, "program: %s", why);
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const double zero = 0.0;
+    const auto dX = c.upload(X, (size_t)n * F);
+    const auto dC = c.upload(code, (size_t)n_code);
+    const auto dK = c.upload(n_consts ? consts : &zero, (size_t)(n_consts ? n_consts : 1));
+    const auto dO = c.buffer<double>((size_t)n);
+    const int bs = 256;
+    if (c.ok())
+        hipLaunchKernelGGL(predict_kernel, dim3(grid_for(n, bs)), dim3(bs), ROVMPC_MAX_STACK * bs * sizeof(double), h->stream,
+                           dX.p, (long long)n, (int)F, dC.p, (int)n_code, dK.p, dO.p);
+    c.download(out, dO);
+    return c.finish();
+}
+
+template <typename T>
+static int math_probe_run(rovmpc_handle *h, int32_t fn, const double *x, const double *y, int64_t n, double *out0, double *out1) {
+    std::vector<T> hx(x, x + n), hy, ho((size_t)n), ho1;          // (plain conversion to T)
+    if (y) hy.assign(y, y + n);
+    if (out1) ho1.resize((size_t)n);
+    HelperCall c(h);
+    const auto dX = c.upload(hx.data(), (size_t)n);
+    const auto dY = y ? c.upload(hy.data(), (size_t)n) : DevArray<T>{nullptr, 0};
+    const auto dO = c.buffer<T>((size_t)n);
+    const auto dO1 = out1 ? c.buffer<T>((size_t)n) : DevArray<T>{nullptr, 0};
+    if (c.ok())
+        hipLaunchKernelGGL(math_probe_kernel<T>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (int)fn, (const T *)dX.p,
+                           (const T *)dY.p, (long long)n, dO.p, dO1.p);
+    c.download(ho.data(), dO);
+    if (out1) c.download(ho1.data(), dO1);
+    if (int rc = c.finish()) return rc;
+    for (int64_t i = 0; i < n; ++i) out0[i] = (double)ho[i];
+    if (out1) for (int64_t i = 0; i < n; ++i) out1[i] = (double)ho1[i];
+    return ROVMPC_OK;
+}
+
+extern "C" int rovmpc_math_probe(rovmpc_handle *h, int32_t fn, int32_t dtype, const double *x, const double *y, int64_t n,
+                                 double *out0, double *out1) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    const bool two_in = fn == ROVMPC_PROBE_DIV || fn == ROVMPC_PROBE_DIVQ || fn == ROVMPC_PROBE_DIVX || fn == ROVMPC_PROBE_MIN_RAW;
+    if (fn < 0 || fn >= ROVMPC_PROBE_COUNT || (dtype != ROVMPC_F64 && dtype != ROVMPC_F32) || n < 0 || n > (int64_t)1 << 24 ||
+        (n > 0 && (!x || !out0 || (two_in && !y))))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_math_probe: bad argument");
+    if (fn == ROVMPC_PROBE_SIN_BOUNDED)                      // the unchecked sine is undefined outside its limit
+        for (int64_t i = 0; i < n; ++i) {
+            const double v = dtype == ROVMPC_F32 ? (double)(float)x[i] : x[i];
+            if (!(fabs(v) < (dtype == ROVMPC_F32 ? (double)TRIGF_FAST_LIMIT : TRIG_FAST_LIMIT)))
+                FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_math_probe: input %lld (%g) is outside the bounded sine's domain", (long long)i, x[i]);
+        }
+    if (n == 0) return ROVMPC_OK;
+    if (!two_in) y = nullptr;
+    return dtype == ROVMPC_F32 ? math_probe_run<float>(h, fn, x, y, n, out0, out1) : math_probe_run<double>(h, fn, x, y, n, out0, out1);
+}
+
+extern "C" int rovmpc_lagrangian_rollout(rovmpc_handle *h, const int32_t *code_th, int32_t n_th, const int32_t *code_ga, int32_t n_ga,
+                                         const double *consts, int32_t n_consts, const double *time, int64_t T, const double *y0,
+                                         int64_t B, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!code_th || !code_ga || !time || !y0 || !out || T < 1 || B < 1 || n_consts < 0 || n_consts > ROVMPC_MAX_CODE || (n_consts > 0 && !consts))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_lagrangian_rollout: bad argument");
+    const char *why;
+    if ((why = validate_code(code_th, n_th, 4, n_consts))) FAIL(h, ROVMPC_ERR_INVALID, "theta acceleration program: %s", why);
+    if ((why = validate_code(code_ga, n_ga, 4, n_consts))) FAIL(h, ROVMPC_ERR_INVALID, "gamma acceleration program: %s", why);
+    HelperCall c(h);
+    const double zero = 0.0;
+    const auto dCt = c.upload(code_th, (size_t)n_th);
+    const auto dCg = c.upload(code_ga, (size_t)n_ga);
+    const auto dK = c.upload(n_consts ? consts : &zero, (size_t)(n_consts ? n_consts : 1));
+    const auto dT = c.upload(time, (size_t)T);
+    const auto dY = c.upload(y0, (size_t)B * 4);
+    const auto dO = c.buffer<double>((size_t)4 * B * T);
+    const int bs = 64;
+    if (c.ok())
+        hipLaunchKernelGGL(lagrangian_rollout_kernel, dim3(grid_for(B, bs)), dim3(bs), (size_t)(4 + ROVMPC_MAX_STACK) * bs * sizeof(double), h->stream,
+                           dCt.p, (int)n_th, dCg.p, (int)n_ga, dK.p, dT.p, (long long)T, dY.p, (long long)B, dO.p);
+    c.download(out, dO);
+    return c.finish();
+}
+
+extern "C" int rovmpc_replay(rovmpc_handle *h, const double *Xs, const double *time, int64_t T, double theta0, double gamma0,
+                             int32_t integrator, double *theta_out, double *gamma_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!h->has_model) FAIL(h, ROVMPC_ERR_NO_MODEL, "rovmpc_set_model has not been called");
+    if (T < 1 || !Xs || !time || integrator < ROVMPC_RK4 || integrator > ROVMPC_TRAPEZOID)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_replay: bad argument");
+    HelperCall c(h);
+    const auto dX = c.upload(Xs, (size_t)T * h->n_feat);
+    const auto dT = c.upload(time, (size_t)T);
+    const auto dIt = c.buffer<double>((size_t)T), dIg = c.buffer<double>((size_t)T);
+    const auto dOt = c.buffer<double>((size_t)T), dOg = c.buffer<double>((size_t)T);
+    if (!c.ok()) return c.finish();
+    if (integrator >= ROVMPC_DOUBLE_EULER) {
+        // second-derivative models: predict every row, then integrate twice
+        const int bs = 256;
+        for (int which = 0; which < 2; ++which)
+            hipLaunchKernelGGL(predict_kernel, dim3(grid_for(T, bs)), dim3(bs), ROVMPC_MAX_STACK * bs * sizeof(double), h->stream,
+                               dX.p, (long long)T, h->n_feat, which == 0 ? h->d_code_th : h->d_code_ga,
+                               which == 0 ? h->n_th : h->n_ga, h->d_consts64, which == 0 ? dIt.p : dIg.p);
+        hipLaunchKernelGGL(replay_second_order_kernel, dim3(1), dim3(64), 0, h->stream, dIt.p, dIg.p, dT.p, (long long)T, theta0,
+                           gamma0, integrator, dOt.p, dOg.p);
+    } else {
+        if (T > 1) {
+            const int bs = 128;
+            const size_t lds = (size_t)(h->n_feat + ROVMPC_MAX_STACK) * bs * sizeof(double);
+            hipLaunchKernelGGL(replay_increments_kernel, dim3(grid_for(T - 1, bs)), dim3(bs), lds, h->stream, dX.p, dT.p,
+                               (long long)T, h->n_feat, h->d_code_th, h->n_th, h->d_code_ga, h->n_ga, h->d_consts64, integrator,
+                               dIt.p, dIg.p);
+        }
+        hipLaunchKernelGGL(replay_cumsum_kernel, dim3(1), dim3(64), 0, h->stream, dIt.p, dIg.p, (long long)T, theta0, gamma0,
+                           dOt.p, dOg.p);
+    }
+    c.download(theta_out, dOt);
+    c.download(gamma_out, dOg);
+    return c.finish();
+}
+
+extern "C" int rovmpc_solve_catenary(rovmpc_handle *h, const double *l, const double *dH, double L, int64_t n, double *C_out,
+                                     double *T_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (n < 0 || (n > 0 && (!l || !dH || !C_out))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_solve_catenary: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dl = c.upload(l, (size_t)n);
+    const auto dh = c.upload(dH, (size_t)n);
+    const auto dC = c.buffer<double>((size_t)n), dT = c.buffer<double>((size_t)n);
+    if (c.ok())
+        hipLaunchKernelGGL(solve_catenary_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dl.p, dh.p, L, h->cfg.c_lo,
+                           h->cfg.c_hi, h->cfg.cable_wet_weight / L, (long long)n, dC.p, T_out ? dT.p : nullptr);
+    c.download(C_out, dC);
+    c.download(T_out, dT);
+    return c.finish();
+}
+
+extern "C" int rovmpc_rodrigues(rovmpc_handle *h, const double *v, const double *axis, const double *angle, int64_t n, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (n < 0 || (n > 0 && (!v || !axis || !angle || !out))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_rodrigues: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dv = c.upload(v, (size_t)n * 3);
+    const auto da = c.upload(axis, (size_t)n * 3);
+    const auto dg = c.upload(angle, (size_t)n);
+    const auto dout = c.buffer<double>((size_t)n * 3);
+    if (c.ok())
+        hipLaunchKernelGGL(rodrigues_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dv.p, da.p, dg.p, (long long)n, dout.p);
+    c.download(out, dout);
+    return c.finish();
+}
+
+extern "C" int rovmpc_catenary_points(rovmpc_handle *h, const double *A, const double *B, double L, int64_t n, int32_t M,
+                                      double *pts, int32_t *valid, double *params) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (n < 0 || M < 2 || (n > 0 && (!A || !B || !pts || !valid))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_catenary_points: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dA = c.upload(A, (size_t)n * 3);
+    const auto dB = c.upload(B, (size_t)n * 3);
+    const auto dP = c.buffer<double>((size_t)n * M * 3);
+    const auto dV = c.buffer<int32_t>((size_t)n);
+    const auto dQ = c.buffer<double>((size_t)n * 3);
+    const double up = h->cfg.frame == ROVMPC_ENU ? 1.0 : -1.0;
+    if (c.ok())
+        hipLaunchKernelGGL(catenary_points_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dA.p, dB.p, L, up, h->cfg.c_lo,
+                           h->cfg.c_hi, (long long)n, M, dP.p, dV.p, dQ.p);
+    c.download(pts, dP);
+    c.download(valid, dV);
+    c.download(params, dQ);
+    return c.finish();
+}
+
+extern "C" int rovmpc_compute_catenary_3d(rovmpc_handle *h, const double *p0, const double *p1, double rope_length, int64_t n,
+                                          int32_t num_points, double *pts, double *a_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (n < 0 || num_points < 2 || (n > 0 && (!p0 || !p1 || !pts))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_compute_catenary_3d: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dA = c.upload(p0, (size_t)n * 3);
+    const auto dB = c.upload(p1, (size_t)n * 3);
+    const auto dP = c.buffer<double>((size_t)n * num_points * 3);
+    const auto dQ = c.buffer<double>((size_t)n);
+    if (c.ok())
+        hipLaunchKernelGGL(catenary_3d_kernel, dim3(grid_for(n, 128)), dim3(128), 0, h->stream, dA.p, dB.p, rope_length,
+                           (long long)n, num_points, dP.p, dQ.p);
+    c.download(pts, dP);
+    c.download(a_out, dQ);
+    return c.finish();
+}
+
+extern "C" int rovmpc_transform_catenary(rovmpc_handle *h, const double *A, const double *B, const double *theta,
+                                         const double *gamma, double L, int64_t n, int32_t M, double *out, int32_t *npts,
+                                         double *z_low) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (n < 0 || M < 2 || (n > 0 && (!A || !B || !theta || !gamma || !out || !npts)))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_transform_catenary: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dA = c.upload(A, (size_t)n * 3);
+    const auto dB = c.upload(B, (size_t)n * 3);
+    const auto dt = c.upload(theta, (size_t)n);
+    const auto dg = c.upload(gamma, (size_t)n);
+    const auto dO = c.buffer<double>((size_t)4 * n * M * 3);
+    const auto dN = c.buffer<int32_t>((size_t)n * 2);
+    const auto dZ = c.buffer<double>((size_t)n);
+    const double up = h->cfg.frame == ROVMPC_ENU ? 1.0 : -1.0;
+    if (c.ok())
+        hipLaunchKernelGGL(transform_catenary_kernel, dim3(grid_for(n, 128)), dim3(128), 0, h->stream, dA.p, dB.p, dt.p, dg.p, L, up,
+                           h->cfg.c_lo, h->cfg.c_hi, (long long)n, M, dO.p, dN.p, dZ.p);
+    c.download(out, dO);
+    c.download(npts, dN);
+    c.download(z_low, dZ);
+    return c.finish();
+}
+
+extern "C" int rovmpc_velocity_transform(rovmpc_handle *h, const double *R, const double *v, int64_t n, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (n < 0 || (n > 0 && (!R || !v || !out))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_velocity_transform: bad argument");
+    if (n == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dR = c.upload(R, (size_t)n * 9);
+    const auto dv = c.upload(v, (size_t)n * 3);
+    const auto dout = c.buffer<double>((size_t)n * 3);
+    if (c.ok())
+        hipLaunchKernelGGL(velocity_transform_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dR.p, dv.p, (long long)n, dout.p);
+    c.download(out, dout);
+    return c.finish();
+}
+
+extern "C" int rovmpc_extract_features(rovmpc_handle *h, const double *P0, const double *P1, const double *V1, const double *time,
+                                       const double *theta, const double *gamma, int64_t T, int32_t with_prev, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (T < 2 || !P0 || !P1 || !V1 || !time || !theta || !gamma || !out)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_extract_features: bad argument (np.gradient needs at least 2 rows)");
+    HelperCall c(h);
+    const int F = with_prev ? 18 : 16;
+    const auto d0 = c.upload(P0, (size_t)T * 3);
+    const auto d1 = c.upload(P1, (size_t)T * 3);
+    const auto dv = c.upload(V1, (size_t)T * 3);
+    const auto dt = c.upload(time, (size_t)T);
+    const auto dth = c.upload(theta, (size_t)T);
+    const auto dga = c.upload(gamma, (size_t)T);
+    const auto dout = c.buffer<double>((size_t)T * F);
+    if (c.ok())
+        hipLaunchKernelGGL(extract_features_kernel, dim3(grid_for(T, 256)), dim3(256), 0, h->stream, d0.p, d1.p, dv.p, dt.p, dth.p,
+                           dga.p, (long long)T, with_prev, dout.p);
+    c.download(out, dout);
+    return c.finish();
+}
+
+// Hat matrix of the least-squares polynomial fit of degree `order` on `window` equally spaced samples
+// (centred abscissae): H = Q Q^T with Q the orthonormalised monomials (modified Gram-Schmidt, twice).
+static void savgol_hat_matrix(int window, int order, std::vector<double> &H) {
+    const int w = window, m = order + 1, half = w / 2;
+    std::vector<long double> Q((size_t)w * m);
+    for (int c = 0; c < m; ++c) {
+        for (int r = 0; r < w; ++r) Q[(size_t)r * m + c] = powl((long double)(r - half), c);
+        for (int pass = 0; pass < 2; ++pass)
+            for (int p = 0; p < c; ++p) {
+                long double d = 0;
+                for (int r = 0; r < w; ++r) d += Q[(size_t)r * m + c] * Q[(size_t)r * m + p];
+                for (int r = 0; r < w; ++r) Q[(size_t)r * m + c] -= d * Q[(size_t)r * m + p];
+            }
+        long double n = 0;
+        for (int r = 0; r < w; ++r) n += Q[(size_t)r * m + c] * Q[(size_t)r * m + c];
+        n = sqrtl(n);
+        for (int r = 0; r < w; ++r) Q[(size_t)r * m + c] /= n;
+    }
+    H.assign((size_t)w * w, 0.0);
+    for (int i = 0; i < w; ++i)
+        for (int j = 0; j < w; ++j) {
+            long double s = 0;
+            for (int c = 0; c < m; ++c) s += Q[(size_t)i * m + c] * Q[(size_t)j * m + c];
+            H[(size_t)i * w + j] = (double)s;
+        }
+}
+
+extern "C" int rovmpc_features_dd(rovmpc_handle *h, const double *P0_mm, const double *P1_mm, const double *V_mm, const double *time,
+                                  const double *theta, const double *gamma, int64_t T, int32_t window, int32_t polyorder,
+                                  double *features, double *targets) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (!P0_mm || !P1_mm || !V_mm || !time || !theta || !gamma || !features)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_features_dd: null argument");
+    if (window < 3 || window > 255 || window % 2 == 0 || polyorder < 0 || polyorder >= window)
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_features_dd: window must be odd in 3..255 and polyorder < window (got %d, %d)", window, polyorder);
+    if (T < window) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_features_dd: %lld rows, fewer than the smoothing window %d (savgol_filter mode='interp')", (long long)T, window);
+    std::vector<double> H;
+    savgol_hat_matrix(window, polyorder, H);
+    HelperCall c(h);
+    const auto d0 = c.upload(P0_mm, (size_t)T * 3);
+    const auto d1 = c.upload(P1_mm, (size_t)T * 3);
+    const auto dv = c.upload(V_mm, (size_t)T * 3);
+    const auto dt = c.upload(time, (size_t)T);
+    const auto dth = c.upload(theta, (size_t)T);
+    const auto dga = c.upload(gamma, (size_t)T);
+    const auto dW = c.upload((const double *)H.data(), H.size());
+    // pass 2: [dtheta, dgamma, a_sway, a_surge, a_x, a_y, a_z] <- gradients of pass-1 columns (main_fun.py:825-847);
+    // pass 3: targets [ddtheta, ddgamma] <- gradients of columns 2, 3 (:835-836)
+    const int pairs[] = {0, 2, 1, 3, 4, 6, 5, 7, 8, 11, 9, 12, 10, 13, /* pass 3 */ 2, 0, 3, 1};
+    const auto dpairs = c.upload(pairs, sizeof(pairs) / sizeof(pairs[0]));
+    const auto dF = c.buffer<double>((size_t)T * 14);
+    const auto dY = c.buffer<double>((size_t)T * 2);
+    const dim3 grid(grid_for(T, 256)), block(256);
+    if (c.ok()) {
+        hipLaunchKernelGGL(features_dd_pass1_kernel, grid, block, 0, h->stream, d0.p, d1.p, dv.p, dth.p, dga.p, dW.p, window,
+                           (long long)T, dF.p);
+        hipLaunchKernelGGL(gradient_columns_kernel, grid, block, 0, h->stream, (const double *)dF.p, 14, dF.p, 14, dt.p,
+                           (long long)T, 7, (const int *)dpairs.p);
+        hipLaunchKernelGGL(gradient_columns_kernel, grid, block, 0, h->stream, (const double *)dF.p, 14, dY.p, 2, dt.p,
+                           (long long)T, 2, (const int *)dpairs.p + 14);
+    }
+    c.download(features, dF);
+    c.download(targets, dY);
+    return c.finish();
+}
+
+extern "C" int rovmpc_gaussian_filter1d(rovmpc_handle *h, const double *x, int64_t T, double sigma, double truncate, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (T < 1 || !x || !out || !(sigma > 0) || !(truncate > 0))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_gaussian_filter1d: bad argument");
+    const int radius = (int)(truncate * sigma + 0.5);                  // scipy/ndimage/_filters.py gaussian_filter1d
+    if (radius > 4096) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_gaussian_filter1d: kernel radius %d too large", radius);
+    std::vector<double> w(radius + 1);
+    double sum = 0.0;
+    for (int k = -radius; k <= radius; ++k) sum += exp(-0.5 / (sigma * sigma) * (double)k * (double)k);
+    for (int k = 0; k <= radius; ++k) w[k] = exp(-0.5 / (sigma * sigma) * (double)k * (double)k) / sum;
+    HelperCall c(h);
+    const auto dx = c.upload(x, (size_t)T);
+    const auto dw = c.upload((const double *)w.data(), w.size());
+    const auto dout = c.buffer<double>((size_t)T);
+    if (c.ok())
+        hipLaunchKernelGGL(gaussian_filter1d_kernel, dim3(grid_for(T, 256)), dim3(256), 0, h->stream, dx.p, (long long)T, dw.p,
+                           radius, dout.p);
+    c.download(out, dout);
+    return c.finish();
+}
+
+extern "C" int rovmpc_kabsch_velocity_transform(rovmpc_handle *h, const double *P, const double *Q, const double *v, int64_t T,
+                                                int32_t M, int32_t batch_gates, double *v_out, double *R_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    if (T < 0 || M < 1 || M > 4096 || (T > 0 && (!P || !Q || !v || !v_out)))
+        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_kabsch_velocity_transform: bad argument");
+    if (T == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const auto dP = c.upload(P, (size_t)T * M * 3);
+    const auto dQ = c.upload(Q, (size_t)T * M * 3);
+    const auto dv = c.upload(v, (size_t)T * 3);
+    const auto dout = c.buffer<double>((size_t)T * 3);
+    const auto dR = c.buffer<double>((size_t)T * 9);
+    if (c.ok())
+        hipLaunchKernelGGL(kabsch_kernel, dim3(grid_for(T, 128)), dim3(128), 0, h->stream, dP.p, dQ.p, dv.p, (long long)T, M,
+                           batch_gates, dout.p, R_out ? dR.p : nullptr);
+    c.download(v_out, dout);
+    c.download(R_out, dR);
+    return c.finish();
+}

@@ -1,219 +1,20 @@
 // rovmpc.hip -- C ABI (include/rovmpc.h) over the HIP kernels.  gfx950 only, no torch types.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <string>
-#include <vector>
+#include "rovmpc_internal.h"
 
 #include <hip/hiprtc.h>
-#include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <map>
-#include <mutex>
-#include <thread>
 
-#include "util_kernels.h"
+#include "mppi_kernels.h"
 #include "cem_kernels.h"
 #include "proposal_kernels.h"
 #include "nav_kernels.h"
 #include "tether_kernels.h"
+#include "comm_kernels.h"
 #include "embedded_sources.inc"
 
-using namespace rovmpc;
-
-static thread_local std::string g_create_error;
-
-// Where the kernel that ends a step leaves its results for the host: a block of doubles in mapped host memory and, behind
-// it, the sequence word that kernel releases at system scope and the host spins on (mailbox_wait).
-struct Mailbox {
-    double *h_out = nullptr, *d_out = nullptr;
-    unsigned long long *h_done = nullptr, *d_done = nullptr;
-    unsigned long long seq = 0;                  // last sequence number handed out
-};
-
-// Partial results of an update kernel's workgroups and the ticket word its last workgroup re-arms (zeroed once): the set of
-// rovmpc_*_update_device; a controller keeps one per problem in its PlanCtl.
-struct Slab { void *rows = nullptr; unsigned *ticket = nullptr; };
-
-// What a controller that iterates on a plan (MPPI: the nominal; CEM: mean and spread) owns, for B problems side by side (every
-// per-problem array the one-problem array repeated B times): candidate tensors, costs, states and records of its own (the
-// other entry points' buffers are never touched), the plans double-buffered by iteration, the update's slabs and tickets
-// and the mailbox [B][row] of its step.  Made at rovmpc_*_reset_batch, again when B changes.  `single`: the one-problem
-// controller of rovmpc_*_reset / _step, made at its first reset with B = 1; state and seed reach its sampler as kernel
-// arguments, so it has no staging block and no seeds.
-struct PlanCtl {
-    const char *name, *abi;                      // "MPPI", "mppi": for the messages
-    bool single;
-    int B = 0;                                   // 0: no reset yet
-    void *U = nullptr, *J = nullptr;             // T [B][K][N][3], T [B][K]
-    double *state = nullptr, *record = nullptr;  // [B][16], [B][result_len]
-    unsigned long long *seeds = nullptr;         // [B]: kept by the first sampler of a step for the later ones (batched)
-    double *plan = nullptr, *spread = nullptr;   // [2][B][3N] each; spread: CEM only
-    int cur = 0;                                 // half of plan (and spread) holding the handle's
-    void *slab = nullptr;                        // [B] slabs of slab_stride 64-bit words
-    unsigned *tickets = nullptr;                 // [B] of the problems' updates, then the step's
-    size_t slab_stride = 0, row = 0;             // row: 64-bit words per problem of the mailbox
-    double *h_stage = nullptr, *d_stage = nullptr;   // mapped: states [B][16], seeds [B] of the step being enqueued (batched)
-    Mailbox box;                                 // [B][row]
-    unsigned long long steps = 0;
-};
-
-struct rovmpc_handle {
-    rovmpc_config cfg;
-    hipStream_t stream = nullptr;
-    std::string err;
-    // model
-    bool has_model = false, builtin = false;
-    int model_kind = MODEL_INTERP;   // MODEL_BUILTIN | MODEL_INTERP | MODEL_JIT
-    hipFunction_t jit_fn = nullptr;  // MODEL_JIT: kernel of the run-time specialised module
-    int jit_ckc = 0;                 // candidates per workgroup the module was specialised for (0: run-time)
-    hipFunction_t jit_fn_step = nullptr;   //            its pipelined closed-loop step entry
-    int jit_gi = 0, jit_ts = 0;            //            structure found in the rows (ROVMPC_JIT_GI / ROVMPC_JIT_TS of rollout_kernels.h)
-    hipStream_t pipe_streams[2] = {nullptr, nullptr};     // pipelined closed loop: launches alternate between the two
-    bool pipe_placed = false, pipe_stream_owned = false;  // [1] probed against the caller's stream; replaced by one of the handle's own
-    std::string pipe_placement;
-    hipEvent_t pipe_ev[3] = {nullptr, nullptr, nullptr};
-    // closed loop with GPU-side hand-off (pipelined form): sequence words [2] + state ring [4][4] in one block,
-    // and the granule / trajectory hand-off buffers by step parity
-    unsigned long long *d_step_seq = nullptr;
-    unsigned long long *d_cl_granules = nullptr;
-    double *d_cl_blk_traj = nullptr;
-    int cl_form = 0;                 // form of the last closed-loop call (rovmpc_closed_loop_form)
-    int n_feat = 0;
-    double mean[ROVMPC_MAX_FEATURES], scale[ROVMPC_MAX_FEATURES];
-    int n_th = 0, n_ga = 0, n_consts = 0;
-    unsigned used_planes = 0xffffffffu;   // exogenous planes read by the loaded expressions
-    int32_t *d_code_th = nullptr, *d_code_ga = nullptr;
-    void *d_consts = nullptr;        // T
-    double *d_consts64 = nullptr;    // double (utility kernels)
-    void *d_Rtab = nullptr;          // T [N][9]
-    void *d_k = nullptr;             // RolloutConsts<T>
-    bool has_rtab = false;
-    // launch geometry / workspace
-    int CK = 0, nblocks = 0, NT = 0;
-    int n_cu = 256;                  // compute units of the device (multiProcessorCount)
-    size_t lds_bytes = 0, esz = 8;
-    void *d_U = nullptr, *d_J = nullptr, *d_traj_all = nullptr;
-    double *d_state = nullptr, *d_blk_traj = nullptr, *d_result = nullptr;
-    unsigned long long *d_granules = nullptr;  // [gran_stride(max_blocks, N)] tagged hand-off granules: costs, then best trajectories
-    unsigned *epoch_ctr = nullptr;            // launches issued (host counter; tag of the next launch = ++*epoch_ctr, never 0)
-    unsigned long long *d_stamps = nullptr;   // diagnostic library only
-    void *d_gtab = nullptr;                   // shared gamma table of a launch (long horizons) + its epoch tag behind it
-    const unsigned long long *arg_flag_consumed = nullptr;   // hand-off flags of the step being enqueued (native collective)
-    unsigned long long *arg_flag_rolled = nullptr;
-    unsigned long long arg_consumed_need = 0, arg_rolled_seq = 0;
-    unsigned long long *arg_slot_bad = nullptr;
-    int arg_inject = 0;
-    // error word: pinned host memory mapped into the device (ERR_* bits of rollout_kernels.h), raised at system scope by
-    // the kernels' give-up paths, read and cleared by rovmpc_comm_sync / rovmpc_device_status
-    unsigned *h_err = nullptr, *d_err = nullptr;
-    double handoff_timeout_ms = 10000.0;      // give-up time of the GPU-side hand-off waits (rovmpc_set_option)
-    int inject_skip_rolled = 0, inject_skip_consumed = 0;   // test hooks: the next N steps lose that publication
-    // rovmpc_mpc_step_sampled: two candidate tensors (the sampler of step s+1 reads the winner of step s for the warm
-    // start) and the mailbox of the record (its sequence numbers are samp_steps)
-    void *d_Us[2] = {nullptr, nullptr};
-    Mailbox samp_box;
-    unsigned long long samp_steps = 0;
-    double *d_best = nullptr;                    // [2][N][3]: winner's sequence of the last fused-sampling steps, by step parity
-    unsigned long long *d_blk_u = nullptr;       // [max_blocks][6 N] tagged granules + [max_blocks][3 N] doubles: per-workgroup best controls of a fused-sampling step
-    // what the last sampled step drew with (rovmpc_sampled_candidates re-draws the tensor for inspection)
-    unsigned long long last_seed = 0, last_step = 0; double last_mean[3] = {}, last_std[3] = {}; int last_warm = 0; bool last_fused = false;
-    double *arg_result_host = nullptr; unsigned long long *arg_done_flag = nullptr; unsigned long long arg_done_seq = 0;
-    void *arg_J = nullptr;                       // costs of the launch being enqueued go here instead of d_J (null: d_J)
-    // MPPI (rovmpc_mppi_*): mailbox [record, nu*, stats]; CEM (rovmpc_cem_*): [record, mu*, sigma*, stats, elite list]
-    PlanCtl mppi{"MPPI", "mppi", true}, cem{"CEM", "cem", true};
-    PlanCtl mppi_b{"MPPI", "mppi", false}, cem_b{"CEM", "cem", false};
-    Slab mppi_slab_x, cem_slab_x;                // of rovmpc_*_update_device (allocated at its first call)
-    // shaping of the controllers' proposal (rovmpc_set_noise_correlation, rovmpc_mppi_set_bounds); the defaults launch the
-    // white samplers and the unbounded update
-    double prop_beta[3] = {0.0, 0.0, 0.0}, prop_root[3] = {1.0, 1.0, 1.0};    // root = sqrt((1 - beta)(1 + beta))
-    double mppi_lo[3] = {-INFINITY, -INFINITY, -INFINITY}, mppi_hi[3] = {INFINITY, INFINITY, INFINITY};
-    bool prop_colored = false, mppi_boxed = false;
-    // navigation cost of the controllers (rovmpc_set_nav_cost): the setting, its tracks [nav_Bt][nav_Tr][3] and spheres
-    // [ROVMPC_NAV_MAX_SPHERES][4] in device memory; unset: nav_cost_kernel is not launched
-    bool nav_on = false;
-    rovmpc_nav_cost nav = {};
-    double *d_nav_track = nullptr, *d_nav_spheres = nullptr;
-    size_t nav_track_cap = 0;                    // doubles allocated behind d_nav_track
-    int nav_Bt = 0; long long nav_Tr = 0;
-    // tether keep-out cost of the controllers (rovmpc_set_tether_cost): the setting, its spheres in device memory and the
-    // buffer [tether_cap][K][N+1][2] the rollout stores its trajectories in; unset: tether_cost_kernel is not launched and
-    // the rollout gets no trajectory buffer
-    bool tether_on = false;
-    rovmpc_tether_cost tether = {};
-    double *d_tether_spheres = nullptr;
-    void *d_tether_traj = nullptr;
-    int tether_cap = 0;                          // problems d_tether_traj holds
-    // batched launches: workspace for `batch_cap` problems
-    int batch_cap = 0, last_batch = 1;
-    void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
-    const double *plant_next = nullptr;       // closed loop: plant update fused into the step being enqueued
-    double *plant_state = nullptr;
-    int plant_feedback = 0;
-    double *h_result = nullptr;      // pinned
-    // native collective (rovmpc_comm_*)
-    ncclComm_t comm = nullptr;
-    int comm_rank = 0, comm_world = 0, comm_flip = 0;
-    static constexpr int NSLOT = 4;       // collectives in flight (RCCL's small all-reduce is ~2 rollouts long)
-    // Several communicators (each with a high-priority stream of its own), used round-robin by the slots:
-    // collectives on one communicator serialise, and a latency-bound 3 KB all-reduce over 8 GPUs lasts longer than a
-    // rollout -- with more than one communicator the collectives of consecutive steps overlap each other as well as
-    // the rollouts.  Three by default: with the caller's stream that is four hardware queues, the runtime's default
-    // limit (a fifth stream was measured to cost 80 us per step).  comms[0] == comm.
-    static constexpr int NCOMM_MAX = 3;
-    ncclComm_t comms[NCOMM_MAX] = {};
-    hipStream_t comm_streams[NCOMM_MAX] = {};
-    int ncomm = 0;
-    bool comm_placed = false;             // place_comm_streams has run (first rovmpc_step_device_allreduce)
-    bool comm_aborted = false;            // rovmpc_comm_abort: no further collective is issued (guarded by comm_call_mu)
-    std::mutex comm_call_mu;              // the worker's [aborted? -> ncclAllReduce] against rovmpc_comm_abort
-    std::string comm_placement;           // what it found (rovmpc_get_info "comm_placement")
-    // GPU-side hand-off between the caller's stream and the collective streams (no events on the caller's stream:
-    // an event record costs ~3 us and a cross-stream wait ~6 us of its timeline per step, measured):
-    // rolled[p] = uses of slot p whose rollout has published its row; consumed[p] = uses whose select has read it.
-    unsigned long long *d_flags = nullptr;             // [3][NSLOT]: rolled, consumed, bad use
-    unsigned long long slot_uses[NSLOT] = {};
-    long long *d_slots[NSLOT] = {};
-    hipEvent_t ev_selected[NSLOT] = {};   // recorded at rovmpc_comm_join, one per collective stream
-    bool slot_used[NSLOT] = {};
-    // the collective is enqueued by a worker thread so its host cost (ncclAllReduce is ~20 us of
-    // host time per call) overlaps the enqueue of the next rollout
-    struct CommJob { int p; double *d_result; unsigned long long use; int c; int inject;
-                     double *ring; unsigned long long *seq_theta; long long step_next; };     // (closed loop: the select hands theta over)
-    unsigned long long comm_rr = 0;       // steps issued: communicator of a step = comm_rr % ncomm (same on every rank)
-    std::thread comm_thread;
-    std::mutex comm_mu;
-    std::condition_variable comm_cv;
-    std::deque<CommJob> comm_q;
-    unsigned long long comm_submitted[NSLOT] = {}, comm_done[NSLOT] = {};
-    bool comm_stop = false;
-    std::string comm_err;
-    // timing
-    std::vector<hipEvent_t> ev;
-    int ev_used = 0;
-    bool timing = false;
-};
-
-#define FAIL(h, code, ...)                                        \
-    do {                                                          \
-        char _b[512];                                             \
-        snprintf(_b, sizeof(_b), __VA_ARGS__);                    \
-        if (h) (h)->err = _b; else g_create_error = _b;           \
-        return (code);                                            \
-    } while (0)
-
-#define HIPCHK(h, call)                                                                     \
-    do {                                                                                    \
-        hipError_t _e = (call);                                                             \
-        if (_e != hipSuccess)                                                               \
-            FAIL(h, ROVMPC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e),  \
-                 __FILE__, __LINE__);                                                       \
-    } while (0)
+thread_local std::string g_create_error;
 
 extern "C" const char *rovmpc_version(void) { return "rovmpc 0.1 (gfx950)"; }
 
@@ -405,8 +206,7 @@ static const char *configure_geometry(rovmpc_handle *h, int model, bool strict =
 
 
 // Geometry of one launch: B problems of K candidates each in the grid (B = 1: the handle's own geometry).
-struct Geo { int CK, NT, nblocks; };
-static Geo launch_geometry(const rovmpc_handle *h, int B) {
+Geo launch_geometry(const rovmpc_handle *h, int B) {
     Geo g{h->CK, h->NT, h->nblocks};
     const rovmpc_config *cfg = &h->cfg;
     if (B > 1 && h->model_kind == MODEL_BUILTIN && cfg->candidates_per_block == 0 && cfg->threads_per_block == 0) {
@@ -529,8 +329,6 @@ extern "C" int rovmpc_create(const rovmpc_config *cfg, rovmpc_handle **out) {
     *out = h;
     return ROVMPC_OK;
 }
-
-extern "C" int rovmpc_comm_destroy(rovmpc_handle *h);
 
 extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     if (!h) return;
@@ -790,7 +588,7 @@ static std::string jit_source(const rovmpc_handle *h, const int32_t *code_th, in
 // ---- model ---------------------------------------------------------------------------------
 
 // Static validation: opcodes known, indices in range, stack discipline, final depth 1.
-static const char *validate_code(const int32_t *code, int n, int n_feat, int n_consts) {
+const char *validate_code(const int32_t *code, int n, int n_feat, int n_consts) {
     if (n < 1 || n > ROVMPC_MAX_CODE) return "program length out of range";
     int sp = 0;
     for (int pc = 0; pc < n; ++pc) {
@@ -972,7 +770,7 @@ extern "C" int rovmpc_set_rotation_table(rovmpc_handle *h, const double *R) {
 
 // ---- launches -------------------------------------------------------------------------------
 
-template <typename T> static void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, const double *d_state,
+template <typename T> void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, const double *d_state,
                                             const void *d_U, void *d_traj_all, const Geo &g, int B) {
     const rovmpc_config &c = h->cfg;
     a.U = (const T *)d_U; a.state = d_state; a.k = (const RolloutConsts<T> *)h->d_k;
@@ -1007,6 +805,8 @@ template <typename T> static void fill_args(const rovmpc_handle *h, RolloutArgs<
     a.gtab = (B == 1 && !no_gtab) ? (T *)h->d_gtab : nullptr;
     a.gtab_tag = B == 1 ? (unsigned long long *)((char *)h->d_gtab + (size_t)8 * (c.N + 1) * 8) : nullptr;
 }
+template void fill_args<double>(const rovmpc_handle *, RolloutArgs<double> &, const double *, const void *, void *, const Geo &, int);
+template void fill_args<float>(const rovmpc_handle *, RolloutArgs<float> &, const double *, const void *, void *, const Geo &, int);
 
 template <typename T, int MODEL, int VT>
 static hipError_t launch_one(const rovmpc_handle *h, const RolloutArgs<T> &a, int B, hipStream_t s) {
@@ -1076,7 +876,7 @@ template <typename T> static hipError_t launch_rollout_t(const rovmpc_handle *h,
     return launch_one<T, MODEL_INTERP, 2>(h, a, B, s);
 }
 
-static int check_ready(rovmpc_handle *h) {
+int check_ready(rovmpc_handle *h) {
     if (!h->has_model) FAIL(h, ROVMPC_ERR_NO_MODEL, "rovmpc_set_model has not been called");
     const int want = h->cfg.feature_map == ROVMPC_FEATURES_GEN2 ? 17 : h->cfg.feature_map == ROVMPC_FEATURES_GEN3 ? 14 : 18;
     if (h->n_feat != want)
@@ -1086,8 +886,8 @@ static int check_ready(rovmpc_handle *h) {
     return ROVMPC_OK;
 }
 
-static int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, void *d_traj_all, double *d_result,
-                        long long k_offset, long long *d_slots, int rank, int world, hipStream_t s, int B = 1) {
+int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, void *d_traj_all, double *d_result,
+                        long long k_offset, long long *d_slots, int rank, int world, hipStream_t s, int B) {
     int rc = check_ready(h);
     if (rc) return rc;
     const bool time_it = h->timing && h->ev_used + 2 <= (int)h->ev.size();
@@ -1151,7 +951,17 @@ extern "C" int rovmpc_batch_costs_device(rovmpc_handle *h, const void **d_J) {
     return ROVMPC_OK;
 }
 
-static int take_device_errors(rovmpc_handle *h);
+// Error word of the handle (non-blocking): 0 = nothing raised; otherwise ROVMPC_ERR_HIP with the reason, and the word is
+// cleared.  Only meaningful for work the host has already synchronised with.
+static int take_device_errors(rovmpc_handle *h) {
+    if (!h->h_err) return ROVMPC_OK;
+    const unsigned e = __atomic_exchange_n(h->h_err, 0u, __ATOMIC_ACQ_REL);
+    if (!e) return ROVMPC_OK;
+    FAIL(h, ROVMPC_ERR_HIP, "GPU-side hand-off gave up:%s%s%s -- the affected step's record carries a NaN cost",
+         (e & ERR_WAIT_ROLLED) ? " [a collective never saw its rollout's row]" : "",
+         (e & ERR_CONSUMED) ? " [a rollout never saw the select that frees its slot row]" : "",
+         (e & ERR_SWEEP) ? " [the arg-min sweep never saw a workgroup's record]" : "");
+}
 
 // ---- MPC.step with the candidates drawn on the GPU: one call, no copies on the step path ---------------------------
 static int ensure_sampler(rovmpc_handle *h) {
@@ -1175,7 +985,7 @@ static int mailbox_wait(rovmpc_handle *h, const Mailbox &m, unsigned long long s
     }
 }
 
-static int launched(rovmpc_handle *h, const char *what) {
+int launched(rovmpc_handle *h, const char *what) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
     return ROVMPC_OK;
@@ -1311,18 +1121,6 @@ extern "C" int rovmpc_sampled_candidates(rovmpc_handle *h, void *U_out) {
     }
     HIPCHK(h, hipMemcpy(U_out, h->d_Us[cur], (size_t)h->cfg.K * h->cfg.N * 3 * h->esz, hipMemcpyDeviceToHost));
     return ROVMPC_OK;
-}
-
-// Error word of the handle (non-blocking): 0 = nothing raised; otherwise ROVMPC_ERR_HIP with the reason, and the word is
-// cleared.  Only meaningful for work the host has already synchronised with.
-static int take_device_errors(rovmpc_handle *h) {
-    if (!h->h_err) return ROVMPC_OK;
-    const unsigned e = __atomic_exchange_n(h->h_err, 0u, __ATOMIC_ACQ_REL);
-    if (!e) return ROVMPC_OK;
-    FAIL(h, ROVMPC_ERR_HIP, "GPU-side hand-off gave up:%s%s%s -- the affected step's record carries a NaN cost",
-         (e & ERR_WAIT_ROLLED) ? " [a collective never saw its rollout's row]" : "",
-         (e & ERR_CONSUMED) ? " [a rollout never saw the select that frees its slot row]" : "",
-         (e & ERR_SWEEP) ? " [the arg-min sweep never saw a workgroup's record]" : "");
 }
 
 extern "C" int rovmpc_device_status(rovmpc_handle *h) {
@@ -1506,9 +1304,20 @@ static int plan_batch_ready(rovmpc_handle *h, PlanCtl &c, const char *fn, int B,
 
 struct ProposalTile { int rows, stride; };
 
+// A tile is `rows` whole candidates, a multiple of 4: about one Philox block per thread (rows 3N <= 1024 elements), one
+// phase-2 thread per (row, channel) (3 rows <= PROPOSAL_NT), 4 rows where a row alone is longer.  A tile row takes `stride`
+// doubles of LDS, 3N padded up to 3 mod 32 (the bank rule of phase 2): at most 4 x 1027 doubles, 33 KB, per workgroup.
+static ProposalTile proposal_tile(int N) {
+    const int row3 = 3 * N;
+    int rows = 1024 / row3;
+    if (rows > PROPOSAL_NT / 3) rows = PROPOSAL_NT / 3;
+    rows &= ~3;
+    if (rows < 4) rows = 4;
+    return {rows, row3 + ((3 - row3 % 32) + 32) % 32};
+}
+
 // ---- the navigation cost (nav_kernels.h): C_k of the vehicle's predicted path added to J between rollout and update ----
 // One launch for B problems on the tile of the shaped sampler; track_stride: doubles between the problems' tracks.
-static ProposalTile proposal_tile(int N);
 
 static int launch_nav_cost(rovmpc_handle *h, const double *d_state, const void *d_U, void *d_J, double *d_C, uint64_t step, int B,
                            size_t track_stride, hipStream_t s) {
@@ -1774,18 +1583,6 @@ template <typename BA, typename A> static BA plan_batch_args(const A &a, const P
     } while (0)
 
 // ---- the shaped proposal (proposal_kernels.h): AR(1) noise along the horizon and a box, for MPPI and CEM alike --------
-// A tile is `rows` whole candidates, a multiple of 4: about one Philox block per thread (rows 3N <= 1024 elements), one
-// phase-2 thread per (row, channel) (3 rows <= PROPOSAL_NT), 4 rows where a row alone is longer.  A tile row takes `stride`
-// doubles of LDS, 3N padded up to 3 mod 32 (the bank rule of phase 2): at most 4 x 1027 doubles, 33 KB, per workgroup.
-static ProposalTile proposal_tile(int N) {
-    const int row3 = 3 * N;
-    int rows = 1024 / row3;
-    if (rows > PROPOSAL_NT / 3) rows = PROPOSAL_NT / 3;
-    rows &= ~3;
-    if (rows < 4) rows = 4;
-    return {rows, row3 + ((3 - row3 % 32) + 32) % 32};
-}
-
 // The draw around `mean` with spread `sigma` (null: std3 on every node) inside [lo3, hi3], for c's problems
 static int launch_proposal_sample(rovmpc_handle *h, const PlanCtl &c, const PlanIter &it, const double *std3, const double *lo3,
                                   const double *hi3, const double *mean, const double *sigma, const char *what) {
@@ -2232,310 +2029,6 @@ extern "C" int rovmpc_timing_read(rovmpc_handle *h, double *avg_ms, double *min_
     return ROVMPC_OK;
 }
 
-// ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <typename T> T *as() { return (T *)p; }
-};
-
-#define UPLOAD(h, buf, src, bytes)                                                               \
-    do {                                                                                         \
-        HIPCHK(h, (buf).alloc(bytes));                                                           \
-        HIPCHK(h, hipMemcpyAsync((buf).p, (src), (bytes), hipMemcpyHostToDevice, (h)->stream));  \
-    } while (0)
-
-static inline int grid_for(long long n, int bs) { return (int)((n + bs - 1) / bs); }
-
-extern "C" int rovmpc_predict(rovmpc_handle *h, const double *Xs, int64_t n, int32_t which, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!h->has_model) FAIL(h, ROVMPC_ERR_NO_MODEL, "rovmpc_set_model has not been called");
-    if (n < 0 || (n > 0 && (!Xs || !out)) || which < 0 || which > 1) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_predict: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dX, dO;
-    UPLOAD(h, dX, Xs, (size_t)n * h->n_feat * sizeof(double));
-    HIPCHK(h, dO.alloc((size_t)n * sizeof(double)));
-    const int bs = 256;
-    hipLaunchKernelGGL(predict_kernel, dim3(grid_for(n, bs)), dim3(bs), ROVMPC_MAX_STACK * bs * sizeof(double), h->stream,
-                       dX.as<double>(), (long long)n, h->n_feat, which == 0 ? h->d_code_th : h->d_code_ga,
-                       which == 0 ? h->n_th : h->n_ga, h->d_consts64, dO.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dO.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_eval_expression(rovmpc_handle *h, const int32_t *code, int32_t n_code, const double *consts, int32_t n_consts,
-                                      const double *X, int32_t F, int64_t n, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!code || n < 0 || F < 1 || F > ROVMPC_MAX_FEATURES || n_consts < 0 || n_consts > ROVMPC_MAX_CODE || (n_consts > 0 && !consts) ||
-        (n > 0 && (!X || !out)))
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_eval_expression: bad argument");
-    if (const char *why = validate_code(code, n_code, F, n_consts)) FAIL(h, ROVMPC_ERR_INVALID, "program: %s", why);
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dX, dO, dC, dK;
-    const double zero = 0.0;
-    UPLOAD(h, dX, X, (size_t)n * F * sizeof(double));
-    UPLOAD(h, dC, code, (size_t)n_code * sizeof(int32_t));
-    UPLOAD(h, dK, n_consts ? consts : &zero, (size_t)(n_consts ? n_consts : 1) * sizeof(double));
-    HIPCHK(h, dO.alloc((size_t)n * sizeof(double)));
-    const int bs = 256;
-    hipLaunchKernelGGL(predict_kernel, dim3(grid_for(n, bs)), dim3(bs), ROVMPC_MAX_STACK * bs * sizeof(double), h->stream,
-                       dX.as<double>(), (long long)n, (int)F, dC.as<int32_t>(), (int)n_code, dK.as<double>(), dO.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dO.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-template <typename T>
-static int math_probe_run(rovmpc_handle *h, int32_t fn, const double *x, const double *y, int64_t n, double *out0, double *out1) {
-    std::vector<T> hx(x, x + n), hy, ho((size_t)n), ho1;          // (plain conversion to T)
-    if (y) hy.assign(y, y + n);
-    DevBuf dX, dY, dO, dO1;
-    const size_t bytes = (size_t)n * sizeof(T);
-    UPLOAD(h, dX, hx.data(), bytes);
-    if (y) UPLOAD(h, dY, hy.data(), bytes);
-    HIPCHK(h, dO.alloc(bytes));
-    if (out1) HIPCHK(h, dO1.alloc(bytes));
-    hipLaunchKernelGGL(math_probe_kernel<T>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (int)fn, dX.as<T>(),
-                       y ? dY.as<T>() : (const T *)nullptr, (long long)n, dO.as<T>(), out1 ? dO1.as<T>() : (T *)nullptr);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(ho.data(), dO.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (out1) { ho1.resize((size_t)n); HIPCHK(h, hipMemcpyAsync(ho1.data(), dO1.p, bytes, hipMemcpyDeviceToHost, h->stream)); }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t i = 0; i < n; ++i) out0[i] = (double)ho[i];
-    if (out1) for (int64_t i = 0; i < n; ++i) out1[i] = (double)ho1[i];
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_math_probe(rovmpc_handle *h, int32_t fn, int32_t dtype, const double *x, const double *y, int64_t n,
-                                 double *out0, double *out1) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    const bool two_in = fn == ROVMPC_PROBE_DIV || fn == ROVMPC_PROBE_DIVQ || fn == ROVMPC_PROBE_DIVX || fn == ROVMPC_PROBE_MIN_RAW;
-    if (fn < 0 || fn >= ROVMPC_PROBE_COUNT || (dtype != ROVMPC_F64 && dtype != ROVMPC_F32) || n < 0 || n > (int64_t)1 << 24 ||
-        (n > 0 && (!x || !out0 || (two_in && !y))))
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_math_probe: bad argument");
-    if (fn == ROVMPC_PROBE_SIN_BOUNDED)                      // the unchecked sine is undefined outside its limit
-        for (int64_t i = 0; i < n; ++i) {
-            const double v = dtype == ROVMPC_F32 ? (double)(float)x[i] : x[i];
-            if (!(fabs(v) < (dtype == ROVMPC_F32 ? (double)TRIGF_FAST_LIMIT : TRIG_FAST_LIMIT)))
-                FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_math_probe: input %lld (%g) is outside the bounded sine's domain", (long long)i, x[i]);
-        }
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!two_in) y = nullptr;
-    return dtype == ROVMPC_F32 ? math_probe_run<float>(h, fn, x, y, n, out0, out1) : math_probe_run<double>(h, fn, x, y, n, out0, out1);
-}
-
-extern "C" int rovmpc_lagrangian_rollout(rovmpc_handle *h, const int32_t *code_th, int32_t n_th, const int32_t *code_ga, int32_t n_ga,
-                                         const double *consts, int32_t n_consts, const double *time, int64_t T, const double *y0,
-                                         int64_t B, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!code_th || !code_ga || !time || !y0 || !out || T < 1 || B < 1 || n_consts < 0 || n_consts > ROVMPC_MAX_CODE || (n_consts > 0 && !consts))
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_lagrangian_rollout: bad argument");
-    const char *why;
-    if ((why = validate_code(code_th, n_th, 4, n_consts))) FAIL(h, ROVMPC_ERR_INVALID, "theta acceleration program: %s", why);
-    if ((why = validate_code(code_ga, n_ga, 4, n_consts))) FAIL(h, ROVMPC_ERR_INVALID, "gamma acceleration program: %s", why);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dCt, dCg, dK, dT, dY, dO;
-    const double zero = 0.0;
-    UPLOAD(h, dCt, code_th, (size_t)n_th * sizeof(int32_t));
-    UPLOAD(h, dCg, code_ga, (size_t)n_ga * sizeof(int32_t));
-    UPLOAD(h, dK, n_consts ? consts : &zero, (size_t)(n_consts ? n_consts : 1) * sizeof(double));
-    UPLOAD(h, dT, time, (size_t)T * sizeof(double));
-    UPLOAD(h, dY, y0, (size_t)B * 4 * sizeof(double));
-    HIPCHK(h, dO.alloc((size_t)4 * B * T * sizeof(double)));
-    const int bs = 64;
-    hipLaunchKernelGGL(lagrangian_rollout_kernel, dim3(grid_for(B, bs)), dim3(bs), (size_t)(4 + ROVMPC_MAX_STACK) * bs * sizeof(double), h->stream,
-                       dCt.as<int32_t>(), (int)n_th, dCg.as<int32_t>(), (int)n_ga, dK.as<double>(), dT.as<double>(), (long long)T,
-                       dY.as<double>(), (long long)B, dO.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dO.p, (size_t)4 * B * T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_replay(rovmpc_handle *h, const double *Xs, const double *time, int64_t T, double theta0, double gamma0,
-                             int32_t integrator, double *theta_out, double *gamma_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!h->has_model) FAIL(h, ROVMPC_ERR_NO_MODEL, "rovmpc_set_model has not been called");
-    if (T < 1 || !Xs || !time || integrator < ROVMPC_RK4 || integrator > ROVMPC_TRAPEZOID)
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_replay: bad argument");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dX, dT, dIt, dIg, dOt, dOg;
-    UPLOAD(h, dX, Xs, (size_t)T * h->n_feat * sizeof(double));
-    UPLOAD(h, dT, time, (size_t)T * sizeof(double));
-    HIPCHK(h, dIt.alloc((size_t)T * sizeof(double)));
-    HIPCHK(h, dIg.alloc((size_t)T * sizeof(double)));
-    HIPCHK(h, dOt.alloc((size_t)T * sizeof(double)));
-    HIPCHK(h, dOg.alloc((size_t)T * sizeof(double)));
-    if (integrator >= ROVMPC_DOUBLE_EULER) {
-        // second-derivative models: predict every row, then integrate twice
-        const int bs = 256;
-        for (int which = 0; which < 2; ++which) {
-            hipLaunchKernelGGL(predict_kernel, dim3(grid_for(T, bs)), dim3(bs), ROVMPC_MAX_STACK * bs * sizeof(double), h->stream,
-                               dX.as<double>(), (long long)T, h->n_feat, which == 0 ? h->d_code_th : h->d_code_ga,
-                               which == 0 ? h->n_th : h->n_ga, h->d_consts64, which == 0 ? dIt.as<double>() : dIg.as<double>());
-            HIPCHK(h, hipGetLastError());
-        }
-        hipLaunchKernelGGL(replay_second_order_kernel, dim3(1), dim3(64), 0, h->stream, dIt.as<double>(), dIg.as<double>(),
-                           dT.as<double>(), (long long)T, theta0, gamma0, integrator, dOt.as<double>(), dOg.as<double>());
-        HIPCHK(h, hipGetLastError());
-        if (theta_out) HIPCHK(h, hipMemcpyAsync(theta_out, dOt.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (gamma_out) HIPCHK(h, hipMemcpyAsync(gamma_out, dOg.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return ROVMPC_OK;
-    }
-    if (T > 1) {
-        const int bs = 128;
-        const size_t lds = (size_t)(h->n_feat + ROVMPC_MAX_STACK) * bs * sizeof(double);
-        hipLaunchKernelGGL(replay_increments_kernel, dim3(grid_for(T - 1, bs)), dim3(bs), lds, h->stream, dX.as<double>(),
-                           dT.as<double>(), (long long)T, h->n_feat, h->d_code_th, h->n_th, h->d_code_ga, h->n_ga,
-                           h->d_consts64, integrator, dIt.as<double>(), dIg.as<double>());
-        HIPCHK(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(replay_cumsum_kernel, dim3(1), dim3(64), 0, h->stream, dIt.as<double>(), dIg.as<double>(), (long long)T,
-                       theta0, gamma0, dOt.as<double>(), dOg.as<double>());
-    HIPCHK(h, hipGetLastError());
-    if (theta_out) HIPCHK(h, hipMemcpyAsync(theta_out, dOt.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (gamma_out) HIPCHK(h, hipMemcpyAsync(gamma_out, dOg.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_solve_catenary(rovmpc_handle *h, const double *l, const double *dH, double L, int64_t n, double *C_out,
-                                     double *T_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (n < 0 || (n > 0 && (!l || !dH || !C_out))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_solve_catenary: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dl, dh, dC, dT;
-    UPLOAD(h, dl, l, (size_t)n * sizeof(double));
-    UPLOAD(h, dh, dH, (size_t)n * sizeof(double));
-    HIPCHK(h, dC.alloc((size_t)n * sizeof(double)));
-    HIPCHK(h, dT.alloc((size_t)n * sizeof(double)));
-    hipLaunchKernelGGL(solve_catenary_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dl.as<double>(), dh.as<double>(), L,
-                       h->cfg.c_lo, h->cfg.c_hi, h->cfg.cable_wet_weight / L, (long long)n, dC.as<double>(),
-                       T_out ? dT.as<double>() : nullptr);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(C_out, dC.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (T_out) HIPCHK(h, hipMemcpyAsync(T_out, dT.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_rodrigues(rovmpc_handle *h, const double *v, const double *axis, const double *angle, int64_t n, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (n < 0 || (n > 0 && (!v || !axis || !angle || !out))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_rodrigues: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dv, da, dg, dout;
-    UPLOAD(h, dv, v, (size_t)n * 3 * sizeof(double));
-    UPLOAD(h, da, axis, (size_t)n * 3 * sizeof(double));
-    UPLOAD(h, dg, angle, (size_t)n * sizeof(double));
-    HIPCHK(h, dout.alloc((size_t)n * 3 * sizeof(double)));
-    hipLaunchKernelGGL(rodrigues_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dv.as<double>(), da.as<double>(),
-                       dg.as<double>(), (long long)n, dout.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dout.p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_catenary_points(rovmpc_handle *h, const double *A, const double *B, double L, int64_t n, int32_t M,
-                                      double *pts, int32_t *valid, double *params) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (n < 0 || M < 2 || (n > 0 && (!A || !B || !pts || !valid))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_catenary_points: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dA, dB, dP, dV, dQ;
-    UPLOAD(h, dA, A, (size_t)n * 3 * sizeof(double));
-    UPLOAD(h, dB, B, (size_t)n * 3 * sizeof(double));
-    HIPCHK(h, dP.alloc((size_t)n * M * 3 * sizeof(double)));
-    HIPCHK(h, dV.alloc((size_t)n * sizeof(int32_t)));
-    HIPCHK(h, dQ.alloc((size_t)n * 3 * sizeof(double)));
-    const double up = h->cfg.frame == ROVMPC_ENU ? 1.0 : -1.0;
-    hipLaunchKernelGGL(catenary_points_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dA.as<double>(), dB.as<double>(), L,
-                       up, h->cfg.c_lo, h->cfg.c_hi, (long long)n, M, dP.as<double>(), dV.as<int32_t>(), dQ.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(pts, dP.p, (size_t)n * M * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(valid, dV.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (params) HIPCHK(h, hipMemcpyAsync(params, dQ.p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_compute_catenary_3d(rovmpc_handle *h, const double *p0, const double *p1, double rope_length, int64_t n,
-                                          int32_t num_points, double *pts, double *a_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (n < 0 || num_points < 2 || (n > 0 && (!p0 || !p1 || !pts))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_compute_catenary_3d: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dA, dB, dP, dQ;
-    UPLOAD(h, dA, p0, (size_t)n * 3 * sizeof(double));
-    UPLOAD(h, dB, p1, (size_t)n * 3 * sizeof(double));
-    HIPCHK(h, dP.alloc((size_t)n * num_points * 3 * sizeof(double)));
-    HIPCHK(h, dQ.alloc((size_t)n * sizeof(double)));
-    hipLaunchKernelGGL(catenary_3d_kernel, dim3(grid_for(n, 128)), dim3(128), 0, h->stream, dA.as<double>(), dB.as<double>(), rope_length,
-                       (long long)n, num_points, dP.as<double>(), dQ.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(pts, dP.p, (size_t)n * num_points * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (a_out) HIPCHK(h, hipMemcpyAsync(a_out, dQ.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_transform_catenary(rovmpc_handle *h, const double *A, const double *B, const double *theta,
-                                         const double *gamma, double L, int64_t n, int32_t M, double *out, int32_t *npts,
-                                         double *z_low) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (n < 0 || M < 2 || (n > 0 && (!A || !B || !theta || !gamma || !out || !npts)))
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_transform_catenary: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dA, dB, dt, dg, dO, dN, dZ;
-    UPLOAD(h, dA, A, (size_t)n * 3 * sizeof(double));
-    UPLOAD(h, dB, B, (size_t)n * 3 * sizeof(double));
-    UPLOAD(h, dt, theta, (size_t)n * sizeof(double));
-    UPLOAD(h, dg, gamma, (size_t)n * sizeof(double));
-    const size_t ob = (size_t)4 * n * M * 3 * sizeof(double);
-    HIPCHK(h, dO.alloc(ob));
-    HIPCHK(h, dN.alloc((size_t)n * 2 * sizeof(int32_t)));
-    HIPCHK(h, dZ.alloc((size_t)n * sizeof(double)));
-    const double up = h->cfg.frame == ROVMPC_ENU ? 1.0 : -1.0;
-    hipLaunchKernelGGL(transform_catenary_kernel, dim3(grid_for(n, 128)), dim3(128), 0, h->stream, dA.as<double>(), dB.as<double>(),
-                       dt.as<double>(), dg.as<double>(), L, up, h->cfg.c_lo, h->cfg.c_hi, (long long)n, M, dO.as<double>(),
-                       dN.as<int32_t>(), dZ.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dO.p, ob, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(npts, dN.p, (size_t)n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (z_low) HIPCHK(h, hipMemcpyAsync(z_low, dZ.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_velocity_transform(rovmpc_handle *h, const double *R, const double *v, int64_t n, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (n < 0 || (n > 0 && (!R || !v || !out))) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_velocity_transform: bad argument");
-    if (n == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dR, dv, dout;
-    UPLOAD(h, dR, R, (size_t)n * 9 * sizeof(double));
-    UPLOAD(h, dv, v, (size_t)n * 3 * sizeof(double));
-    HIPCHK(h, dout.alloc((size_t)n * 3 * sizeof(double)));
-    hipLaunchKernelGGL(velocity_transform_kernel, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, dR.as<double>(), dv.as<double>(),
-                       (long long)n, dout.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dout.p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
 #ifdef ROVMPC_STAMPS
 // Diagnostic library only: stamp slots per workgroup (the row length of what rovmpc_diag_read_stamps copies) ...
 extern "C" int32_t rovmpc_diag_stamp_slots(void) { return RV_NSTAMP; }
@@ -2550,142 +2043,6 @@ extern "C" int rovmpc_diag_read_stamps(rovmpc_handle *h, unsigned long long *out
     return ROVMPC_OK;
 }
 #endif
-
-extern "C" int rovmpc_extract_features(rovmpc_handle *h, const double *P0, const double *P1, const double *V1, const double *time,
-                                       const double *theta, const double *gamma, int64_t T, int32_t with_prev, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (T < 2 || !P0 || !P1 || !V1 || !time || !theta || !gamma || !out)
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_extract_features: bad argument (np.gradient needs at least 2 rows)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int F = with_prev ? 18 : 16;
-    DevBuf d0, d1, dv, dt, dth, dga, dout;
-    UPLOAD(h, d0, P0, (size_t)T * 3 * sizeof(double));
-    UPLOAD(h, d1, P1, (size_t)T * 3 * sizeof(double));
-    UPLOAD(h, dv, V1, (size_t)T * 3 * sizeof(double));
-    UPLOAD(h, dt, time, (size_t)T * sizeof(double));
-    UPLOAD(h, dth, theta, (size_t)T * sizeof(double));
-    UPLOAD(h, dga, gamma, (size_t)T * sizeof(double));
-    HIPCHK(h, dout.alloc((size_t)T * F * sizeof(double)));
-    hipLaunchKernelGGL(extract_features_kernel, dim3(grid_for(T, 256)), dim3(256), 0, h->stream, d0.as<double>(), d1.as<double>(),
-                       dv.as<double>(), dt.as<double>(), dth.as<double>(), dga.as<double>(), (long long)T, with_prev,
-                       dout.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dout.p, (size_t)T * F * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-// Hat matrix of the least-squares polynomial fit of degree `order` on `window` equally spaced samples
-// (centred abscissae): H = Q Q^T with Q the orthonormalised monomials (modified Gram-Schmidt, twice).
-static void savgol_hat_matrix(int window, int order, std::vector<double> &H) {
-    const int w = window, m = order + 1, half = w / 2;
-    std::vector<long double> Q((size_t)w * m);
-    for (int c = 0; c < m; ++c) {
-        for (int r = 0; r < w; ++r) Q[(size_t)r * m + c] = powl((long double)(r - half), c);
-        for (int pass = 0; pass < 2; ++pass)
-            for (int p = 0; p < c; ++p) {
-                long double d = 0;
-                for (int r = 0; r < w; ++r) d += Q[(size_t)r * m + c] * Q[(size_t)r * m + p];
-                for (int r = 0; r < w; ++r) Q[(size_t)r * m + c] -= d * Q[(size_t)r * m + p];
-            }
-        long double n = 0;
-        for (int r = 0; r < w; ++r) n += Q[(size_t)r * m + c] * Q[(size_t)r * m + c];
-        n = sqrtl(n);
-        for (int r = 0; r < w; ++r) Q[(size_t)r * m + c] /= n;
-    }
-    H.assign((size_t)w * w, 0.0);
-    for (int i = 0; i < w; ++i)
-        for (int j = 0; j < w; ++j) {
-            long double s = 0;
-            for (int c = 0; c < m; ++c) s += Q[(size_t)i * m + c] * Q[(size_t)j * m + c];
-            H[(size_t)i * w + j] = (double)s;
-        }
-}
-
-extern "C" int rovmpc_features_dd(rovmpc_handle *h, const double *P0_mm, const double *P1_mm, const double *V_mm, const double *time,
-                                  const double *theta, const double *gamma, int64_t T, int32_t window, int32_t polyorder,
-                                  double *features, double *targets) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (!P0_mm || !P1_mm || !V_mm || !time || !theta || !gamma || !features)
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_features_dd: null argument");
-    if (window < 3 || window > 255 || window % 2 == 0 || polyorder < 0 || polyorder >= window)
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_features_dd: window must be odd in 3..255 and polyorder < window (got %d, %d)", window, polyorder);
-    if (T < window) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_features_dd: %lld rows, fewer than the smoothing window %d (savgol_filter mode='interp')", (long long)T, window);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    std::vector<double> H;
-    savgol_hat_matrix(window, polyorder, H);
-    DevBuf d0, d1, dv, dt, dth, dga, dW, dF, dY, dpairs;
-    UPLOAD(h, d0, P0_mm, (size_t)T * 3 * sizeof(double));
-    UPLOAD(h, d1, P1_mm, (size_t)T * 3 * sizeof(double));
-    UPLOAD(h, dv, V_mm, (size_t)T * 3 * sizeof(double));
-    UPLOAD(h, dt, time, (size_t)T * sizeof(double));
-    UPLOAD(h, dth, theta, (size_t)T * sizeof(double));
-    UPLOAD(h, dga, gamma, (size_t)T * sizeof(double));
-    UPLOAD(h, dW, H.data(), H.size() * sizeof(double));
-    // pass 2: [dtheta, dgamma, a_sway, a_surge, a_x, a_y, a_z] <- gradients of pass-1 columns (main_fun.py:825-847);
-    // pass 3: targets [ddtheta, ddgamma] <- gradients of columns 2, 3 (:835-836)
-    const int pairs[] = {0, 2, 1, 3, 4, 6, 5, 7, 8, 11, 9, 12, 10, 13, /* pass 3 */ 2, 0, 3, 1};
-    UPLOAD(h, dpairs, pairs, sizeof(pairs));
-    HIPCHK(h, dF.alloc((size_t)T * 14 * sizeof(double)));
-    HIPCHK(h, dY.alloc((size_t)T * 2 * sizeof(double)));
-    const dim3 grid(grid_for(T, 256)), block(256);
-    hipLaunchKernelGGL(features_dd_pass1_kernel, grid, block, 0, h->stream, d0.as<double>(), d1.as<double>(), dv.as<double>(),
-                       dth.as<double>(), dga.as<double>(), dW.as<double>(), window, (long long)T, dF.as<double>());
-    hipLaunchKernelGGL(gradient_columns_kernel, grid, block, 0, h->stream, (const double *)dF.as<double>(), 14, dF.as<double>(), 14,
-                       dt.as<double>(), (long long)T, 7, (const int *)dpairs.p);
-    hipLaunchKernelGGL(gradient_columns_kernel, grid, block, 0, h->stream, (const double *)dF.as<double>(), 14, dY.as<double>(), 2,
-                       dt.as<double>(), (long long)T, 2, (const int *)dpairs.p + 14);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(features, dF.p, (size_t)T * 14 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (targets) HIPCHK(h, hipMemcpyAsync(targets, dY.p, (size_t)T * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_gaussian_filter1d(rovmpc_handle *h, const double *x, int64_t T, double sigma, double truncate, double *out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (T < 1 || !x || !out || !(sigma > 0) || !(truncate > 0))
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_gaussian_filter1d: bad argument");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int radius = (int)(truncate * sigma + 0.5);                  // scipy/ndimage/_filters.py gaussian_filter1d
-    if (radius > 4096) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_gaussian_filter1d: kernel radius %d too large", radius);
-    std::vector<double> w(radius + 1);
-    double sum = 0.0;
-    for (int k = -radius; k <= radius; ++k) sum += exp(-0.5 / (sigma * sigma) * (double)k * (double)k);
-    for (int k = 0; k <= radius; ++k) w[k] = exp(-0.5 / (sigma * sigma) * (double)k * (double)k) / sum;
-    DevBuf dx, dw, dout;
-    UPLOAD(h, dx, x, (size_t)T * sizeof(double));
-    UPLOAD(h, dw, w.data(), w.size() * sizeof(double));
-    HIPCHK(h, dout.alloc((size_t)T * sizeof(double)));
-    hipLaunchKernelGGL(gaussian_filter1d_kernel, dim3(grid_for(T, 256)), dim3(256), 0, h->stream, dx.as<double>(), (long long)T,
-                       dw.as<double>(), radius, dout.as<double>());
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, dout.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_kabsch_velocity_transform(rovmpc_handle *h, const double *P, const double *Q, const double *v, int64_t T,
-                                                int32_t M, int32_t batch_gates, double *v_out, double *R_out) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    if (T < 0 || M < 1 || M > 4096 || (T > 0 && (!P || !Q || !v || !v_out)))
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_kabsch_velocity_transform: bad argument");
-    if (T == 0) return ROVMPC_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf dP, dQ, dv, dout, dR;
-    UPLOAD(h, dP, P, (size_t)T * M * 3 * sizeof(double));
-    UPLOAD(h, dQ, Q, (size_t)T * M * 3 * sizeof(double));
-    UPLOAD(h, dv, v, (size_t)T * 3 * sizeof(double));
-    HIPCHK(h, dout.alloc((size_t)T * 3 * sizeof(double)));
-    HIPCHK(h, dR.alloc((size_t)T * 9 * sizeof(double)));
-    hipLaunchKernelGGL(kabsch_kernel, dim3(grid_for(T, 128)), dim3(128), 0, h->stream, dP.as<double>(), dQ.as<double>(),
-                       dv.as<double>(), (long long)T, M, batch_gates, dout.as<double>(), R_out ? dR.as<double>() : nullptr);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(v_out, dout.p, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (R_out) HIPCHK(h, hipMemcpyAsync(R_out, dR.p, (size_t)T * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ROVMPC_OK;
-}
 
 // ---- native collective ------------------------------------------------------------------------
 
@@ -2794,7 +2151,7 @@ static void comm_worker(rovmpc_handle *h) {
 }
 
 // Block the calling thread until the worker has ENQUEUED (not executed) every job on slot p.
-static int comm_wait_enqueued(rovmpc_handle *h, int p) {
+int comm_wait_enqueued(rovmpc_handle *h, int p) {
     std::unique_lock<std::mutex> lk(h->comm_mu);
     h->comm_cv.wait(lk, [&] { return h->comm_done[p] == h->comm_submitted[p]; });
     if (!h->comm_err.empty()) FAIL(h, ROVMPC_ERR_HIP, "collective worker: %s", h->comm_err.c_str());
@@ -2896,8 +2253,8 @@ extern "C" int rovmpc_comm_init(rovmpc_handle *h, const void *id128, int32_t ran
 // candidate shows up as a multiple of the undisturbed time -- and against the ones already chosen, until `want` are found.
 // Candidates created here and not chosen are destroyed.  Every wait is bounded (2 ms); the probe takes a few milliseconds.
 // Returns the chosen streams (possibly fewer than `want`, possibly none) and a one-line report.
-static int choose_side_streams(rovmpc_handle *h, hipStream_t caller, const std::vector<hipStream_t> &seed, int want,
-                               std::vector<hipStream_t> &chosen, std::string &log) {
+int choose_side_streams(rovmpc_handle *h, hipStream_t caller, const std::vector<hipStream_t> &seed, int want,
+                        std::vector<hipStream_t> &chosen, std::string &log) {
     unsigned long long *d_flag = nullptr; double *d_x = nullptr;
     HIPCHK(h, hipMalloc((void **)&d_flag, 8));
     HIPCHK(h, hipMemset(d_flag, 0, 8));
@@ -2964,7 +2321,7 @@ static int choose_side_streams(rovmpc_handle *h, hipStream_t caller, const std::
 
 // The collective streams: one per communicator where the probe finds that many, else the communicators share what it found;
 // nothing found (or ROVMPC_COMM_PLACE=0): the streams of rovmpc_comm_init stay.
-static int place_comm_streams(rovmpc_handle *h, hipStream_t caller) {
+int place_comm_streams(rovmpc_handle *h, hipStream_t caller) {
     h->comm_placed = true;
     if (const char *e = getenv("ROVMPC_COMM_PLACE")) if (!strcmp(e, "0")) { h->comm_placement = "off (ROVMPC_COMM_PLACE=0)"; return ROVMPC_OK; }
     std::vector<hipStream_t> seed, chosen;
@@ -3113,321 +2470,4 @@ extern "C" int rovmpc_comm_destroy(rovmpc_handle *h) {
     h->comm_placed = false;
     h->comm_aborted = false;
     return take_device_errors(h);       // anything raised since the last rovmpc_comm_sync
-}
-
-// ---- closed loop ----------------------------------------------------------------------------------
-
-// Workspace of the GPU-side closed-loop hand-off; fills the pointers of `p` and zeroes the sequence words on `s`.
-static int closed_loop_workspace(rovmpc_handle *h, HandoffArgs &p, hipStream_t s) {
-    const rovmpc_config &c = h->cfg;
-    const size_t max_blocks = c.candidates_per_block > 0 ? (size_t)((c.K + c.candidates_per_block - 1) / c.candidates_per_block) : (size_t)c.K;
-    if (!h->d_step_seq) {
-        HIPCHK(h, hipMalloc((void **)&h->d_step_seq, 256));
-        HIPCHK(h, hipMalloc((void **)&h->d_cl_granules, 2 * gran_stride((int)max_blocks, c.N) * sizeof(unsigned long long)));
-        HIPCHK(h, hipMemset(h->d_cl_granules, 0, 2 * gran_stride((int)max_blocks, c.N) * sizeof(unsigned long long)));
-        HIPCHK(h, hipMalloc((void **)&h->d_cl_blk_traj, 2 * max_blocks * (size_t)(c.N + 1) * 2 * sizeof(double)));
-    }
-    HIPCHK(h, hipMemsetAsync(h->d_step_seq, 0, 128, s));
-    // the ring holds NaN until a step writes it: a wait that gives up before its state arrives reads NaN, not a state
-    HIPCHK(h, hipMemsetAsync(h->d_step_seq + 16, 0xff, 128, s));
-    p.seq_theta = h->d_step_seq; p.seq_gamma = h->d_step_seq + 8;             // separate 64-byte lines
-    p.ring = reinterpret_cast<double *>(h->d_step_seq + 16);                   // [4][4] doubles
-    p.granules2 = h->d_cl_granules; p.blk_traj2 = h->d_cl_blk_traj;
-    return ROVMPC_OK;
-}
-
-// ---- pipelined closed loop: one step per launch, launches alternating between two streams -----------------------
-template <typename T, int VT>
-static hipError_t launch_step(const rovmpc_handle *h, const RolloutArgs<T> &a, const HandoffArgs &p, hipStream_t s, bool probe, int *capacity) {
-    const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_BUILTIN, VT) * sizeof(T);
-    auto kern = (a.CK == 16 && a.ck_shift == 4) ? closed_loop_step_kernel16<T, MODEL_BUILTIN, VT> : closed_loop_step_kernel<T, MODEL_BUILTIN, VT>;   // (literal-CK instance: rollout_body, CKC)
-    if constexpr (sizeof(T) == 8) { if (a.CK == 16 && a.ck_shift == 4 && a.N == 20 && !getenv("ROVMPC_NO_LITERAL_N")) kern = closed_loop_step_kernel16_n20<T, MODEL_BUILTIN, VT>; }
-    if (probe) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        int per_cu = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, a.NT, lds);
-        if (e != hipSuccess) return e;
-        *capacity = per_cu * h->n_cu;
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(a.NT), lds, s, a, p);
-    return hipGetLastError();
-}
-
-template <typename T>
-static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_t T_steps, double *d_state, const void *d_pools,
-                                   int32_t n_pools, int32_t feedback, double *d_results, hipStream_t s) {
-    Geo g = launch_geometry(h, 1);
-    // Two launches are in flight at any time (launch g + 1 may start once launch g - 1 is complete), and the later one's
-    // workgroups hold their CU slots while they wait for the earlier one's sweeper: both grids must fit the chip at once,
-    // whatever order the two queues dispatch in.  Four-wave workgroups share a CU three at a time (measured with the HW_ID
-    // stamp), five-wave ones do not: unless the caller fixed the geometry, use 256 threads.
-    if (h->cfg.threads_per_block == 0 && h->cfg.candidates_per_block == 0 && g.NT > 256 && g.CK <= 16) g.NT = 256;
-    // The launches alternate between the caller's stream and the process's high-priority stream (process_pipe_stream):
-    // streams of equal priority can share a hardware queue, and then nothing overlaps.
-    if (!h->pipe_streams[1]) FAIL(h, ROVMPC_ERR_HIP, "no second stream for the pipelined closed loop");
-    if (!h->pipe_placed) {
-        // ... provided that stream does not sit on the caller's command-processor pipe (31 us per step instead of 15,
-        // measured in round 2 with a stream created late): probe it, and others if it fails (choose_side_streams)
-        h->pipe_placed = true;
-        const char *e = getenv("ROVMPC_COMM_PLACE");
-        if (!(e && !strcmp(e, "0"))) {
-            std::vector<hipStream_t> chosen;
-            int rc = choose_side_streams(h, s, {h->pipe_streams[1]}, 1, chosen, h->pipe_placement);
-            if (rc) return rc;
-            if (!chosen.empty() && chosen[0] != h->pipe_streams[1]) { h->pipe_streams[1] = chosen[0]; h->pipe_stream_owned = true; }
-            if (getenv("ROVMPC_COMM_PLACE_VERBOSE")) fprintf(stderr, "[rovmpc] pipelined loop's second stream: %s\n", h->pipe_placement.c_str());
-        }
-    }
-    if (!h->pipe_ev[0])
-        for (auto &ev : h->pipe_ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const int vt = h->cfg.vt_mode;
-    const size_t R = rovmpc_result_len(h);
-    RolloutArgs<T> a;
-    HandoffArgs p;
-    int rcw = closed_loop_workspace(h, p, s);
-    if (rcw) return rcw;
-    p.T = T_steps; p.exo = d_exo;
-    const size_t pool_bytes = (size_t)h->cfg.K * h->cfg.N * 3 * sizeof(T);
-    int capacity = 0;
-    if (h->model_kind == MODEL_BUILTIN) {
-        h->plant_feedback = 0;
-        fill_args<T>(h, a, d_state, d_pools, nullptr, g, 1);
-        --*h->epoch_ctr;                                         // (the probe takes no epoch)
-        hipError_t e = vt == 0 ? launch_step<T, 0>(h, a, p, s, true, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, s, true, &capacity)
-                                                                                      : launch_step<T, 2>(h, a, p, s, true, &capacity);
-        if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
-    } else if (h->model_kind == MODEL_JIT) {
-        if (!h->jit_fn_step) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "the run-time specialised module has no pipelined entry");
-        const size_t lds = rollout_lds_elems<T>(h->cfg.N, g.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int per_cu = 0;
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_step, g.NT, lds) != hipSuccess) per_cu = 0;
-        capacity = per_cu * h->n_cu;
-    } else {
-        FAIL(h, ROVMPC_ERR_UNSUPPORTED, "pipelined closed loop: compiled-in and hiprtc-specialised models only (the interpreter runs launch per step)");
-    }
-    if (2 * g.nblocks > capacity)
-        FAIL(h, ROVMPC_ERR_UNSUPPORTED, "pipelined closed loop needs two grids resident at once: 2 x %d workgroups exceed the device's capacity %d "
-                                        "(use rovmpc_closed_loop_device)", g.nblocks, capacity);
-    h->cl_form = 2;
-    hipLaunchKernelGGL(plant_update_kernel, dim3(1), dim3(64), 0, s, d_state, d_exo, (const double *)nullptr);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->pipe_ev[2], s));
-    HIPCHK(h, hipStreamWaitEvent(h->pipe_streams[1], h->pipe_ev[2], 0));
-    for (int64_t i = 0; i < T_steps; ++i) {
-        hipStream_t st = (i & 1) ? h->pipe_streams[1] : s;
-        h->plant_feedback = feedback ? 1 : 0;
-        fill_args<T>(h, a, d_state, (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes, nullptr, g, 1);   // one epoch per step
-        h->plant_feedback = 0;
-        a.result = d_results + (size_t)i * R; a.k_offset = 0; a.slots = nullptr; a.rank = 0; a.world = 1;
-        a.sweeper = 0;
-        p.step = i;
-        const HandoffArgs &pi = p;
-        hipError_t e;
-        if (h->model_kind == MODEL_JIT) {
-            const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            struct { RolloutArgs<T> a; HandoffArgs p; } both{a, pi};
-            size_t asz = sizeof(both);
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &both, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-            e = hipModuleLaunchKernel(h->jit_fn_step, a.nblocks, 1, 1, a.NT, 1, 1, (unsigned)lds, st, nullptr, extra);
-        } else {
-            e = vt == 0 ? launch_step<T, 0>(h, a, pi, st, false, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, pi, st, false, &capacity)
-                                                                                      : launch_step<T, 2>(h, a, pi, st, false, &capacity);
-        }
-        if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "pipelined closed-loop launch failed: %s", hipGetErrorString(e));
-    }
-    HIPCHK(h, hipEventRecord(h->pipe_ev[1], h->pipe_streams[1]));
-    HIPCHK(h, hipStreamWaitEvent(s, h->pipe_ev[1], 0));
-    return ROVMPC_OK;
-}
-
-// Workgroups of the closed-loop step kernel (the instance launch_step / jit_fn_step would run, with its dynamic LDS) the
-// device holds at once: resident workgroups per CU x CUs; 0 if the model has no step kernel or the query fails.  Sets the
-// kernel's dynamic-LDS attribute on the way, as the launches need.
-template <typename T>
-static int step_kernel_capacity(rovmpc_handle *h, const Geo &g) {
-    const int vt = h->cfg.vt_mode;
-    int capacity = 0;
-    if (h->model_kind == MODEL_BUILTIN) {
-        RolloutArgs<T> a;
-        const HandoffArgs p{};
-        fill_args<T>(h, a, nullptr, nullptr, nullptr, g, 1);
-        --*h->epoch_ctr;                                         // (the probe takes no epoch)
-        hipError_t e = vt == 0 ? launch_step<T, 0>(h, a, p, nullptr, true, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, nullptr, true, &capacity)
-                                                                                              : launch_step<T, 2>(h, a, p, nullptr, true, &capacity);
-        if (e != hipSuccess) capacity = 0;
-    } else if (h->model_kind == MODEL_JIT && h->jit_fn_step) {
-        const size_t lds = rollout_lds_elems<T>(h->cfg.N, g.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int per_cu = 0;
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_step, g.NT, lds) != hipSuccess) per_cu = 0;
-        capacity = per_cu * h->n_cu;
-    }
-    return capacity;
-}
-
-// ---- sharded closed loop with the state handed over on the GPU ----------------------------------------------------------
-// BASELINE config 5 as it is asked (every step the candidate-sharded one), model feedback: step g + 1's rollout is launched
-// right behind step g's on the caller's stream -- no join, no plant-update kernel, no event on that stream -- and waits ON THE
-// GPU for the state: gamma early from its own rank's sweeper (gamma's path is candidate-invariant, hence the same on every
-// rank), theta from the select kernel that follows step g's all-reduce on the collective stream (the GLOBAL winner's first
-// node).  Its controls load, positions, gamma table and first velocity-transform half run meanwhile, so a step costs
-// rollout + max(0, all-reduce + select - prologue) instead of rollout + all-reduce + select + join + update
-// (world 1: 47.5 -> ~20 us).  Compiled-in and hiprtc models whose step-kernel grid is resident in one round (the caller,
-// rovmpc_closed_loop_device, checks that); records are the join-based loop's bit for bit.
-template <typename T>
-static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const double *d_exo, int64_t T_steps, double *d_state, const void *d_pools,
-                                         int32_t n_pools, int64_t k_offset, double *d_results, hipStream_t s) {
-    const Geo g = launch_geometry(h, 1);
-    const int vt = h->cfg.vt_mode;
-    const size_t R = rovmpc_result_len(h);
-    if (!h->comm_placed) {
-        int rc = place_comm_streams(h, s);
-        if (rc) return rc;
-    }
-    HandoffArgs p;
-    int rcw = closed_loop_workspace(h, p, s);
-    if (rcw) return rcw;
-    p.T = T_steps; p.exo = d_exo;
-    const size_t pool_bytes = (size_t)h->cfg.K * h->cfg.N * 3 * sizeof(T);
-    RolloutArgs<T> a;
-    for (int64_t i = 0; i < T_steps; ++i) {
-        const int sp = h->comm_flip;
-        h->comm_flip = (h->comm_flip + 1) % rovmpc_handle::NSLOT;
-        if (h->slot_used[sp]) {
-            int rc = comm_wait_enqueued(h, sp);
-            if (rc) return rc;
-        }
-        h->slot_used[sp] = true;
-        const unsigned long long use = ++h->slot_uses[sp];
-        h->arg_flag_consumed = h->d_flags + rovmpc_handle::NSLOT + sp; h->arg_consumed_need = use - 1;
-        h->arg_flag_rolled = h->d_flags + sp; h->arg_rolled_seq = use;
-        h->arg_slot_bad = h->d_flags + 2 * rovmpc_handle::NSLOT + sp;
-        int inject = 0;
-        if (h->inject_skip_rolled > 0) { --h->inject_skip_rolled; inject |= 1; }
-        if (h->inject_skip_consumed > 0) { --h->inject_skip_consumed; inject |= 2; }
-        h->arg_inject = inject;
-        h->plant_feedback = 1;
-        fill_args<T>(h, a, d_state, (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes, nullptr, g, 1);   // one epoch per step
-        h->plant_feedback = 0;
-        h->arg_flag_consumed = nullptr; h->arg_flag_rolled = nullptr; h->arg_slot_bad = nullptr; h->arg_inject = 0;
-        a.result = h->d_result; a.k_offset = k_offset; a.slots = h->d_slots[sp]; a.rank = h->comm_rank; a.world = h->comm_world;
-        p.step = i;
-        hipError_t e;
-        int capacity = 0;     // (not probed here: the caller's step_kernel_capacity has set the LDS attribute)
-        if (h->model_kind == MODEL_JIT) {
-            const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            struct { RolloutArgs<T> a; HandoffArgs p; } both{a, p};
-            size_t asz = sizeof(both);
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &both, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-            e = hipModuleLaunchKernel(h->jit_fn_step, a.nblocks, 1, 1, a.NT, 1, 1, (unsigned)lds, s, nullptr, extra);
-        } else {
-            e = vt == 0 ? launch_step<T, 0>(h, a, p, s, false, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, s, false, &capacity)
-                                                                          : launch_step<T, 2>(h, a, p, s, false, &capacity);
-        }
-        if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "sharded closed-loop launch failed: %s", hipGetErrorString(e));
-        {
-            std::lock_guard<std::mutex> lk(h->comm_mu);
-            h->comm_q.push_back({sp, d_results + (size_t)i * R, use, (int)(h->comm_rr++ % (unsigned long long)h->ncomm), inject,
-                                 i + 1 < T_steps ? p.ring : nullptr, p.seq_theta, (long long)(i + 1)});
-            ++h->comm_submitted[sp];
-        }
-        h->comm_cv.notify_all();
-    }
-    int rc = rovmpc_comm_join(h, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(final_state_kernel, dim3(1), dim3(64), 0, s, d_state, d_exo, (const double *)d_results, (long long)T_steps, (int)R, 1);
-    HIPCHK(h, hipGetLastError());
-    return ROVMPC_OK;
-}
-
-extern "C" int rovmpc_closed_loop_pipelined_device(rovmpc_handle *h, const double *d_exo, int64_t T, double *d_state,
-                                                   const void *d_pools, int32_t n_pools, int32_t feedback, double *d_results,
-                                                   void *stream) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    h->cl_form = 0;
-    if (T < 1 || n_pools < 1 || !d_exo || !d_state || !d_pools || !d_results)
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_closed_loop_pipelined_device: bad argument");
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (h->comm) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "pipelined closed loop is single-GPU: the sharded loop needs a host-issued collective per step");
-    if (feedback && h->cfg.feature_map == ROVMPC_FEATURES_GEN3)
-        FAIL(h, ROVMPC_ERR_UNSUPPORTED, "closed loop with model feedback carries (theta, gamma) only (see rovmpc_closed_loop_device)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return h->cfg.dtype == ROVMPC_F64
-               ? closed_loop_pipelined_t<double>(h, d_exo, T, d_state, d_pools, n_pools, feedback, d_results, (hipStream_t)stream)
-               : closed_loop_pipelined_t<float>(h, d_exo, T, d_state, d_pools, n_pools, feedback, d_results, (hipStream_t)stream);
-}
-
-extern "C" int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, int64_t T, double *d_state, const void *d_pools,
-                                         int32_t n_pools, int64_t k_offset, int32_t feedback, double *d_results, void *stream) {
-    if (!h) return ROVMPC_ERR_INVALID;
-    h->cl_form = 0;
-    if (T < 1 || n_pools < 1 || !d_exo || !d_state || !d_pools || !d_results)
-        FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_closed_loop_device: bad argument");
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (feedback && h->cfg.feature_map == ROVMPC_FEATURES_GEN3)
-        FAIL(h, ROVMPC_ERR_UNSUPPORTED, "closed loop with model feedback carries (theta, gamma) only; the second-order map needs the rates "
-                                        "(dtheta, dgamma) in state slots 14/15 -- supply measured rows (feedback = 0)");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t R = rovmpc_result_len(h);
-    const size_t pool_bytes = (size_t)h->cfg.K * h->cfg.N * 3 * h->esz;
-    if (!h->comm) {
-        // one GPU: the plant update of step i + 1 rides on the epilogue of step i (sweeping workgroup), so the
-        // loop is back-to-back rollout kernels; only step 0 needs the stand-alone update
-        h->cl_form = 1;
-        hipLaunchKernelGGL(plant_update_kernel, dim3(1), dim3(64), 0, s, d_state, d_exo, (const double *)nullptr);
-        HIPCHK(h, hipGetLastError());
-        for (int64_t i = 0; i < T; ++i) {
-            const void *U = (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes;
-            h->plant_next = i + 1 < T ? d_exo + (size_t)(i + 1) * 16 : nullptr;
-            h->plant_state = d_state; h->plant_feedback = feedback ? 1 : 0;
-            rc = enqueue_step(h, d_state, U, nullptr, d_results + (size_t)i * R, 0, nullptr, 0, 1, s);
-            h->plant_next = nullptr; h->plant_state = nullptr; h->plant_feedback = 0;
-            if (rc) return rc;
-        }
-        return ROVMPC_OK;
-    }
-    // model feedback over the sharded step: the GPU-side hand-off (closed_loop_sharded_handoff_t) unless the model runs on the
-    // interpreter (no step kernel), ROVMPC_CL_JOIN asks for the join-based form below, or the step kernel's grid is not
-    // resident in one round: step g + 1's workgroups spin on their CU slots until step g's select has run, so a grid of
-    // several rounds would leave the all-reduce and select of step g nowhere to run (every step a hand-off time-out)
-    if (feedback && T > 1 && !getenv("ROVMPC_CL_JOIN") &&
-        (h->model_kind == MODEL_BUILTIN || (h->model_kind == MODEL_JIT && h->jit_fn_step))) {
-        HIPCHK(h, hipSetDevice(h->cfg.device));
-        const Geo g = launch_geometry(h, 1);
-        const int capacity = h->cfg.dtype == ROVMPC_F64 ? step_kernel_capacity<double>(h, g) : step_kernel_capacity<float>(h, g);
-        const bool one_round = capacity > 0 && g.nblocks <= capacity;
-        if (getenv("ROVMPC_CL_VERBOSE"))
-            fprintf(stderr, "[rovmpc] sharded closed loop: %d workgroups, %d resident at once -> %s\n", g.nblocks, capacity,
-                    one_round ? "GPU-side hand-off" : "join per step");
-        if (one_round) {
-            h->cl_form = 4;
-            return h->cfg.dtype == ROVMPC_F64 ? closed_loop_sharded_handoff_t<double>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s)
-                                              : closed_loop_sharded_handoff_t<float>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s);
-        }
-    }
-    h->cl_form = 3;
-    for (int64_t i = 0; i < T; ++i) {
-        const double *prev = (feedback && i > 0) ? d_results + (size_t)(i - 1) * R : nullptr;
-        if (prev) {
-            // the previous global record is produced on the side stream
-            rc = rovmpc_comm_join(h, s);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(plant_update_kernel, dim3(1), dim3(64), 0, s, d_state, d_exo + (size_t)i * 16, prev);
-        HIPCHK(h, hipGetLastError());
-        const void *U = (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes;
-        rc = rovmpc_step_device_allreduce(h, d_state, U, k_offset, d_results + (size_t)i * R, s);
-        if (rc) return rc;
-    }
-    if (h->comm) return rovmpc_comm_join(h, s);
-    return ROVMPC_OK;
 }
