@@ -241,6 +241,26 @@ def tether_cost(spheres, w, margin=0.0):
     return t
 
 
+FIT_MAX_MARKERS = 16
+FIT_OUT = 6
+
+
+class FitParams(C.Structure):
+    """Mirror of ``rovmpc_fit_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double)]
+
+    @classmethod
+    def make(cls, tol: float = 1e-12, max_iter: int = 40) -> "FitParams":
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) <= 1000:
+            raise ValueError(f"max_iter must be an integer in 1..1000 (got {max_iter!r})")
+        tol = float(tol)
+        if not tol >= 0:
+            raise ValueError(f"tol must be >= 0 (got {tol!r})")
+        p = cls()
+        p.struct_size, p.max_iter, p.tol = C.sizeof(cls), int(max_iter), tol
+        return p
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -274,6 +294,9 @@ _SIGNATURES = {
     "rovmpc_nav_cost_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, _P]),
     "rovmpc_set_tether_cost": (C.c_int, [_P, C.POINTER(TetherCost)]),
     "rovmpc_tether_cost_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "rovmpc_default_fit_params": (None, [C.POINTER(FitParams)]),
+    "rovmpc_fit_theta_gamma": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.POINTER(FitParams), _P]),
+    "rovmpc_fit_theta_gamma_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.POINTER(FitParams), _P]),
     "rovmpc_mppi_row_len": (C.c_int32, [_P]),
     "rovmpc_cem_row_len": (C.c_int32, [_P, C.c_int32]),
     "rovmpc_mppi_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P]),

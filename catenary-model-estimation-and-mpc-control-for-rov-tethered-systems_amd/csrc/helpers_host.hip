@@ -2,6 +2,7 @@
 #include "rovmpc_internal.h"
 
 #include "util_kernels.h"
+#include "fit_kernels.h"
 
 // ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
 
@@ -438,4 +439,73 @@ extern "C" int rovmpc_kabsch_velocity_transform(rovmpc_handle *h, const double *
     c.download(v_out, dout);
     c.download(R_out, dR);
     return c.finish();
+}
+
+// ---- (theta, gamma) from cable markers (fit_kernels.h) -----------------------------------------
+
+extern "C" void rovmpc_default_fit_params(rovmpc_fit_params *p) {
+    if (!p) return;
+    p->struct_size = (int32_t)sizeof(rovmpc_fit_params);
+    p->max_iter = 40;
+    p->tol = 1e-12;
+}
+
+// the checks both entries share, then the kernel's arguments but for the pointers
+static int fit_args(rovmpc_handle *h, const char *entry, const void *P0, const void *P1, const void *Y, int64_t B, int32_t M,
+                    const rovmpc_fit_params *params, const void *out, FitArgs &a) {
+    rovmpc_fit_params p;
+    rovmpc_default_fit_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(rovmpc_fit_params))
+            FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_fit_params.struct_size %d != %d (ABI mismatch)", params->struct_size, (int)sizeof(rovmpc_fit_params));
+        p = *params;
+    }
+    if (B < 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: B must be >= 0 (got %lld)", entry, (long long)B);
+    if (M < 3 || M > ROVMPC_FIT_MAX_MARKERS) FAIL(h, ROVMPC_ERR_INVALID, "%s: M must be in 3..%d (got %d)", entry, ROVMPC_FIT_MAX_MARKERS, M);
+    if (!(p.tol >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "%s: tol must be >= 0 (got %g)", entry, p.tol);
+    if (p.max_iter < 1 || p.max_iter > 1000) FAIL(h, ROVMPC_ERR_INVALID, "%s: max_iter must be in 1..1000 (got %d)", entry, p.max_iter);
+    if (B > 0 && (!P0 || !P1 || !Y || !out)) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (P0, P1, Y or out)", entry);
+    const rovmpc_config &c = h->cfg;
+    const bool f64 = c.dtype == ROVMPC_F64;
+    memset(&a, 0, sizeof(a));
+    a.L = f64 ? c.L : (double)(float)c.L; a.c_lo = f64 ? c.c_lo : (double)(float)c.c_lo; a.c_hi = f64 ? c.c_hi : (double)(float)c.c_hi;
+    a.up = c.frame == ROVMPC_ENU ? 1.0 : -1.0;
+    a.tol = p.tol; a.B = B; a.M = M; a.max_iter = p.max_iter;
+    return ROVMPC_OK;
+}
+
+static void launch_fit(rovmpc_handle *h, const FitArgs &a) {
+    hipLaunchKernelGGL(fit_theta_gamma_kernel, dim3(grid_for(a.B, FIT_FRAMES)), dim3(FIT_NT), 0, h->stream, a);
+}
+
+extern "C" int rovmpc_fit_theta_gamma(rovmpc_handle *h, const double *P0, const double *P1, const double *Y, int64_t B, int32_t M,
+                                      const double *guess, const rovmpc_fit_params *params, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    FitArgs a;
+    if (int rc = fit_args(h, "rovmpc_fit_theta_gamma", P0, P1, Y, B, M, params, out, a)) return rc;
+    if (B == 0) return ROVMPC_OK;
+    if (B > (int64_t)1 << 24) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_fit_theta_gamma: more than 2^24 frames in one call (got %lld)", (long long)B);
+    HelperCall c(h);
+    const auto d0 = c.upload(P0, (size_t)B * 3);
+    const auto d1 = c.upload(P1, (size_t)B * 3);
+    const auto dY = c.upload(Y, (size_t)B * M * 3);
+    const auto dG = guess ? c.upload(guess, (size_t)B * 2) : DevArray<double>{nullptr, 0};
+    const auto dO = c.buffer<double>((size_t)B * ROVMPC_FIT_OUT);
+    a.P0 = d0.p; a.P1 = d1.p; a.Y = dY.p; a.guess = dG.p; a.out = dO.p;
+    if (c.ok()) launch_fit(h, a);
+    c.download(out, dO);
+    return c.finish();
+}
+
+extern "C" int rovmpc_fit_theta_gamma_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t B,
+                                             int32_t M, const double *d_guess, const rovmpc_fit_params *params, double *d_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    FitArgs a;
+    if (int rc = fit_args(h, "rovmpc_fit_theta_gamma_device", d_P0, d_P1, d_Y, B, M, params, d_out, a)) return rc;
+    if (B == 0) return ROVMPC_OK;
+    if (B > (int64_t)1 << 24) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_fit_theta_gamma_device: more than 2^24 frames in one call (got %lld)", (long long)B);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    a.P0 = d_P0; a.P1 = d_P1; a.Y = d_Y; a.guess = d_guess; a.out = d_out;
+    launch_fit(h, a);
+    return launched(h, "marker fit");
 }

@@ -2,14 +2,16 @@
 pointer entry points.  Everything numeric happens in the HIP library."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
-from dataclasses import dataclass, field, asdict
+import enum
+from dataclasses import dataclass, field, asdict, replace
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
-from ._lib import Config, State, MPPIParams, CEMParams, RovmpcError, check, load_library
+from ._lib import Config, State, MPPIParams, CEMParams, FitParams, RovmpcError, check, load_library
 from .model import DynamicsModel, default_model
 
 
@@ -104,6 +106,33 @@ class MPCState:
         if a.shape != (16,):
             raise ValueError("P0, P1, V1, A1 must have 3 components each")
         return a
+
+    def with_markers(self, markers, guess=None, engine: Optional["Engine"] = None) -> "MPCState":
+        """A copy whose theta and gamma are fitted to the cable markers (M, 3) of this state's P0 and P1
+        (``Engine.fit_theta_gamma``; ``guess`` (theta, gamma): the start, by default this state's own angles).  Raises
+        ValueError naming the status unless the fit is CONVERGED.  ``engine``: the one whose L, bracket and frame hold
+        (default: the shared helper engine)."""
+        if guess is None:
+            guess = (self.theta, self.gamma)
+        fit = (engine or default_engine()).fit_theta_gamma(self.P0, self.P1, markers, guess=guess)
+        status = FitStatus(int(fit.status))
+        if status is not FitStatus.CONVERGED:
+            raise ValueError(f"marker fit did not converge: status {status.name} after {int(fit.iters)} trial steps (rms {float(fit.rms):g} m)")
+        return replace(self, theta=float(fit.theta), gamma=float(fit.gamma))
+
+
+class FitStatus(enum.IntEnum):
+    """``rovmpc_fit_status`` (include/rovmpc.h)."""
+    CONVERGED = 0
+    MAX_ITER = 1
+    DEGENERATE = 2
+    CHORD = 3
+    TOO_FEW = 4
+    NONFINITE = 5
+
+
+CableFit = collections.namedtuple("CableFit", "theta gamma rms rms0 iters status")
+CableFit.__doc__ = """Columns of ``rovmpc_fit_theta_gamma``'s out: arrays (B,), or scalars for one frame; iters and status integers."""
 
 
 def state_array(state) -> np.ndarray:
@@ -788,6 +817,52 @@ class Engine:
         self._check(self.lib.rovmpc_kabsch_velocity_transform(self._h, _ptr(P), _ptr(Q), _ptr(v), T, M, int(batch_gates),
                                                               _ptr(out), _ptr(R)))
         return out, R
+
+    def _fit_inputs(self, P0, P1, markers, guess):
+        Y = np.ascontiguousarray(markers, np.float64)
+        single = Y.ndim == 2
+        if single:
+            Y = Y[None]
+        if Y.ndim != 3 or Y.shape[2] != 3:
+            raise ValueError(f"markers must be (M, 3) or (B, M, 3), got {np.shape(markers)}")
+        B, M = Y.shape[0], Y.shape[1]
+        if not 3 <= M <= _lib.FIT_MAX_MARKERS:
+            raise ValueError(f"3 to {_lib.FIT_MAX_MARKERS} markers per frame (got {M})")
+        c = lambda x, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), shape))
+        P0, P1 = c(P0, (B, 3)), c(P1, (B, 3))
+        G = None if guess is None else c(guess, (B, 2))
+        return P0, P1, Y, G, B, M, single
+
+    @staticmethod
+    def _fit_result(out, single):
+        cols = [out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4].astype(np.int64), out[:, 5].astype(np.int64)]
+        return CableFit(*[col[0] for col in cols]) if single else CableFit(*cols)
+
+    def fit_theta_gamma(self, P0, P1, markers, guess=None, tol: float = 1e-12, max_iter: int = 40) -> "CableFit":
+        """(theta, gamma) of the cable between P0 and P1 from its markers (rovmpc_fit_theta_gamma; law in include/rovmpc.h):
+        ``markers`` (M, 3) for one frame or (B, M, 3), 3 <= M <= 16, a NaN row = a missing marker; P0, P1 (3,) or (B, 3);
+        ``guess`` (2,) or (B, 2): the start, (0, 0) if None.  A local fit from that start.  Returns a ``CableFit`` of
+        arrays (B,), scalars for one frame; ``status`` holds ``FitStatus`` values."""
+        P0, P1, Y, G, B, M, single = self._fit_inputs(P0, P1, markers, guess)
+        params = FitParams.make(tol, max_iter)
+        out = np.empty((B, _lib.FIT_OUT))
+        self._check(self.lib.rovmpc_fit_theta_gamma(self._h, _ptr(P0), _ptr(P1), _ptr(Y), B, M, _ptr(G), C.byref(params), _ptr(out)))
+        return self._fit_result(out, single)
+
+    def fit_theta_gamma_device(self, P0, P1, markers, guess=None, tol: float = 1e-12, max_iter: int = 40) -> "CableFit":
+        """``fit_theta_gamma`` through the device entry (rovmpc_fit_theta_gamma_device) on torch buffers: the same bits."""
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        P0, P1, Y, G, B, M, single = self._fit_inputs(P0, P1, markers, guess)
+        params = FitParams.make(tol, max_iter)
+        d0, d1, dY = (torch.tensor(x, device=dev) for x in (P0, P1, Y))
+        dG = None if G is None else torch.tensor(G, device=dev)
+        dO = torch.empty((B, _lib.FIT_OUT), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_fit_theta_gamma_device(self._h, d0.data_ptr(), d1.data_ptr(), dY.data_ptr(), B, M,
+                                                           None if dG is None else dG.data_ptr(), C.byref(params), dO.data_ptr()))
+        torch.cuda.synchronize(dev)                     # (the device: the fit runs on the handle's own stream)
+        return self._fit_result(dO.cpu().numpy(), single)
 
 
 _default_engine: Optional[Engine] = None

@@ -193,6 +193,14 @@ def kabsch_velocity_transform(original_points, corrected_points, rob_speed, batc
     return default_engine().kabsch_velocity_transform(original_points, corrected_points, rob_speed, batch_gates)
 
 
+def fit_theta_gamma(P0, P1, markers, guess=None, tol: float = 1e-12, max_iter: int = 40):
+    """(theta, gamma) of the augmented catenary between P0 and P1 from cable markers (M, 3) or (B, M, 3): the inverse of
+    ``transform_catenary`` with ``Catenary(L)`` at the shared helper engine's L = 3 m, bracket and ENU frame
+    (``Engine.fit_theta_gamma`` for other settings).  catenary_from_data.py:40-50 is the per-frame loop this serves.
+    Returns a ``CableFit`` (theta, gamma, rms, rms0, iters, status)."""
+    return default_engine().fit_theta_gamma(P0, P1, markers, guess=guess, tol=tol, max_iter=max_iter)
+
+
 def compute_rotation_kabsch(P, Q):
     """velocity_transform_batch.py:8-19 for one frame: (N,3) original and corrected points -> R (3,3)."""
     P = np.asarray(P, float); Q = np.asarray(Q, float)

@@ -546,6 +546,85 @@ int rovmpc_set_tether_cost(rovmpc_handle *h, const rovmpc_tether_cost *tc);
 int rovmpc_tether_cost_device(rovmpc_handle *h, const double *d_state, const void *d_U, const void *d_traj,
                               double *d_C, double *d_D, void *d_J, void *stream);
 
+/* ---- (theta, gamma) from cable markers: the inverse of the augmented catenary, batched over frames -----------------------
+ * Every controller starts from a state whose theta and gamma somebody measured.  These two entries produce them from the
+ * markers a motion-capture frame carries along the cable (16 in the reference's recordings), frame by frame
+ * (catenary_from_data.py:40-50 is the per-frame loop this serves): a least-squares fit of the tether law's cable to the
+ * markers by Levenberg-Marquardt, one 64-lane wave per frame.
+ * Law.  All arithmetic in double whatever cfg.dtype T is; L = (T) cfg.L, c_lo = (T) cfg.c_lo, c_hi = (T) cfg.c_hi as the
+ * tether cost holds them; up = +1 (ENU) or -1 (NED) from cfg.frame.  One frame: A = P0, P = P1, rel = P - A, M markers Y_m
+ * (3 <= M <= ROVMPC_FIT_MAX_MARKERS), y_m = Y_m - A, and a start (theta_0, gamma_0), (0, 0) without `guess`.
+ *      model: X_m(theta, gamma) - A, m = 0 .. M - 1: the cable points of the tether law above at n_shape_pts = M (t_m =
+ *             m / (M - 1)) for the node (rel, theta, gamma), by the same device functions; the chord where the rotated system
+ *             has no root inside [c_lo, c_hi].  The model is evaluated at theta, theta (+) h and theta (-) h together, h =
+ *             ROVMPC_FIT_H = 2^-20 ((+), (-): the rounded sum and difference).  A point (theta, gamma) is USABLE when all
+ *             three are catenaries (none the chord) and finite;
+ *      weights: w_m = 0 for a marker with a non-finite coordinate (missing: motion capture drops markers), else 1;
+ *      objective: F(theta, gamma) = sum_m w_m |X_m - Y_m|^2, formed as sum w_m |(X_m - A) - y_m|^2;
+ *      Jacobian: dX_m/dgamma = k_gamma x (X_m - A) with k_gamma = rel / |rel| -- exact: gamma turns the cable about the chord;
+ *             dX_m/dtheta = (X_m(theta (+) h) - X_m(theta (-) h)) 2^19;
+ *      sums:  a, b, c = the entries of J^T J, (g_0, g_1) = J^T r with r_m = (X_m - A) - y_m, and F, each the sum over m of
+ *             w_m times a dot product fma(x x', fma(y y', z z')), added by a 16-lane xor butterfly in the order 8, 4, 2, 1 (the
+ *             slots m >= M hold 0): a function of the frame alone;
+ *      step:  mu starts at ROVMPC_FIT_MU0 = 1e-3;  a' = a (1 + mu), c' = c (1 + mu), d = a' c' - b^2,
+ *             dtheta = (g_1 b - g_0 c') / d,  dgamma = (g_0 b - g_1 a') / d;  the trial point is (theta + dtheta, gamma + dgamma).
+ *             The trial is ACCEPTED when it is usable and F does not increase beyond its own rounding,
+ *             F_trial <= F + ROVMPC_FIT_SLACK L sqrt(F sum w_m)  (SLACK = 2^-48: |dF| <= 2 sqrt(F) |dr| for an error dr of the
+ *             residual vector, and the points of a cable of length L are good to a few 2^-52 L each; without it the iterate
+ *             of a noisy frame is settled by comparisons of rounding errors): it becomes the iterate and mu = max(mu / 10,
+ *             ROVMPC_FIT_MU_MIN = 1e-12).  Otherwise it is rejected (a trial that turns into the chord or goes non-finite is
+ *             a rejected step): the iterate stays and mu = 10 mu;
+ *      stop:  after a trial step with max(|dtheta|, |dgamma|) <= tol, accepted or not: CONVERGED.  (Once a step is below
+ *             the tolerance the iterate is where the fit can place it; near the minimum of a noisy frame F is flat to
+ *             rounding, and whether such a step lowers F is no longer information.  An accepted one is taken.)  After
+ *             max_iter trial steps: MAX_ITER.  Defaults tol = 1e-12, max_iter = 40.
+ * Status, decided in this order:
+ *      NONFINITE   a coordinate of A, P or the start is non-finite, or rel = 0: theta^ = gamma^ = rms = rms0 = NaN;
+ *      TOO_FEW     no valid marker with 0 < m < M - 1 (X_0 = A and X_{M-1} = P whatever the angles: the end markers carry no
+ *                  information): the start is returned, with the model's rms there (NaN without any valid marker);
+ *      DEGENERATE  the start is not usable and B' at theta_0 is vertical (l' = 0: every sample lies on the chord line and no
+ *                  bracket gives a catenary; example: a vertical chord at theta = 0), or a c - b^2 <= 2^-80 a c (or not a
+ *                  number) at the start or after an accepted step that did not end the fit.  That iterate is returned;
+ *      CHORD       the start is not usable otherwise (taut, or the root outside the bracket): the Jacobian is identically
+ *                  zero on the chord.  The start is returned;
+ *      MAX_ITER, CONVERGED as above.
+ * out[b] = [theta^, gamma^, rms = sqrt(F / sum w_m) at the estimate, rms0 = the same at the start, trial steps used, status].
+ * The fit is LOCAL, from the start it is given: gamma^ is not wrapped and neither angle is clamped.  The map (theta, gamma) ->
+ * curve is not one-to-one: on steep chords a far start can end at another pair of angles that gives the SAME curve to
+ * rounding (an exact alias: rms = 0 there too).  Start from the previous frame's estimate where the angles themselves
+ * matter.  Markers are matched to samples by index, not by arc length.
+ * The bits of out[b] are a function of frame b, the parameters and the config alone: not of B, the frame's place in the
+ * batch or the entry.  Bad arguments (a null handle or required pointer, B < 0, M outside 3 .. ROVMPC_FIT_MAX_MARKERS, a
+ * struct_size mismatch, tol < 0 or NaN, max_iter outside 1 .. 1000) give ROVMPC_ERR_INVALID with a message and launch
+ * nothing; B = 0 is ROVMPC_OK and launches nothing.
+ * Not provided: arc-length correspondence, an unknown cable length or end points, robust losses, a search over aliases,
+ * filtering over time. */
+#define ROVMPC_FIT_MAX_MARKERS 16
+#define ROVMPC_FIT_OUT 6
+#define ROVMPC_FIT_H 0x1p-20
+#define ROVMPC_FIT_MU0 1e-3
+#define ROVMPC_FIT_MU_MIN 1e-12
+#define ROVMPC_FIT_DET_MIN 0x1p-80
+#define ROVMPC_FIT_SLACK 0x1p-48
+typedef enum rovmpc_fit_status {
+    ROVMPC_FIT_CONVERGED = 0, ROVMPC_FIT_MAX_ITER = 1, ROVMPC_FIT_DEGENERATE = 2, ROVMPC_FIT_CHORD = 3, ROVMPC_FIT_TOO_FEW = 4,
+    ROVMPC_FIT_NONFINITE = 5
+} rovmpc_fit_status;
+typedef struct rovmpc_fit_params {
+    int32_t struct_size;             /* = sizeof(rovmpc_fit_params), ABI check                           */
+    int32_t max_iter;                /* 1..1000 trial steps                                              */
+    double  tol;                     /* radians, >= 0                                                    */
+} rovmpc_fit_params;
+void rovmpc_default_fit_params(rovmpc_fit_params *p);
+/* Host pointers: P0[B][3], P1[B][3], Y[B][M][3], guess[B][2] or NULL, params or NULL (the defaults), out[B][ROVMPC_FIT_OUT].
+ * Uploads, one launch, one synchronise. */
+int rovmpc_fit_theta_gamma(rovmpc_handle *h, const double *P0, const double *P1, const double *Y, int64_t B, int32_t M,
+                           const double *guess, const rovmpc_fit_params *params, double *out);
+/* The same on device pointers (all double), enqueued on the handle's stream without a synchronise: for use between a sensor
+ * upload and the next control step, which the same stream orders behind it. */
+int rovmpc_fit_theta_gamma_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t B,
+                                  int32_t M, const double *d_guess, const rovmpc_fit_params *params, double *d_out);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
