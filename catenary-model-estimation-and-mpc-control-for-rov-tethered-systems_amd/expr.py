@@ -60,7 +60,9 @@ class _Compiler:
         self.max_depth = 0
 
     def _emit(self, op: str, arg: int = 0, delta: int = 0):
-        self.code.append(((arg & 0xFFFFFF) << 8) | OP[op])
+        # a signed int32 word: a negative POWI exponent is the two's-complement image of (arg << 8) | op, which the device's
+        # arithmetic `ins >> 8` reads back sign-extended (|arg| < 2^22 always, so the word fits)
+        self.code.append((arg << 8) | OP[op])
         self.depth += delta
         self.max_depth = max(self.max_depth, self.depth)
 

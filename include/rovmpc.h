@@ -90,9 +90,22 @@ extern "C" {
  * (simply.py:65-66, PySRTrainingScript.py:53-54, cluster_run/train_dynamics.py:28-46,
  * dynamic_eq_theta_cluster.py:35-43).
  * Values are what NumPy gives for the reference's lambdified rows to a few ulp (DESIGN.md section 3 has the bound of each
- * primitive), special operands included, with ONE deviation: sin(-0.0) is +0.0 where NumPy gives -0.0 (the argument
- * reduction computes (+0) * pi + (-0) = +0), so an expression such as 1 / sin(x) is +inf there and not -inf.  Every other
- * zero, every non-zero argument and cos(-0.0) = 1 agree in sign; tests/test_device_math_gpu.py pins this behaviour. */
+ * primitive and of each opcode), special operands included, with FOUR deviations, each pinned by
+ * tests/test_expr_paths_gpu.py on every route a row can take (interpreter and hiprtc, fp64 and fp32):
+ *  - sin(-0.0) is +0.0 where NumPy gives -0.0 (the argument reduction computes (+0) * pi + (-0) = +0), so an expression such
+ *    as 1 / sin(x) is +inf there and not -inf.  Every other zero, every non-zero argument and cos(-0.0) = 1 agree in sign
+ *    (tests/test_device_math_gpu.py pins the primitive).
+ *  - POWI with a negative exponent is 1 / x**|e| by square-and-multiply: where x**|e| overflows the result is a zero of the
+ *    right sign, where NumPy's pow still returns a subnormal (|result| < 2^-1022, fp32 2^-126).
+ *  - fp32 only: SQRT and SAFE_SQRT read a subnormal operand as a zero of its sign (v_sqrt_f32), so sqrt(1e-45f) is 0 and
+ *    sqrt(-1e-45f) is -0 where NumPy gives 3.7e-23 and NaN.
+ *  - hiprtc route only: a / D with a stage-invariant D (no state slot in it) under a dividend that reads one is a * (1 / D),
+ *    the reciprocal taken once per row.  Where 1 / D is not a normal number (|D| below 2^-1022 or above 2^1022; fp32 2^-126 and
+ *    2^126) the product is inf, NaN or short of bits where the quotient is finite: 6.7e-308 / 4.9e-324 is inf, not 1.35e16.
+ *    D = 0, inf and NaN give the quotient's own value.  Keeping the quotient for those rows, by a select or behind a wave-uniform
+ *    branch, cost 11% of a step on the generation-2 rows and 23% on a row with two such quotients.
+ * A word is a SIGNED int32: a negative POWI exponent is the two's-complement image of (e << 8) | 16, which `word >> 8` reads
+ * back sign-extended (|e| < 2^22; larger integer-valued exponents are POW). */
 enum rovmpc_opcode {
     ROVMPC_OP_PUSH_C = 0, ROVMPC_OP_PUSH_F = 1,
     ROVMPC_OP_ADD = 2, ROVMPC_OP_SUB = 3, ROVMPC_OP_MUL = 4, ROVMPC_OP_DIV = 5,

@@ -42,7 +42,7 @@ import numpy as np
 _EXPR_NS = {
     "sin": np.sin, "cos": np.cos, "tanh": np.tanh, "exp": np.exp, "log": np.log,
     "sqrt": np.sqrt, "Abs": np.abs, "abs": np.abs,
-    "square": np.square, "neg": np.negative,
+    "square": np.square, "neg": np.negative, "pow": np.power, "Pow": np.power,
     # cluster_run/train_dynamics.py:28-30 custom operators
     "safe_log": lambda x: np.log(np.abs(x) + 1e-5),
     "safe_sqrt": lambda x: np.sqrt(np.abs(x)),
