@@ -1341,10 +1341,10 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             };
             if (nsteps > 0) fetch(0, 0);
             const bool bounded = s_prog[0] == 0 && Trig<T>::bounded(m_abs(X3[0]));   // every sine argument of the loop is below the fast-path limit
-            // sincos(theta_n) for the velocity transform.  theta moves by |d| ~ 1e-4 per step, so
-            // after a full evaluation at step 0 (and every 16th step, or whenever a lane's |d|
-            // reaches 2^-7) the pair is advanced by the angle-addition formulas with the odd/even
-            // Taylor polynomials of d to d^5 / d^6 (truncation < 4e-19 there).
+            // sincos(theta_n) for the velocity transform.  Next to the scaler mean theta moves by |d| ~ 1e-3 per step
+            // (1/60 s; 0.017 from theta = 0.6, 0.04 from 1.5: tests/test_rollout_steps_gpu.py), so after a full evaluation
+            // at step 0 (and every 16th step, or whenever a lane's |d| reaches 2^-6) the pair is advanced by the
+            // angle-addition formulas with the odd/even Taylor polynomials of d to d^7 / d^6 (truncation < 1e-19 there).
             T st = T(0), ct = T(1);
             if (VT == ROVMPC_VT_COMPOSE) trig.sincos(th0, &st, &ct);
             // One loop for the common mode (RK4, interpolated delay slot, bounded sine arguments) with its flags
