@@ -11,16 +11,16 @@ from ._lib import (RovmpcError, load_library, exported_symbols, LIB_PATH,
 from .expr import compile_expression, disassemble, ExpressionError, Program
 from .model import (DynamicsModel, default_model, generation2_model, generation3_model, FEATURE_NAMES_GEN3, load_model_dir, read_equation_csv, select_row,
                     chosen_complexity_from_txt, FEATURE_NAMES_GEN1)
-from .engine import Engine, MPCConfig, MPCState, StepResult, default_engine, state_array, CableFit, FitStatus
+from .engine import Engine, MPCConfig, MPCState, StepResult, default_engine, state_array, CableFit, FitStatus, CableTrack, TrackState
 from .geometry import (rodrigues_rotation, transform_catenary, transform_catenary_batch, solve_catenary,
                        cable_tension, Catenary, Catenary3D, compute_catenary_3D, lowest_point, rotation_axes, velocity_transform,
-                       kabsch_velocity_transform, compute_rotation_kabsch, fit_theta_gamma)
+                       kabsch_velocity_transform, compute_rotation_kabsch, fit_theta_gamma, track_markers)
 from .integrate import (SymbolicRegressor, rk4_integration, integrate_theta_gamma, rk4_theta_gamma,
                         integrate_second_order)
 from .features import extract_features, extract_features_arrays, features_dd, features_dd_arrays, preprocess_signals, compute_derivatives
 from .lagrangian import euler_lagrange, el_residuals, lagrangian_rollout, differentiate, EulerLagrange
 from .trajgen import generate_rov_trajectories, trajectory_csv
-from ._lib import MPPIParams, CEMParams, FitParams
+from ._lib import MPPIParams, CEMParams, FitParams, TrackParams
 from .mpc import MPC, MPPI, CEM, BatchedMPPI, BatchedCEM, NavCost, TetherCost, PlanLoopResult, GaussianSampler, DeviceGaussianSampler, synthetic_problem
 from .closed_loop import run_plan_closed_loop
 

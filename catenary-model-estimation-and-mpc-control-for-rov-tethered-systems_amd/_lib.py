@@ -261,6 +261,34 @@ class FitParams(C.Structure):
         return p
 
 
+TRACK_MAX_STARTS = 8
+TRACK_OUT = 9
+TRACK_DEFAULT_STARTS = ((0.0, 0.0), (0.3, 0.0), (-0.3, 0.0), (0.6, 0.0), (-0.6, 0.0))
+
+
+class TrackParams(C.Structure):
+    """Mirror of ``rovmpc_track_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("n_starts", C.c_int32), ("max_iter", C.c_int32), ("reserved_", C.c_int32),
+                ("tol", C.c_double), ("rms_max", C.c_double), ("starts", (C.c_double * 2) * TRACK_MAX_STARTS)]
+
+    @classmethod
+    def make(cls, starts=None, rms_max: float = float("inf"), tol: float = 1e-12, max_iter: int = 40) -> "TrackParams":
+        f = FitParams.make(tol, max_iter)
+        starts = [tuple(float(x) for x in s) for s in (TRACK_DEFAULT_STARTS if starts is None else starts)]
+        if not 1 <= len(starts) <= TRACK_MAX_STARTS or any(len(s) != 2 for s in starts):
+            raise ValueError(f"starts must be 1..{TRACK_MAX_STARTS} pairs (theta, gamma) (got {starts!r})")
+        if not all(math.isfinite(x) for s in starts for x in s):
+            raise ValueError(f"starts must be finite (got {starts!r})")
+        rms_max = float(rms_max)
+        if not rms_max > 0:
+            raise ValueError(f"rms_max must be > 0 (got {rms_max!r})")
+        p = cls()
+        p.struct_size, p.n_starts, p.max_iter, p.tol, p.rms_max = C.sizeof(cls), len(starts), f.max_iter, f.tol, rms_max
+        for k, s in enumerate(starts):
+            p.starts[k][0], p.starts[k][1] = s
+        return p
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -297,6 +325,9 @@ _SIGNATURES = {
     "rovmpc_default_fit_params": (None, [C.POINTER(FitParams)]),
     "rovmpc_fit_theta_gamma": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.POINTER(FitParams), _P]),
     "rovmpc_fit_theta_gamma_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.POINTER(FitParams), _P]),
+    "rovmpc_default_track_params": (None, [C.POINTER(TrackParams)]),
+    "rovmpc_track_markers": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.POINTER(TrackParams), _P]),
+    "rovmpc_track_markers_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.POINTER(TrackParams), _P, _P]),
     "rovmpc_mppi_row_len": (C.c_int32, [_P]),
     "rovmpc_cem_row_len": (C.c_int32, [_P, C.c_int32]),
     "rovmpc_mppi_closed_loop_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(MPPIParams), _P]),

@@ -70,61 +70,83 @@ RV_DEV bool fit_eval(const TetherArgs &t, V3<double> rel, double th, double ga, 
     return fit_uniform(usable);
 }
 
-__global__ void __launch_bounds__(FIT_NT) fit_theta_gamma_kernel(const FitArgs a) {
-    const int lane = threadIdx.x & 63;
-    const long long f = (long long)blockIdx.x * FIT_FRAMES + (threadIdx.x >> 6);
-    if (f >= a.B) return;                                                   // the whole wave
-    const int v = lane >> 4, m = lane & 15, M = a.M;
-    const int ms = m < M ? m : M - 1;                                       // lanes beyond the markers repeat the last sample, weight 0
+// One frame as its wave holds it: the lane's role (variant v, sample m, ms the sample it evaluates), the frame relative to A,
+// the lane's marker and weight, the counts of valid and of valid interior markers, and `fin`, which is 0, or NaN once a
+// coordinate of A or P is non-finite ((A - A) + ...).
+struct FitFrame {
+    TetherArgs t;
+    V3<double> rel, y;
+    double nw, ni, fin;
+    int v, m, ms;
+    bool wm;
+};
 
-    TetherArgs t = {};
-    t.L = a.L; t.c_lo = a.c_lo; t.c_hi = a.c_hi; t.up = a.up; t.M = M;
-    const double *A = a.P0 + 3 * f, *P = a.P1 + 3 * f, *Yf = a.Y + (3 * f) * M + 3 * ms;
+struct FitResult { double th, ga, rms, rms0; int iters, status; };
+
+// Frame f of P0[.][3], P1[.][3], Y[.][M][3].
+RV_DEV FitFrame fit_load(const double *P0, const double *P1, const double *Y, long long f, int M, double L, double c_lo, double c_hi,
+                         double up, int lane) {
+    FitFrame q;
+    q.v = lane >> 4; q.m = lane & 15;
+    q.ms = q.m < M ? q.m : M - 1;                                           // lanes beyond the markers repeat the last sample, weight 0
+    q.t = TetherArgs{};
+    q.t.L = L; q.t.c_lo = c_lo; q.t.c_hi = c_hi; q.t.up = up; q.t.M = M;
+    const double *A = P0 + 3 * f, *P = P1 + 3 * f, *Yf = Y + (3 * f) * M + 3 * q.ms;
     const double Ax = A[0], Ay = A[1], Az = A[2];
-    const V3<double> rel = {P[0] - Ax, P[1] - Ay, P[2] - Az};
-    const V3<double> y = {Yf[0] - Ax, Yf[1] - Ay, Yf[2] - Az};
-    const bool wm = m < M && m_finite(y.x) && m_finite(y.y) && m_finite(y.z);
-    const double nw = fit_butterfly(wm ? 1.0 : 0.0);
-    const double ni = fit_butterfly(wm && m > 0 && m < M - 1 ? 1.0 : 0.0);
-    double th = a.guess ? a.guess[2 * f] : 0.0, ga = a.guess ? a.guess[2 * f + 1] : 0.0;
-    double *out = a.out + ROVMPC_FIT_OUT * f;
+    q.rel = {P[0] - Ax, P[1] - Ay, P[2] - Az};
+    q.y = {Yf[0] - Ax, Yf[1] - Ay, Yf[2] - Az};
+    q.wm = q.m < M && m_finite(q.y.x) && m_finite(q.y.y) && m_finite(q.y.z);
+    q.nw = fit_butterfly(q.wm ? 1.0 : 0.0);
+    q.ni = fit_butterfly(q.wm && q.m > 0 && q.m < M - 1 ? 1.0 : 0.0);
+    q.fin = ((Ax - Ax) + (Ay - Ay) + (Az - Az)) + ((q.rel.x - q.rel.x) + (q.rel.y - q.rel.y) + (q.rel.z - q.rel.z));
+    return q;
+}
 
-    // (A - A) + ... is 0, or NaN once a coordinate of A, P or the start is non-finite
-    const double fin = ((Ax - Ax) + (Ay - Ay) + (Az - Az)) + ((rel.x - rel.x) + (rel.y - rel.y) + (rel.z - rel.z)) + ((th - th) + (ga - ga));
-    if (fit_uniform(fin != fin || (rel.x == 0.0 && rel.y == 0.0 && rel.z == 0.0))) {
-        if (lane == 0) {
-            const double q = __builtin_nan("");
-            out[0] = q; out[1] = q; out[2] = q; out[3] = q; out[4] = 0.0; out[5] = (double)ROVMPC_FIT_NONFINITE;
-        }
-        return;
+// The law of rovmpc_fit_theta_gamma for one frame from the start (th, ga), on the whole wave: every lane returns the same
+// bits.  Both kernels that fit (fit_theta_gamma_kernel, track_markers_kernel of track_kernels.h) call this and nothing else.
+RV_DEV FitResult fit_frame(const FitFrame &q, double tol, int max_iter, double th, double ga) {
+    const double fin = q.fin + ((th - th) + (ga - ga));                     // NaN once the start is non-finite too
+    if (fit_uniform(fin != fin || (q.rel.x == 0.0 && q.rel.y == 0.0 && q.rel.z == 0.0))) {
+        const double n = __builtin_nan("");
+        return {n, n, n, n, 0, ROVMPC_FIT_NONFINITE};
     }
-
+    const double nw = q.nw;
     FitSums S = {}, St;
     double tht = th, gat = ga, dth = 0.0, dga = 0.0, mu = ROVMPC_FIT_MU0, F0 = 0.0;
     int iters = 0, status = ROVMPC_FIT_MAX_ITER;
     for (bool first = true;; first = false) {
         bool vertical;
-        const bool usable = fit_eval(t, rel, tht, gat, v, m, ms, y, wm, St, vertical);
+        const bool usable = fit_eval(q.t, q.rel, tht, gat, q.v, q.m, q.ms, q.y, q.wm, St, vertical);
         bool moved = false;
         if (first) {
             S = St; F0 = St.F; moved = true;
-            if (fit_uniform(ni == 0.0)) { status = ROVMPC_FIT_TOO_FEW; break; }
+            if (fit_uniform(q.ni == 0.0)) { status = ROVMPC_FIT_TOO_FEW; break; }
             if (!usable) { status = vertical ? ROVMPC_FIT_DEGENERATE : ROVMPC_FIT_CHORD; break; }
         } else {
             ++iters;
-            moved = usable && fit_uniform(St.F <= S.F + (ROVMPC_FIT_SLACK * a.L) * ::sqrt(nw * S.F));
+            moved = usable && fit_uniform(St.F <= S.F + (ROVMPC_FIT_SLACK * q.t.L) * ::sqrt(nw * S.F));
             if (moved) { th = tht; ga = gat; S = St; mu = ::fmax(mu * 0.1, ROVMPC_FIT_MU_MIN); } else mu *= 10.0;
-            if (fit_uniform(::fmax(::fabs(dth), ::fabs(dga)) <= a.tol)) { status = ROVMPC_FIT_CONVERGED; break; }
+            if (fit_uniform(::fmax(::fabs(dth), ::fabs(dga)) <= tol)) { status = ROVMPC_FIT_CONVERGED; break; }
         }
         if (moved && fit_uniform(!(S.a * S.c - S.b * S.b > ROVMPC_FIT_DET_MIN * S.a * S.c))) { status = ROVMPC_FIT_DEGENERATE; break; }
-        if (iters >= a.max_iter) break;
+        if (iters >= max_iter) break;
         const double ad = S.a * (1.0 + mu), cd = S.c * (1.0 + mu), id = 1.0 / (ad * cd - S.b * S.b);
         dth = (S.g1 * S.b - S.g0 * cd) * id;
         dga = (S.g0 * S.b - S.g1 * ad) * id;
         tht = th + dth; gat = ga + dga;
     }
+    return {th, ga, ::sqrt(S.F / nw), ::sqrt(F0 / nw), iters, status};
+}
+
+__global__ void __launch_bounds__(FIT_NT) fit_theta_gamma_kernel(const FitArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long f = (long long)blockIdx.x * FIT_FRAMES + (threadIdx.x >> 6);
+    if (f >= a.B) return;                                                   // the whole wave
+    const FitFrame q = fit_load(a.P0, a.P1, a.Y, f, a.M, a.L, a.c_lo, a.c_hi, a.up, lane);
+    const FitResult r = fit_frame(q, a.tol, a.max_iter, a.guess ? a.guess[2 * f] : 0.0, a.guess ? a.guess[2 * f + 1] : 0.0);
     if (lane == 0) {
-        out[0] = th; out[1] = ga; out[2] = ::sqrt(S.F / nw); out[3] = ::sqrt(F0 / nw); out[4] = (double)iters; out[5] = (double)status;
+        double *out = a.out + ROVMPC_FIT_OUT * f;
+        out[0] = r.th; out[1] = r.ga; out[2] = r.rms; out[3] = r.rms0; out[4] = (double)r.iters; out[5] = (double)r.status;
     }
 }
 

@@ -3,6 +3,7 @@
 
 #include "util_kernels.h"
 #include "fit_kernels.h"
+#include "track_kernels.h"
 
 // ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
 
@@ -508,4 +509,95 @@ extern "C" int rovmpc_fit_theta_gamma_device(rovmpc_handle *h, const double *d_P
     a.P0 = d_P0; a.P1 = d_P1; a.Y = d_Y; a.guess = d_guess; a.out = d_out;
     launch_fit(h, a);
     return launched(h, "marker fit");
+}
+
+// ---- (theta, gamma) along marker recordings (track_kernels.h) ----------------------------------
+
+extern "C" void rovmpc_default_track_params(rovmpc_track_params *p) {
+    if (!p) return;
+    rovmpc_fit_params f;
+    rovmpc_default_fit_params(&f);
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(rovmpc_track_params);
+    p->n_starts = 5;
+    p->max_iter = f.max_iter;
+    p->tol = f.tol;
+    p->rms_max = HUGE_VAL;
+    const double th[5] = {0.0, 0.3, -0.3, 0.6, -0.6};
+    for (int k = 0; k < 5; ++k) p->starts[k][0] = th[k];
+}
+
+// the checks both entries share, then the kernel's arguments but for the pointers
+static int track_args(rovmpc_handle *h, const char *entry, const void *P0, const void *P1, const void *Y, int64_t B, int64_t T, int32_t M,
+                      const rovmpc_track_params *params, const void *out, TrackArgs &a) {
+    rovmpc_track_params p;
+    rovmpc_default_track_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(rovmpc_track_params))
+            FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_track_params.struct_size %d != %d (ABI mismatch)", params->struct_size, (int)sizeof(rovmpc_track_params));
+        p = *params;
+    }
+    if (T < 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: T must be >= 0 (got %lld)", entry, (long long)T);
+    if (p.n_starts < 1 || p.n_starts > ROVMPC_TRACK_MAX_STARTS)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: n_starts must be in 1..%d (got %d)", entry, ROVMPC_TRACK_MAX_STARTS, p.n_starts);
+    for (int k = 0; k < p.n_starts; ++k)
+        if (!std::isfinite(p.starts[k][0]) || !std::isfinite(p.starts[k][1]))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: start %d is not finite (%g, %g)", entry, k, p.starts[k][0], p.starts[k][1]);
+    if (!(p.rms_max > 0)) FAIL(h, ROVMPC_ERR_INVALID, "%s: rms_max must be > 0 (got %g)", entry, p.rms_max);
+    rovmpc_fit_params fp;
+    rovmpc_default_fit_params(&fp);
+    fp.tol = p.tol; fp.max_iter = p.max_iter;
+    FitArgs f;                               // B, M, tol, max_iter and the pointers: the fit's own checks; L, c_lo, c_hi, up as it holds them
+    const bool empty = B == 0 || T == 0;
+    if (int rc = fit_args(h, entry, empty ? nullptr : P0, empty ? nullptr : P1, empty ? nullptr : Y, empty ? 0 : B, M, &fp, empty ? nullptr : out, f))
+        return rc;
+    if (B < 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: B must be >= 0 (got %lld)", entry, (long long)B);
+    if (!empty && (B > ((int64_t)1 << 24) || T > ((int64_t)1 << 24) || B * T > ((int64_t)1 << 24)))
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 frames in one call (got %lld x %lld)", entry, (long long)B, (long long)T);
+    memset(&a, 0, sizeof(a));
+    a.L = f.L; a.c_lo = f.c_lo; a.c_hi = f.c_hi; a.up = f.up;
+    a.tol = p.tol; a.rms_max = p.rms_max; a.B = B; a.T = T; a.M = M; a.max_iter = p.max_iter; a.n_starts = p.n_starts;
+    memcpy(a.starts, p.starts, sizeof(a.starts));
+    return ROVMPC_OK;
+}
+
+// T frames as launches of at most track_chunk; the stream orders them, and each reads the carry the one before left in `out`
+static void launch_track(rovmpc_handle *h, TrackArgs &a) {
+    for (long long t0 = 0; t0 < a.T; t0 += h->track_chunk) {
+        a.t0 = t0; a.t1 = std::min<long long>(a.T, t0 + h->track_chunk);
+        hipLaunchKernelGGL(track_markers_kernel, dim3(grid_for(a.B, FIT_FRAMES)), dim3(FIT_NT), 0, h->stream, a);
+    }
+}
+
+extern "C" int rovmpc_track_markers(rovmpc_handle *h, const double *P0, const double *P1, const double *Y, int64_t B, int64_t T, int32_t M,
+                                    double *carry, const rovmpc_track_params *params, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    TrackArgs a;
+    if (int rc = track_args(h, "rovmpc_track_markers", P0, P1, Y, B, T, M, params, out, a)) return rc;
+    if (B == 0 || T == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    const size_t n = (size_t)B * T;
+    const auto d0 = c.upload(P0, n * 3);
+    const auto d1 = c.upload(P1, n * 3);
+    const auto dY = c.upload(Y, n * M * 3);
+    const auto dC = carry ? c.upload((const double *)carry, (size_t)B * 2) : DevArray<double>{nullptr, 0};
+    const auto dO = c.buffer<double>(n * ROVMPC_TRACK_OUT);
+    a.P0 = d0.p; a.P1 = d1.p; a.Y = dY.p; a.carry = dC.p; a.out = dO.p;
+    if (c.ok()) launch_track(h, a);
+    c.download(out, dO);
+    if (carry) c.download(carry, dC);
+    return c.finish();
+}
+
+extern "C" int rovmpc_track_markers_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t B,
+                                           int64_t T, int32_t M, double *d_carry, const rovmpc_track_params *params, double *d_out,
+                                           double *d_exo) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    TrackArgs a;
+    if (int rc = track_args(h, "rovmpc_track_markers_device", d_P0, d_P1, d_Y, B, T, M, params, d_out, a)) return rc;
+    if (B == 0 || T == 0) return ROVMPC_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    a.P0 = d_P0; a.P1 = d_P1; a.Y = d_Y; a.carry = d_carry; a.out = d_out; a.exo = d_exo;
+    launch_track(h, a);
+    return launched(h, "marker track");
 }

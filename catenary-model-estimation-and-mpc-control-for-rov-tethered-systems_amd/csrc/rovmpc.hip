@@ -1133,6 +1133,9 @@ extern "C" int rovmpc_set_option(rovmpc_handle *h, const char *name, double valu
     if (!strcmp(name, "handoff_timeout_ms")) {
         if (!(value > 0) || value > 600000.0) FAIL(h, ROVMPC_ERR_INVALID, "handoff_timeout_ms must be in (0, 600000]");
         h->handoff_timeout_ms = value;
+    } else if (!strcmp(name, "track_chunk")) {
+        if (!(value >= 1) || value > 65536.0 || value != (double)(int)value) FAIL(h, ROVMPC_ERR_INVALID, "track_chunk must be an integer in 1..65536");
+        h->track_chunk = (int)value;
     } else if (!strcmp(name, "inject_skip_rolled")) {
         h->inject_skip_rolled = (int)value;
     } else if (!strcmp(name, "inject_skip_consumed")) {

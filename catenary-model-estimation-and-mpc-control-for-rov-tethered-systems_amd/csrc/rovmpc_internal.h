@@ -109,6 +109,7 @@ struct rovmpc_handle {
     unsigned *h_err = nullptr, *d_err = nullptr;
     double handoff_timeout_ms = 10000.0;      // give-up time of the GPU-side hand-off waits (rovmpc_set_option)
     int inject_skip_rolled = 0, inject_skip_consumed = 0;   // test hooks: the next N steps lose that publication
+    int track_chunk = 256;                    // frames per launch of rovmpc_track_markers* (rovmpc_set_option)
     // rovmpc_mpc_step_sampled: two candidate tensors (the sampler of step s+1 reads the winner of step s for the warm
     // start) and the mailbox of the record (its sequence numbers are samp_steps)
     void *d_Us[2] = {nullptr, nullptr};

@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import Config, State, MPPIParams, CEMParams, FitParams, RovmpcError, check, load_library
+from ._lib import Config, State, MPPIParams, CEMParams, FitParams, TrackParams, RovmpcError, check, load_library
 from .model import DynamicsModel, default_model
 
 
@@ -133,6 +133,47 @@ class FitStatus(enum.IntEnum):
 
 CableFit = collections.namedtuple("CableFit", "theta gamma rms rms0 iters status")
 CableFit.__doc__ = """Columns of ``rovmpc_fit_theta_gamma``'s out: arrays (B,), or scalars for one frame; iters and status integers."""
+
+
+class TrackState(enum.IntEnum):
+    """``rovmpc_track_state`` (include/rovmpc.h)."""
+    LOCKED = 0
+    ACQUIRED = 1
+    HELD = 2
+    NONE = 3
+
+
+@dataclass(frozen=True)
+class CableTrack:
+    """Columns of ``rovmpc_track_markers``'s out, arrays (T,) for one recording or (B, T): theta, gamma, theta_prev,
+    gamma_prev, rms (NaN where no attempt was accepted), iters (trial steps summed over the frame's attempts), status
+    (``FitStatus`` of the accepted or else the last attempt), state (``TrackState``), start (index into the start list, -1 =
+    the carry); and ``carry`` (2,) or (B, 2): the last accepted estimate, NaN if none, to hand to the next call."""
+    theta: np.ndarray
+    gamma: np.ndarray
+    theta_prev: np.ndarray
+    gamma_prev: np.ndarray
+    rms: np.ndarray
+    iters: np.ndarray
+    status: np.ndarray
+    state: np.ndarray
+    start: np.ndarray
+    carry: np.ndarray
+
+    def rows(self, rows, allow_missing: bool = False) -> np.ndarray:
+        """A copy of the state rows (T, 16) or (B, T, 16) -- what ``MPPI.run`` and the closed loops consume -- with slots
+        12..15 (theta, gamma, theta_prev, gamma_prev) filled from the track.  A frame whose state is NONE has no angles:
+        ValueError, unless ``allow_missing``, which leaves those rows as given."""
+        out = np.array(rows, dtype=np.float64)
+        if out.shape != self.theta.shape + (16,):
+            raise ValueError(f"rows must be {self.theta.shape + (16,)}, got {out.shape}")
+        ok = self.state != TrackState.NONE
+        if not allow_missing and not ok.all():
+            raise ValueError(f"{int((~ok).sum())} frame(s) have no estimate (track state NONE), the first at index "
+                             f"{tuple(int(i) for i in np.argwhere(~ok)[0])}")
+        for slot, col in zip(range(12, 16), (self.theta, self.gamma, self.theta_prev, self.gamma_prev)):
+            out[..., slot] = np.where(ok, col, out[..., slot])
+        return out
 
 
 def state_array(state) -> np.ndarray:
@@ -863,6 +904,65 @@ class Engine:
                                                            None if dG is None else dG.data_ptr(), C.byref(params), dO.data_ptr()))
         torch.cuda.synchronize(dev)                     # (the device: the fit runs on the handle's own stream)
         return self._fit_result(dO.cpu().numpy(), single)
+
+    def _track_inputs(self, P0, P1, markers, carry):
+        Y = np.ascontiguousarray(markers, np.float64)
+        single = Y.ndim == 3
+        if single:
+            Y = Y[None]
+        if Y.ndim != 4 or Y.shape[3] != 3:
+            raise ValueError(f"markers must be (T, M, 3) or (B, T, M, 3), got {np.shape(markers)}")
+        B, T, M = Y.shape[:3]
+        if not 3 <= M <= _lib.FIT_MAX_MARKERS:
+            raise ValueError(f"3 to {_lib.FIT_MAX_MARKERS} markers per frame (got {M})")
+        c = lambda x, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), shape)).copy()
+        P0, P1 = c(P0, (B, T, 3)), c(P1, (B, T, 3))
+        Cy = None if carry is None else c(carry, (B, 2))
+        return P0, P1, Y, Cy, B, T, M, single
+
+    @staticmethod
+    def _track_result(out, carry, B, single):
+        if carry is None:                               # a fresh start returns no carry: it is the last frame's output angles
+            carry = out[:, -1, 0:2].copy() if out.shape[1] else np.full((B, 2), np.nan)
+        i = lambda k: out[..., k].astype(np.int64)
+        cols = [out[..., 0], out[..., 1], out[..., 2], out[..., 3], out[..., 4], i(5), i(6), i(7), i(8), carry]
+        return CableTrack(*[np.ascontiguousarray(col[0] if single else col) for col in cols])
+
+    def track_markers(self, P0, P1, markers, carry=None, starts=None, rms_max: float = float("inf"), tol: float = 1e-12,
+                      max_iter: int = 40) -> "CableTrack":
+        """(theta, gamma) along a recording (rovmpc_track_markers; law in include/rovmpc.h): ``markers`` (T, M, 3) or
+        (B, T, M, 3), a NaN row = a missing marker; P0, P1 (3,), (T, 3) or (B, T, 3); ``carry`` (2,) or (B, 2): the last
+        accepted estimate of the call before, None (or NaN) for a fresh start; ``starts``: the re-acquisition list of
+        (theta, gamma), the law's default if None; ``rms_max``: accept a converged fit only at or below this rms (metres).
+        Returns a ``CableTrack``; ``CableTrack.rows`` fills the state rows the controllers' loops consume."""
+        P0, P1, Y, Cy, B, T, M, single = self._track_inputs(P0, P1, markers, carry)
+        params = TrackParams.make(starts, rms_max, tol, max_iter)
+        out = np.empty((B, T, _lib.TRACK_OUT))
+        self._check(self.lib.rovmpc_track_markers(self._h, _ptr(P0), _ptr(P1), _ptr(Y), B, T, M, _ptr(Cy), C.byref(params), _ptr(out)))
+        return self._track_result(out, Cy, B, single)
+
+    def track_markers_device(self, P0, P1, markers, carry=None, starts=None, rms_max: float = float("inf"), tol: float = 1e-12,
+                             max_iter: int = 40, exo=None):
+        """``track_markers`` through the device entry (rovmpc_track_markers_device) on torch buffers: the same bits.  With
+        ``exo`` (T, 16) or (B, T, 16) returns (CableTrack, the rows as the entry left them)."""
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        P0, P1, Y, Cy, B, T, M, single = self._track_inputs(P0, P1, markers, carry)
+        params = TrackParams.make(starts, rms_max, tol, max_iter)
+        d0, d1, dY = (torch.tensor(x, device=dev) for x in (P0, P1, Y))
+        dC = None if Cy is None else torch.tensor(Cy, device=dev)
+        dE = None if exo is None else torch.tensor(np.ascontiguousarray(exo, np.float64).reshape(B, T, 16), device=dev)
+        dO = torch.empty((B, T, _lib.TRACK_OUT), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_track_markers_device(self._h, d0.data_ptr(), d1.data_ptr(), dY.data_ptr(), B, T, M,
+                                                         None if dC is None else dC.data_ptr(), C.byref(params), dO.data_ptr(),
+                                                         None if dE is None else dE.data_ptr()))
+        torch.cuda.synchronize(dev)                     # (the device: the tracker runs on the handle's own stream)
+        track = self._track_result(dO.cpu().numpy(), None if dC is None else dC.cpu().numpy(), B, single)
+        if dE is None:
+            return track
+        rows = dE.cpu().numpy()
+        return track, (rows[0] if single else rows)
 
 
 _default_engine: Optional[Engine] = None

@@ -201,6 +201,13 @@ def fit_theta_gamma(P0, P1, markers, guess=None, tol: float = 1e-12, max_iter: i
     return default_engine().fit_theta_gamma(P0, P1, markers, guess=guess, tol=tol, max_iter=max_iter)
 
 
+def track_markers(P0, P1, markers, carry=None, starts=None, rms_max: float = float("inf"), tol: float = 1e-12, max_iter: int = 40):
+    """(theta, gamma) along a recording of cable markers (T, M, 3) or (B, T, M, 3): every frame fitted from the last accepted
+    estimate, re-acquired from ``starts`` when that fails, held across frames nothing can be made of
+    (``Engine.track_markers`` on the shared helper engine: L = 3 m, its bracket, ENU).  Returns a ``CableTrack``."""
+    return default_engine().track_markers(P0, P1, markers, carry=carry, starts=starts, rms_max=rms_max, tol=tol, max_iter=max_iter)
+
+
 def compute_rotation_kabsch(P, Q):
     """velocity_transform_batch.py:8-19 for one frame: (N,3) original and corrected points -> R (3,3)."""
     P = np.asarray(P, float); Q = np.asarray(Q, float)

@@ -638,6 +638,65 @@ int rovmpc_fit_theta_gamma(rovmpc_handle *h, const double *P0, const double *P1,
 int rovmpc_fit_theta_gamma_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t B,
                                   int32_t M, const double *d_guess, const rovmpc_fit_params *params, double *d_out);
 
+/* ---- (theta, gamma) along marker recordings: the chain of fits, batched over recordings --------------------------------
+ * The controllers' loops consume rows of 16 whose slots 12..15 are theta, gamma, theta_prev, gamma_prev.  These entries
+ * produce them from a recording (P0, P1 and M markers per frame): each frame is fitted from the last accepted estimate, a
+ * lost frame is re-acquired from a short start list, and a frame nothing can be made of holds the last estimate.  Strictly
+ * sequential along a recording, one 64-lane wave per recording, parallel across recordings; no host in between.
+ * Law.  One recording: frames t = 0 .. T - 1 (A_t = P0_t, P_t = P1_t, Y_t with M markers), the fit's tol and max_iter, a
+ * start list starts[n_starts][2] (1 <= n_starts <= ROVMPC_TRACK_MAX_STARTS, all finite) and rms_max in metres (> 0, +inf
+ * allowed).  Defaults: starts (0, 0), (0.3, 0), (-0.3, 0), (0.6, 0), (-0.6, 0); rms_max = +inf; the fit's tol and max_iter.
+ * The chain's only memory is the carry c = (theta_c, gamma_c), the last ACCEPTED estimate; a non-finite component means
+ * there is none (and c counts as (NaN, NaN)).  Frame t makes attempts in this order: from c if there is one (start index
+ * -1), then from starts[0], starts[1], ...  Each attempt is exactly the law of rovmpc_fit_theta_gamma for that frame with
+ * that start as `guess`.  An attempt is ACCEPTED when its status is CONVERGED and its rms <= rms_max.  The first accepted
+ * attempt ends the frame and becomes the carry.  An attempt that answers TOO_FEW or NONFINITE also ends the frame,
+ * unaccepted: no start can help.  Track state of the frame:
+ *      LOCKED    accepted from the carry;
+ *      ACQUIRED  accepted from a start of the list;
+ *      HELD      none accepted and there is a carry: the output angles are the carry, which stays;
+ *      NONE      none accepted and there is no carry: the output angles are NaN.
+ * out[b][t] = [theta, gamma, theta_prev, gamma_prev, rms of the accepted attempt (NaN without one), trial steps summed over
+ * the frame's attempts, fit status of the accepted attempt or else of the last attempt made, track state, start index of
+ * that attempt].  theta_prev, gamma_prev are the carry as the frame found it -- the output angles of the frame before it,
+ * in this call or, through `carry`, in the call before -- and the frame's own theta, gamma where there was none.
+ * The bits of out[b] and of the outgoing carry are a function of the recording, the incoming carry, the parameters and
+ * the config alone: not of B, the recording's place in the batch, the entry, or how the frames were split over calls or
+ * launches.  (The host splits T into launches of at most `track_chunk` frames, rovmpc_set_option, 1 .. 65536, default 256,
+ * so that no single launch runs long; the carry passes between them in device memory.)  All arithmetic in double, with L,
+ * c_lo, c_hi rounded to cfg.dtype as the fit holds them.  A launch is bounded by construction: at most
+ * track_chunk (1 + n_starts) (max_iter + 1) model evaluations per recording.
+ * Bad arguments (a null handle or required pointer, B < 0, T < 0, M outside 3 .. ROVMPC_FIT_MAX_MARKERS, a struct_size
+ * mismatch, tol < 0 or NaN, max_iter outside 1 .. 1000, n_starts outside 1 .. ROVMPC_TRACK_MAX_STARTS, a non-finite start,
+ * rms_max <= 0 or NaN, B T > 2^24) give ROVMPC_ERR_INVALID with a message and launch nothing; B = 0 or T = 0 is ROVMPC_OK
+ * and launches nothing.
+ * Not provided: smoothing, prediction (the start is the last estimate, not an extrapolation), jump gates, alias search. */
+#define ROVMPC_TRACK_MAX_STARTS 8
+#define ROVMPC_TRACK_OUT 9
+typedef enum rovmpc_track_state {
+    ROVMPC_TRACK_LOCKED = 0, ROVMPC_TRACK_ACQUIRED = 1, ROVMPC_TRACK_HELD = 2, ROVMPC_TRACK_NONE = 3
+} rovmpc_track_state;
+typedef struct rovmpc_track_params {
+    int32_t struct_size;             /* = sizeof(rovmpc_track_params), ABI check                         */
+    int32_t n_starts;                /* 1..ROVMPC_TRACK_MAX_STARTS                                       */
+    int32_t max_iter;                /* the fit's: 1..1000 trial steps per attempt                       */
+    int32_t reserved_;               /* 0                                                                */
+    double  tol;                     /* the fit's: radians, >= 0                                         */
+    double  rms_max;                 /* metres, > 0, +inf = no gate                                      */
+    double  starts[ROVMPC_TRACK_MAX_STARTS][2];   /* (theta, gamma) each, finite; the first n_starts are read */
+} rovmpc_track_params;
+void rovmpc_default_track_params(rovmpc_track_params *p);
+/* Host pointers: P0[B][T][3], P1[B][T][3], Y[B][T][M][3], carry[B][2] in and out or NULL (a fresh start, nothing returned),
+ * params or NULL (the defaults), out[B][T][ROVMPC_TRACK_OUT].  Uploads, the launches, one synchronise. */
+int rovmpc_track_markers(rovmpc_handle *h, const double *P0, const double *P1, const double *Y, int64_t B, int64_t T, int32_t M,
+                         double *carry, const rovmpc_track_params *params, double *out);
+/* The same on device pointers (all double), enqueued on the handle's stream without a synchronise.  d_exo[B][T][16] or NULL:
+ * the state rows of the closed loops (rovmpc_*_closed_loop*_device); slots 12..15 of every frame whose state is not NONE
+ * receive out[b][t][0..3], and nothing else of d_exo is written.  T = 1 with a kept d_carry is the live use, between a sensor
+ * upload and the next control step, which the same stream orders behind it. */
+int rovmpc_track_markers_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t B, int64_t T,
+                                int32_t M, double *d_carry, const rovmpc_track_params *params, double *d_out, double *d_exo);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
