@@ -23,5 +23,6 @@ from .trajgen import generate_rov_trajectories, trajectory_csv
 from ._lib import MPPIParams, CEMParams, FitParams, TrackParams
 from .mpc import MPC, MPPI, CEM, BatchedMPPI, BatchedCEM, NavCost, TetherCost, PlanLoopResult, GaussianSampler, DeviceGaussianSampler, synthetic_problem
 from .closed_loop import run_plan_closed_loop
+from .scoring import score_rows, select_model, RowScores
 
 __version__ = "0.1.0"

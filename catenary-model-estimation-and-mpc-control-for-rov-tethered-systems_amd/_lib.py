@@ -289,6 +289,11 @@ class TrackParams(C.Structure):
         return p
 
 
+SCORE_COLS = 8
+SCORE_TILE = 128
+SCORE_NAMES = ("r2", "rmse", "max_abs", "n_finite", "loss", "r2_deriv", "last", "ss_res")
+MAX_FEATURES = 32
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -363,6 +368,10 @@ _SIGNATURES = {
     "rovmpc_eval_expression": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P]),
     "rovmpc_lagrangian_rollout": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P]),
     "rovmpc_replay": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_int32, _P, _P]),
+    "rovmpc_score_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32,
+                                    _P, _P, _P]),
+    "rovmpc_score_rows_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P,
+                                           C.c_int32, _P, _P, _P]),
     "rovmpc_solve_catenary": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, _P, _P]),
     "rovmpc_rodrigues": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     "rovmpc_catenary_points": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, C.c_int32, _P, _P, _P]),

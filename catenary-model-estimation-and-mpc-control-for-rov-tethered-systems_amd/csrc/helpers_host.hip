@@ -4,6 +4,7 @@
 #include "util_kernels.h"
 #include "fit_kernels.h"
 #include "track_kernels.h"
+#include "score_kernels.h"
 
 // ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
 
@@ -600,4 +601,117 @@ extern "C" int rovmpc_track_markers_device(rovmpc_handle *h, const double *d_P0,
     a.P0 = d_P0; a.P1 = d_P1; a.Y = d_Y; a.carry = d_carry; a.out = d_out; a.exo = d_exo;
     launch_track(h, a);
     return launched(h, "marker track");
+}
+
+// ---- equation rows scored on recordings (score_kernels.h) --------------------------------------
+
+// the checks both entries share; then the programs and lengths packed for one copy: [consts][len][code][code_off][const_off]
+static int score_args(rovmpc_handle *h, const char *entry, const int32_t *code, const int32_t *code_off, const double *consts,
+                      const int32_t *const_off, int32_t R, const void *X, int32_t F, const void *time, const int64_t *len, int64_t T,
+                      int64_t B, const void *truth, int32_t integrator, const void *scores, std::vector<unsigned char> &blob, ScoreArgs &a) {
+    if (!code || !code_off || !const_off || !X || !time || !truth || !scores)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (code, code_off, const_off, X, time, truth or scores)", entry);
+    if (R < 1 || B < 1 || T < 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: R, B and T must be >= 1 (got %d, %lld, %lld)", entry, R, (long long)B, (long long)T);
+    if ((int64_t)R * B > ((int64_t)1 << 24)) FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 (row, recording) pairs in one call (got %d x %lld)", entry, R, (long long)B);
+    if (F < 1 || F > ROVMPC_MAX_FEATURES) FAIL(h, ROVMPC_ERR_INVALID, "%s: F must be in 1..%d (got %d)", entry, ROVMPC_MAX_FEATURES, F);
+    if (integrator < ROVMPC_RK4 || integrator > ROVMPC_TRAPEZOID) FAIL(h, ROVMPC_ERR_INVALID, "%s: unknown integrator %d", entry, integrator);
+    if (code_off[0] != 0 || const_off[0] != 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: code_off[0] and const_off[0] must be 0", entry);
+    for (int r = 0; r < R; ++r)
+        if (code_off[r + 1] < code_off[r] || const_off[r + 1] < const_off[r] || code_off[r + 1] - code_off[r] > ROVMPC_MAX_CODE ||
+            const_off[r + 1] - const_off[r] > ROVMPC_MAX_CODE)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: offsets of row %d are not monotone (or the row is longer than %d)", entry, r, ROVMPC_MAX_CODE);
+    if (const_off[R] > 0 && !consts) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (consts)", entry);
+    for (int r = 0; r < R; ++r)
+        if (const char *why = validate_code(code + code_off[r], code_off[r + 1] - code_off[r], F, const_off[r + 1] - const_off[r]))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: row %d: %s", entry, r, why);
+    if (len)
+        for (int64_t b = 0; b < B; ++b)
+            if (len[b] < 1 || len[b] > T) FAIL(h, ROVMPC_ERR_INVALID, "%s: len[%lld] must be in 1..%lld (got %lld)", entry, (long long)b, (long long)T, (long long)len[b]);
+    const size_t nk = (size_t)const_off[R], nl = len ? (size_t)B : 0, nc = (size_t)code_off[R], no = (size_t)R + 1;
+    const size_t o_len = (nk ? nk : 1) * sizeof(double), o_code = o_len + nl * sizeof(int64_t), o_coff = o_code + nc * sizeof(int32_t),
+                 o_koff = o_coff + no * sizeof(int32_t);
+    blob.assign(o_koff + no * sizeof(int32_t), 0);
+    if (nk) memcpy(blob.data(), consts, nk * sizeof(double));
+    if (nl) memcpy(blob.data() + o_len, len, nl * sizeof(int64_t));
+    memcpy(blob.data() + o_code, code, nc * sizeof(int32_t));
+    memcpy(blob.data() + o_coff, code_off, no * sizeof(int32_t));
+    memcpy(blob.data() + o_koff, const_off, no * sizeof(int32_t));
+    memset(&a, 0, sizeof(a));
+    a.T = T; a.B = B; a.F = F; a.integrator = integrator;
+    // (offsets into the packed copy until score_bind puts the device address under them)
+    a.consts = (const double *)0; a.len = len ? (const long long *)o_len : nullptr; a.code = (const int32_t *)o_code;
+    a.code_off = (const int32_t *)o_coff; a.const_off = (const int32_t *)o_koff;
+    return ROVMPC_OK;
+}
+
+static void score_bind(ScoreArgs &a, const unsigned char *d_blob, bool has_len) {
+    const unsigned char *base = d_blob;
+    a.len = has_len ? (const long long *)(base + (size_t)a.len) : nullptr;
+    a.code = (const int32_t *)(base + (size_t)a.code);
+    a.code_off = (const int32_t *)(base + (size_t)a.code_off);
+    a.const_off = (const int32_t *)(base + (size_t)a.const_off);
+    a.consts = (const double *)base;
+}
+
+static void launch_score(rovmpc_handle *h, int32_t R, const ScoreArgs &a) {
+    hipLaunchKernelGGL(score_rows_kernel, dim3((unsigned)((int64_t)R * a.B)), dim3(SCORE_NT), score_lds_bytes(a.F, a.integrator), h->stream, a);
+}
+
+extern "C" int rovmpc_score_rows(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                 const int32_t *const_off, int32_t R, const double *X, int32_t F, const double *time, const int64_t *len,
+                                 int64_t T, int64_t B, const double *truth, const double *target, const double *y0, int32_t integrator,
+                                 double *scores, double *est, double *pred) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    ScoreArgs a;
+    if (int rc = score_args(h, "rovmpc_score_rows", code, code_off, consts, const_off, R, X, F, time, len, T, B, truth, integrator, scores, blob, a))
+        return rc;
+    HelperCall c(h);
+    const size_t n = (size_t)B * T, rows = (size_t)R * B;
+    const auto dP = c.upload((const unsigned char *)blob.data(), blob.size());
+    const auto dX = c.upload(X, n * F);
+    const auto dT = c.upload(time, n);
+    const auto dY = c.upload(truth, n);
+    const auto dG = target ? c.upload(target, n) : DevArray<double>{nullptr, 0};
+    const auto d0 = y0 ? c.upload(y0, (size_t)B) : DevArray<double>{nullptr, 0};
+    const auto dS = c.buffer<double>(rows * ROVMPC_SCORE_COLS);
+    const auto dE = est ? c.buffer<double>(rows * T) : DevArray<double>{nullptr, 0};
+    const auto dR = pred ? c.buffer<double>(rows * T) : DevArray<double>{nullptr, 0};
+    score_bind(a, dP.p, len != nullptr);
+    a.X = dX.p; a.time = dT.p; a.truth = dY.p; a.target = dG.p; a.y0 = d0.p; a.scores = dS.p; a.est = dE.p; a.pred = dR.p;
+    if (c.ok()) launch_score(h, R, a);
+    c.download(scores, dS);
+    if (est) c.download(est, dE);
+    if (pred) c.download(pred, dR);
+    return c.finish();
+}
+
+extern "C" int rovmpc_score_rows_device(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                        const int32_t *const_off, int32_t R, const double *d_X, int32_t F, const double *d_time,
+                                        const int64_t *len, int64_t T, int64_t B, const double *d_truth, const double *d_target,
+                                        const double *d_y0, int32_t integrator, double *d_scores, double *d_est, double *d_pred) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    ScoreArgs a;
+    if (int rc = score_args(h, "rovmpc_score_rows_device", code, code_off, consts, const_off, R, d_X, F, d_time, len, T, B, d_truth, integrator,
+                            d_scores, blob, a))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (blob.size() > h->score_prog_bytes) {                  // (hipFree waits for the work that still reads the old copy)
+        if (h->d_score_prog) HIPCHK(h, hipFree(h->d_score_prog));
+        h->d_score_prog = nullptr; h->score_prog_bytes = 0;
+        HIPCHK(h, hipMalloc(&h->d_score_prog, blob.size()));
+        h->score_prog_bytes = blob.size();
+    }
+    // The source of the copy is kept in the handle until the copy has run: the caller's arrays may go when the call returns.
+    // Only a second call waits, and only for the copy of the call before (the stream orders the new copy behind that launch).
+    if (h->score_prog_ev) HIPCHK(h, hipEventSynchronize(h->score_prog_ev));
+    else HIPCHK(h, hipEventCreateWithFlags(&h->score_prog_ev, hipEventDisableTiming));
+    h->score_prog_host.swap(blob);
+    HIPCHK(h, hipMemcpyAsync(h->d_score_prog, h->score_prog_host.data(), h->score_prog_host.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->score_prog_ev, h->stream));
+    score_bind(a, (const unsigned char *)h->d_score_prog, len != nullptr);
+    a.X = d_X; a.time = d_time; a.truth = d_truth; a.target = d_target; a.y0 = d_y0; a.scores = d_scores; a.est = d_est; a.pred = d_pred;
+    launch_score(h, R, a);
+    return launched(h, "row scoring");
 }

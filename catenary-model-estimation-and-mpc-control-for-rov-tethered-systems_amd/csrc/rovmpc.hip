@@ -339,8 +339,9 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     void *ptrs[] = {h->d_U, h->d_J, h->d_traj_all, h->d_state, h->d_blk_traj,
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
                     h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
-                    h->d_nav_track, h->d_nav_spheres, h->d_tether_spheres, h->d_tether_traj};
+                    h->d_nav_track, h->d_nav_spheres, h->d_tether_spheres, h->d_tether_traj, h->d_score_prog};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
+    if (h->score_prog_ev) (void)hipEventDestroy(h->score_prog_ev);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     mailbox_free(h->samp_box);
     if (h->h_err) (void)hipHostFree(h->h_err);

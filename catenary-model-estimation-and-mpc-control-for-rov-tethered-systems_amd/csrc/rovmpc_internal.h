@@ -110,6 +110,10 @@ struct rovmpc_handle {
     double handoff_timeout_ms = 10000.0;      // give-up time of the GPU-side hand-off waits (rovmpc_set_option)
     int inject_skip_rolled = 0, inject_skip_consumed = 0;   // test hooks: the next N steps lose that publication
     int track_chunk = 256;                    // frames per launch of rovmpc_track_markers* (rovmpc_set_option)
+    void *d_score_prog = nullptr;             // rovmpc_score_rows_device: the programs and lengths of the last call,
+    size_t score_prog_bytes = 0;              // their host copy (the source of the upload) and the event behind that upload
+    std::vector<unsigned char> score_prog_host;
+    hipEvent_t score_prog_ev = nullptr;
     // rovmpc_mpc_step_sampled: two candidate tensors (the sampler of step s+1 reads the winner of step s for the warm
     // start) and the mailbox of the record (its sequence numbers are samp_steps)
     void *d_Us[2] = {nullptr, nullptr};

@@ -44,6 +44,28 @@ lagrangian_rollout_kernel(const int32_t *code_th, int n_th, const int32_t *code_
     }
 }
 
+// The replay laws' arithmetic, shared by the replay kernels below and score_rows_kernel (score_kernels.h) so that the two
+// cannot contract or associate differently: the increment of one first-order step and one step of the second-order chains.
+// Where a product is fused into the sum that follows it is written out (contraction is off inside): the velocity update of
+// the second-order laws is one fma, the angle update a rounded product and a sum -- what the replay kernels have always
+// computed, now independent of the code around the call.
+RV_DEV double replay_euler_increment(double k1, double dt) { return k1 * dt; }                   // main_fun.py:757-762
+RV_DEV double replay_rk4_increment(double dt, double k1, double k2, double k4) {                  // simulate_rk4_theta_gamma.py:66
+#pragma clang fp contract(off)
+    return (dt / 6) * (k1 + 2 * k2 + 2 * k2 + k4);
+}
+// (y, v) <- one step over dt with dd0 = dd[i-1], dd1 = dd[i]
+RV_DEV void replay_second_order_step(int integrator, double dd0, double dd1, double dt, double &y, double &v) {
+#pragma clang fp contract(off)
+    if (integrator == ROVMPC_DOUBLE_EULER) {
+        y = y + v * dt;
+        v = ::fma(dt, dd0, v);
+    } else {
+        v = ::fma(dt, (dd0 + dd1) / 2, v);
+        y = y + dt * v;
+    }
+}
+
 // Increments of rk4_integration (simulate_rk4_theta_gamma.py:56-66) / integrate_theta_gamma
 // (main_fun.py:757-762) for step i = 1..T-1, both expressions.  inc[0] is unused.
 __global__ void __launch_bounds__(128)
@@ -63,15 +85,15 @@ replay_increments_kernel(const double *__restrict__ Xs, const double *__restrict
         const double k1t = interp_eval<double>(code_th, n_th, consts, x0, 1, stack, NT);
         const double k1g = interp_eval<double>(code_ga, n_ga, consts, x0, 1, stack, NT);
         if (integrator == ROVMPC_EULER) {
-            it = k1t * dt; ig = k1g * dt;
+            it = replay_euler_increment(k1t, dt); ig = replay_euler_increment(k1g, dt);
         } else {
             for (int f = 0; f < F; ++f) feat[(size_t)f * NT] = (x0[f] + x1[f]) / 2;   // :62-63
             const double k2t = interp_eval<double>(code_th, n_th, consts, feat, NT, stack, NT);
             const double k2g = interp_eval<double>(code_ga, n_ga, consts, feat, NT, stack, NT);
             const double k4t = interp_eval<double>(code_th, n_th, consts, x1, 1, stack, NT);
             const double k4g = interp_eval<double>(code_ga, n_ga, consts, x1, 1, stack, NT);
-            it = (dt / 6) * (k1t + 2 * k2t + 2 * k2t + k4t);                          // :66
-            ig = (dt / 6) * (k1g + 2 * k2g + 2 * k2g + k4g);
+            it = replay_rk4_increment(dt, k1t, k2t, k4t);                             // :66
+            ig = replay_rk4_increment(dt, k1g, k2g, k4g);
         }
     }
     if (i0 < T) { inc_th[i0] = it; inc_ga[i0] = ig; }
@@ -93,13 +115,7 @@ replay_second_order_kernel(const double *dd_th, const double *dd_ga, const doubl
     out[0] = y;
     for (long long i = 1; i < T; ++i) {
         const double dt = time[i] - time[i - 1];
-        if (integrator == ROVMPC_DOUBLE_EULER) {
-            y = y + v * dt;
-            v = v + dd[i - 1] * dt;
-        } else {
-            v = v + (dd[i - 1] + dd[i]) / 2 * dt;
-            y = y + dt * v;
-        }
+        replay_second_order_step(integrator, dd[i - 1], dd[i], dt, y, v);
         out[i] = y;
     }
 }

@@ -965,6 +965,46 @@ class Engine:
         return track, (rows[0] if single else rows)
 
 
+    def score_rows(self, programs, X, time, truth, integrator: int = _lib.RK4, target=None, lengths=None, y0=None,
+                   return_est: bool = False, return_pred: bool = False, device: bool = False):
+        """R compiled rows on B recordings (rovmpc_score_rows; law in include/rovmpc.h).  ``programs``: a sequence of
+        (code, consts) per row, each row with its own constants; X (B, T, F), time, truth and target (B, T), lengths and y0
+        (B,) or None, checked and laid out by ``scoring.score_rows``.  Returns (scores (R, B, 8), est or None, pred or None).
+        ``device=True`` goes through rovmpc_score_rows_device on torch buffers: the same bits."""
+        code_off, const_off = [0], [0]
+        for code, consts in programs:
+            code_off.append(code_off[-1] + len(code)); const_off.append(const_off[-1] + len(consts))
+        code = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in programs]), np.int32)
+        consts = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float64).reshape(-1) for _, k in programs] + [np.zeros(1)]))
+        code_off, const_off = np.asarray(code_off, np.int32), np.asarray(const_off, np.int32)
+        R, (B, T, F) = len(programs), X.shape
+        lens = None if lengths is None else np.ascontiguousarray(lengths, np.int64)
+        shape = (R, B, T)
+        if not device:
+            scores = np.empty((R, B, _lib.SCORE_COLS))
+            est = np.empty(shape) if return_est else None
+            pred = np.empty(shape) if return_pred else None
+            self._check(self.lib.rovmpc_score_rows(self._h, _ptr(code), _ptr(code_off), _ptr(consts), _ptr(const_off), R, _ptr(X), F,
+                                                   _ptr(time), _ptr(lens), T, B, _ptr(truth), _ptr(target), _ptr(y0), int(integrator),
+                                                   _ptr(scores), _ptr(est), _ptr(pred)))
+            return scores, est, pred
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        up = lambda x: None if x is None else torch.tensor(x, device=dev)
+        dp = lambda t: None if t is None else t.data_ptr()
+        dX, dT, dY, dG, d0 = up(X), up(time), up(truth), up(target), up(y0)
+        dS = torch.empty((R, B, _lib.SCORE_COLS), dtype=torch.float64, device=dev)
+        dE = torch.empty(shape, dtype=torch.float64, device=dev) if return_est else None
+        dP = torch.empty(shape, dtype=torch.float64, device=dev) if return_pred else None
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_score_rows_device(self._h, _ptr(code), _ptr(code_off), _ptr(consts), _ptr(const_off), R, dp(dX), F,
+                                                      dp(dT), _ptr(lens), T, B, dp(dY), dp(dG), dp(d0), int(integrator), dp(dS), dp(dE),
+                                                      dp(dP)))
+        torch.cuda.synchronize(dev)                     # (the device: the scoring runs on the handle's own stream)
+        back = lambda t: None if t is None else t.cpu().numpy()
+        return back(dS), back(dE), back(dP)
+
+
 _default_engine: Optional[Engine] = None
 
 

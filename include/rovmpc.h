@@ -876,6 +876,64 @@ int rovmpc_replay(rovmpc_handle *h, const double *Xs, const double *time, int64_
                   double theta0, double gamma0, int32_t integrator,
                   double *theta_out, double *gamma_out);
 
+/* ---- score equation rows on recordings: the replay above for R rows on B recordings, reduced to scores on the device ----
+ * What the reference's evaluation scripts do row by row (dd_test_cluster.py:212-247 over both Pareto fronts; one row in
+ * simulate_rk4_theta_gamma.py:84-85, test_cluster.py:145-146, model_test.py:34-35, simulate_theta_gamma.py:108-109; the
+ * derivative's own R^2 in simply.py:85,98): integrate the row along a held-out recording, print r2_score(truth, est).
+ * A ROW is one expression scored against one series; theta rows and gamma rows are separate calls.  Row r is the program
+ * code[code_off[r] .. code_off[r+1]) with its own constants consts[const_off[r] .. const_off[r+1]) (PUSH_C indexes that
+ * slice); every row must pass the validation of rovmpc_eval_expression for F features.  No loaded model is needed.
+ * Recording b: X[b][T][F] scaled rows, time[b][T], truth[b][T], target[b][T] (the derivative the rows were fitted to; may be
+ * NULL), of which the first n = len[b] rows count (len NULL: n = T); y0[b] the start (y0 NULL: truth[b][0]).
+ * integrator: the four values of rovmpc_replay, the same references.
+ * Law.
+ *   est.   e = est[r][b][0 .. n) is, bit for bit, what rovmpc_replay of the same build returns for that expression on the
+ *          first n rows of X[b], time[b] from y0[b]: the same increments (RK4: k1 = f(x_{i-1}), k2 = k3 = f((x_{i-1} + x_i)
+ *          / 2), k4 = f(x_i), inc_i = (dt_i / 6)(k1 + 2 k2 + 2 k2 + k4); Euler: inc_i = f(x_{i-1}) dt_i), summed left to right,
+ *          and the same two-state recurrences from w = 0 for the second-order laws (the velocity update one fused
+ *          multiply-add, the angle update a rounded product and a sum, in both entries).  p = pred[r][b][i] = f_r(X[b][i]) for
+ *          i < n.  Entries of est and pred at or beyond n are NaN.  Both buffers are optional.
+ *   scores[r][b][ROVMPC_SCORE_COLS], with y = truth, g = target, all sums over i = 0 .. n - 1:
+ *          0 r2        1 - SS_res / SS_tot, SS_res = sum (y - e)^2, SS_tot = sum (y - ybar)^2 with ybar = (sum y) / n computed
+ *                      first; n < 2: NaN; SS_tot = 0: 1 if SS_res = 0, else 0 (sklearn's r2_score, force_finite)
+ *          1 rmse      sqrt(SS_res / n)
+ *          2 max_abs   max |y - e|
+ *          3 n_finite  the number of leading finite entries of e, at most n
+ *          4 loss      sum (g - p)^2 / n, the `loss` column of the PySR tables
+ *          5 r2_deriv  r2_score(g, p) by the rule of column 0 (simply.py:85)
+ *          6 last      e[n - 1]
+ *          7 ss_res    SS_res
+ *   Non-finite values.  n_finite < n makes columns 0, 1, 2, 6, 7 NaN; a non-finite p among the n rows, or no target, makes
+ *          columns 4, 5 NaN.  A non-finite truth or target propagates through the sums it enters.
+ *   Summation order.  Every sum (also sum y and sum g) is taken as ROVMPC_SCORE_TILE partial sums, partial j over the terms
+ *          i = j, j + TILE, j + 2 TILE, ... in increasing i from +0, then the tree v[j] += v[j + s] for s = TILE / 2, TILE / 4,
+ *          ..., 1.  Squares, differences and sums are rounded one by one (no fused multiply-add in the metric arithmetic).
+ *          So scores[r][b] is a function of row r, the n rows of recording b and the integrator alone: not of R, B, T, the
+ *          place of the row or the recording in the call, or the entry.
+ *   fp64 only.  One workgroup per (row, recording) walks the recording in tiles of ROVMPC_SCORE_TILE time rows: all lanes
+ *          evaluate f (two evaluations per RK4 step: k4 of a step is k1 of the next), one lane runs the recurrence.
+ * ROVMPC_ERR_INVALID with a message, before anything is launched and with nothing written: a null handle or required pointer
+ * (code, code_off, consts when any row has constants, const_off, X, time, truth, scores), R < 1, B < 1, T < 1, R B > 2^24,
+ * F outside 1 .. ROVMPC_MAX_FEATURES, an integrator that is none of the four, offsets that do not start at 0 or decrease,
+ * len[b] outside 1 .. T, a row that fails validation (its index is in the message).
+ * Not provided: the N-step-ahead skill of a row pair fed its own predictions (the rollout's law), the double cumulative_trapezoid
+ * without offset of dd_test_cluster.py:217-219 (no counterpart in rovmpc_replay), refitting constants, fp32. */
+#define ROVMPC_SCORE_COLS 8
+#define ROVMPC_SCORE_TILE 128
+/* Host pointers.  Uploads, one launch, one synchronise. */
+int rovmpc_score_rows(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                      const int32_t *const_off, int32_t R, const double *X, int32_t F, const double *time, const int64_t *len,
+                      int64_t T, int64_t B, const double *truth, const double *target, const double *y0, int32_t integrator,
+                      double *scores, double *est, double *pred);
+/* The recordings and the results in device memory (all double), enqueued on the handle's stream without a synchronise.  The
+ * programs (code, code_off, consts, const_off) and len stay HOST arrays: they are checked here, before anything is launched,
+ * and copied into a buffer of the handle on the same stream; they may be freed when the call returns.  (A second call on
+ * the handle waits on the host until the first call's copy of the programs has run, not for its kernel.) */
+int rovmpc_score_rows_device(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                             const int32_t *const_off, int32_t R, const double *d_X, int32_t F, const double *d_time,
+                             const int64_t *len, int64_t T, int64_t B, const double *d_truth, const double *d_target,
+                             const double *d_y0, int32_t integrator, double *d_scores, double *d_est, double *d_pred);
+
 /* solve_catenary(l, delta_H, L) (main_fun.py:418-431) and, if T_out != NULL, the tension
  * rule of main_fun.py:302-305 with cfg.cable_wet_weight. */
 int rovmpc_solve_catenary(rovmpc_handle *h, const double *l, const double *delta_H, double L,
