@@ -595,6 +595,10 @@ template <typename T> __host__ __device__ inline size_t rollout_lds_elems(int N,
     return e;
 }
 
+// What the theta chain of the compiled-in model needs before its first step and what hangs on the state, the scaler and
+// constants alone (rollout_body::theta_setup; the names are theta_path's).
+template <typename T> struct ThetaStart { Trig<T> trig; T m16, i16, hKT, K16a, K16b, X3, SX, hf, hq, HA, W, st, ct; };
+
 // LEAN: the plain single-problem step (rovmpc_step_device and the host-pointer entry points): one problem, no slot image,
 // no hand-off flags, no host mirror, no plant update -- those branches are compiled out (measured on one box: the full
 // kernel is 0.3 us slower per C2 step than the round-1 kernel, which had none of them).
@@ -1122,6 +1126,33 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
     const bool chase = LONGH && MODEL == MODEL_BUILTIN && CK <= 16 && wideB && N * CK - early > NT;
     // the integrating wave reports its progress only as far as somebody waits for it (the nodes of the early batch)
     const int prog_until = chase ? N : (early > 0 ? (early + CK - 1) / CK : 0);
+    // Compiled-in model: what the theta chain needs before its first step and what hangs on the state, the scaler and
+    // constants alone -- the pinned sine / cosine coefficients, the step constants, x3 of node 0 with its sine and its share
+    // of the RK4 sum, sincos(theta_0), the role factors of the lane (ThetaStart; see theta_path).  In the single-problem step
+    // the theta waves form it here, behind their phase 2a items, where they would otherwise wait at the barrier for the gamma
+    // wave; behind the last barrier of the prologue only what depends on phase 2b is left.  Every other instance calls this
+    // from theta_path: the hand-off step learns theta_0 from the ring, and on the batched launches, where other workgroups
+    // fill a wave's wait at the barrier, the early set-up measured 0.7 % slower (B = 8).
+    constexpr bool TS_EARLY = LEAN && !HANDOFF && !SAMPLE;
+    auto theta_setup = [&]() -> ThetaStart<T> {
+        ThetaStart<T> t = {Trig<T>(true)};
+        const int role = tid & 3;
+        const T m3 = sMean[3], i3 = sInv[3];
+        t.m16 = sMean[16]; t.i16 = sInv[16];
+        const T KT = T(0.048152514);
+        t.hKT = a.integrator == ROVMPC_EULER ? kk.h * KT : (kk.h / T(6)) * KT;
+        t.K16a = T(3) * t.i16; t.K16b = T(-6) * t.m16 * t.i16;
+        t.X3 = (V0x - m3) * i3;
+        t.SX = t.trig.sin(t.X3);
+        t.hf = (role & 1) ? T(0.5) : T(1); t.hq = (role & 1) ? T(0.5) : T(0);
+        t.HA = t.hq * t.X3;
+        t.W = m_fma(T(-3), t.X3, T(-0.5) * t.K16b) - t.SX;
+        t.st = T(0); t.ct = T(1);
+        if (VT == ROVMPC_VT_COMPOSE) t.trig.sincos(th0, &t.st, &t.ct);
+        return t;
+    };
+    ThetaStart<T> ts = {Trig<T>(false)};
+    if (MODEL == MODEL_BUILTIN && TS_EARLY && tid < nintB) ts = theta_setup();
     RV_STAMP(12);
     if (MODEL == MODEL_BUILTIN && share_sines) {
         while (__hip_atomic_load(s_chain_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(4);
@@ -1302,15 +1333,13 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             const int cc = (tid >> 6) * 16 + c16;               // candidate of this lane
             const bool live = cc < CK;
             const int c = live ? cc : CK - 1;                   // clamp reads of padding lanes
-            const Trig<T> trig(true);
-            const T m3 = sMean[3], i3 = sInv[3], m16 = sMean[16], i16 = sInv[16];
-            const T KT = T(0.048152514);
-            const T hKT = euler ? kk.h * KT : (kk.h / T(6)) * KT;
-            const T K16a = T(3) * i16, K16b = T(-6) * m16 * i16;
             if (HANDOFF && a.wait_theta) {
                 ring_wait(a.seq_theta);
                 if (a.from_ring) { th0 = ring_get(0); thm0 = ring_get(2); }
             }
+            if (!TS_EARLY) ts = theta_setup();             // (hand-off: behind ring_wait, theta_0 has only just arrived)
+            const Trig<T> &trig = ts.trig;
+            const T m16 = ts.m16, i16 = ts.i16, hKT = ts.hKT, K16a = ts.K16a, K16b = ts.K16b;
             // Loop-carried values live in two-element arrays indexed by the step's parity p (a literal in each of the two
             // inlined copies of the step): TH[p] = theta of the previous node, TH[p ^ 1] = theta of this node; X3[p], SX[p] =
             // x3 and its sine at the step's start; O*[p] = the step's operands, fetched one step ahead into O*[p ^ 1].  A step
@@ -1319,8 +1348,8 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             T TH[2] = {thm0, th0};
             if (live && role == 0) RV_PL(sY, 0, 0, c) = th0;
             T X3[2], SX[2];
-            X3[0] = (V0x - m3) * i3; X3[1] = T(0);
-            SX[0] = trig.sin(X3[0]); SX[1] = T(0);
+            X3[0] = ts.X3; X3[1] = T(0);
+            SX[0] = ts.SX; SX[1] = T(0);
             // RK4 with the interpolated delay slot, arranged for the chain's DEPTH (one wave issues a dependent instruction
             // every ~9.5 cycles, an independent one every ~5: tools/micro/fma_latency.hip):
             //  * the lane's sine argument -- x3b on the end lane, (x3a + x3b) / 2 on the midpoint lane -- is ONE FMA,
@@ -1328,10 +1357,10 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             //  * every node's share of the sum, w = -sin x3 - 3 x3 - K16b / 2, is formed once and carried to the next step;
             //    what waits for the step's sines is  S = (base - 4 sin x3m) + w_end  with base = G_n + w_start - K16a (theta_{n-1}
             //    + theta_n) ready long before them.
-            const T hf = (role & 1) ? T(0.5) : T(1), hq = (role & 1) ? T(0.5) : T(0);
+            const T hf = ts.hf, hq = ts.hq;
             const T mK16bh = T(-0.5) * K16b;
-            T HA[2] = {hq * X3[0], T(0)};
-            T W[2] = {m_fma(T(-3), X3[0], mK16bh) - SX[0], T(0)};
+            T HA[2] = {ts.HA, T(0)};
+            T W[2] = {ts.W, T(0)};
             // operands of step n, fetched one step ahead (nothing in the loop waits on another wave)
             T OA[2] = {T(0), T(0)}, OB[2] = {T(0), T(0)}, OC[2] = {T(0), T(0)}, GG[2] = {T(0), T(0)};
             auto fetch = [&](int n, int q) {
@@ -1345,8 +1374,7 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             // (1/60 s; 0.017 from theta = 0.6, 0.04 from 1.5: tests/test_rollout_steps_gpu.py), so after a full evaluation
             // at step 0 (and every 16th step, or whenever a lane's |d| reaches 2^-6) the pair is advanced by the
             // angle-addition formulas with the odd/even Taylor polynomials of d to d^7 / d^6 (truncation < 1e-19 there).
-            T st = T(0), ct = T(1);
-            if (VT == ROVMPC_VT_COMPOSE) trig.sincos(th0, &st, &ct);
+            T st = ts.st, ct = ts.ct;
             // One loop for the common mode (RK4, interpolated delay slot, bounded sine arguments) with its flags
             // as literals, one for everything else with run-time flags.
             auto one_step = [&](auto FAST, auto PAR, int n) {
