@@ -294,6 +294,28 @@ SCORE_TILE = 128
 SCORE_NAMES = ("r2", "rmse", "max_abs", "n_finite", "loss", "r2_deriv", "last", "ss_res")
 MAX_FEATURES = 32
 
+REFIT_MAX_PARAMS = 8
+REFIT_OUT = 6
+REFIT_NAMES = ("loss0", "loss", "orth", "iters", "status", "n_params")
+REFIT_CONVERGED, REFIT_MAX_ITER, REFIT_STALLED, REFIT_NONFINITE, REFIT_NO_PARAMS = range(5)
+
+
+class RefitParams(C.Structure):
+    """Mirror of ``rovmpc_refit_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("max_iter", C.c_int32), ("gtol", C.c_double), ("xtol", C.c_double)]
+
+    @classmethod
+    def make(cls, max_iter: int = 50, gtol: float = 1e-10, xtol: float = 1e-12) -> "RefitParams":
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) <= 1000:
+            raise ValueError(f"max_iter must be an integer in 1..1000 (got {max_iter!r})")
+        gtol, xtol = float(gtol), float(xtol)
+        if not gtol >= 0 or not xtol >= 0:
+            raise ValueError(f"gtol and xtol must be >= 0 (got {gtol!r}, {xtol!r})")
+        p = cls()
+        p.struct_size, p.max_iter, p.gtol, p.xtol = C.sizeof(cls), int(max_iter), gtol, xtol
+        return p
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -372,6 +394,11 @@ _SIGNATURES = {
                                     _P, _P, _P]),
     "rovmpc_score_rows_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P,
                                            C.c_int32, _P, _P, _P]),
+    "rovmpc_default_refit_params": (None, [C.POINTER(RefitParams)]),
+    "rovmpc_refit_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32,
+                                    C.POINTER(RefitParams), _P, _P]),
+    "rovmpc_refit_rows_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P,
+                                           C.c_int32, C.POINTER(RefitParams), _P, _P]),
     "rovmpc_solve_catenary": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, _P, _P]),
     "rovmpc_rodrigues": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     "rovmpc_catenary_points": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, C.c_int32, _P, _P, _P]),

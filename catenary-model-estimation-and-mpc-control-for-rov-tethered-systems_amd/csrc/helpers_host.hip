@@ -5,6 +5,7 @@
 #include "fit_kernels.h"
 #include "track_kernels.h"
 #include "score_kernels.h"
+#include "refit_kernels.h"
 
 // ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
 
@@ -605,16 +606,17 @@ extern "C" int rovmpc_track_markers_device(rovmpc_handle *h, const double *d_P0,
 
 // ---- equation rows scored on recordings (score_kernels.h) --------------------------------------
 
-// the checks both entries share; then the programs and lengths packed for one copy: [consts][len][code][code_off][const_off]
-static int score_args(rovmpc_handle *h, const char *entry, const int32_t *code, const int32_t *code_off, const double *consts,
-                      const int32_t *const_off, int32_t R, const void *X, int32_t F, const void *time, const int64_t *len, int64_t T,
-                      int64_t B, const void *truth, int32_t integrator, const void *scores, std::vector<unsigned char> &blob, ScoreArgs &a) {
-    if (!code || !code_off || !const_off || !X || !time || !truth || !scores)
-        FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (code, code_off, const_off, X, time, truth or scores)", entry);
+// The checks of the scoring and the refit entries, in the order the scoring entry has always made them: the sizes of the call,
+// (its integrator,) the rows, the lengths.  The non-null pointers are the entry's own to check first.
+static int check_row_call(rovmpc_handle *h, const char *entry, int32_t R, int32_t F, int64_t T, int64_t B) {
     if (R < 1 || B < 1 || T < 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: R, B and T must be >= 1 (got %d, %lld, %lld)", entry, R, (long long)B, (long long)T);
     if ((int64_t)R * B > ((int64_t)1 << 24)) FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 (row, recording) pairs in one call (got %d x %lld)", entry, R, (long long)B);
     if (F < 1 || F > ROVMPC_MAX_FEATURES) FAIL(h, ROVMPC_ERR_INVALID, "%s: F must be in 1..%d (got %d)", entry, ROVMPC_MAX_FEATURES, F);
-    if (integrator < ROVMPC_RK4 || integrator > ROVMPC_TRAPEZOID) FAIL(h, ROVMPC_ERR_INVALID, "%s: unknown integrator %d", entry, integrator);
+    return ROVMPC_OK;
+}
+
+static int check_programs(rovmpc_handle *h, const char *entry, const int32_t *code, const int32_t *code_off, const double *consts,
+                          const int32_t *const_off, int32_t R, int32_t F) {
     if (code_off[0] != 0 || const_off[0] != 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: code_off[0] and const_off[0] must be 0", entry);
     for (int r = 0; r < R; ++r)
         if (code_off[r + 1] < code_off[r] || const_off[r + 1] < const_off[r] || code_off[r + 1] - code_off[r] > ROVMPC_MAX_CODE ||
@@ -624,9 +626,19 @@ static int score_args(rovmpc_handle *h, const char *entry, const int32_t *code, 
     for (int r = 0; r < R; ++r)
         if (const char *why = validate_code(code + code_off[r], code_off[r + 1] - code_off[r], F, const_off[r + 1] - const_off[r]))
             FAIL(h, ROVMPC_ERR_INVALID, "%s: row %d: %s", entry, r, why);
+    return ROVMPC_OK;
+}
+
+static int check_lengths(rovmpc_handle *h, const char *entry, const int64_t *len, int64_t T, int64_t B) {
     if (len)
         for (int64_t b = 0; b < B; ++b)
             if (len[b] < 1 || len[b] > T) FAIL(h, ROVMPC_ERR_INVALID, "%s: len[%lld] must be in 1..%lld (got %lld)", entry, (long long)b, (long long)T, (long long)len[b]);
+    return ROVMPC_OK;
+}
+
+// the checked programs and lengths packed for one copy: [consts][len][code][code_off][const_off]
+static void pack_programs(const int32_t *code, const int32_t *code_off, const double *consts, const int32_t *const_off, int32_t R,
+                          int32_t F, const int64_t *len, int64_t T, int64_t B, std::vector<unsigned char> &blob, ScoreArgs &a) {
     const size_t nk = (size_t)const_off[R], nl = len ? (size_t)B : 0, nc = (size_t)code_off[R], no = (size_t)R + 1;
     const size_t o_len = (nk ? nk : 1) * sizeof(double), o_code = o_len + nl * sizeof(int64_t), o_coff = o_code + nc * sizeof(int32_t),
                  o_koff = o_coff + no * sizeof(int32_t);
@@ -637,10 +649,24 @@ static int score_args(rovmpc_handle *h, const char *entry, const int32_t *code, 
     memcpy(blob.data() + o_coff, code_off, no * sizeof(int32_t));
     memcpy(blob.data() + o_koff, const_off, no * sizeof(int32_t));
     memset(&a, 0, sizeof(a));
-    a.T = T; a.B = B; a.F = F; a.integrator = integrator;
+    a.T = T; a.B = B; a.F = F;
     // (offsets into the packed copy until score_bind puts the device address under them)
     a.consts = (const double *)0; a.len = len ? (const long long *)o_len : nullptr; a.code = (const int32_t *)o_code;
     a.code_off = (const int32_t *)o_coff; a.const_off = (const int32_t *)o_koff;
+}
+
+// what both scoring entries check, then the packed copy
+static int score_args(rovmpc_handle *h, const char *entry, const int32_t *code, const int32_t *code_off, const double *consts,
+                      const int32_t *const_off, int32_t R, const void *X, int32_t F, const void *time, const int64_t *len, int64_t T,
+                      int64_t B, const void *truth, int32_t integrator, const void *scores, std::vector<unsigned char> &blob, ScoreArgs &a) {
+    if (!code || !code_off || !const_off || !X || !time || !truth || !scores)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (code, code_off, const_off, X, time, truth or scores)", entry);
+    if (int rc = check_row_call(h, entry, R, F, T, B)) return rc;
+    if (integrator < ROVMPC_RK4 || integrator > ROVMPC_TRAPEZOID) FAIL(h, ROVMPC_ERR_INVALID, "%s: unknown integrator %d", entry, integrator);
+    if (int rc = check_programs(h, entry, code, code_off, consts, const_off, R, F)) return rc;
+    if (int rc = check_lengths(h, entry, len, T, B)) return rc;
+    pack_programs(code, code_off, consts, const_off, R, F, len, T, B, blob, a);
+    a.integrator = integrator;
     return ROVMPC_OK;
 }
 
@@ -651,6 +677,24 @@ static void score_bind(ScoreArgs &a, const unsigned char *d_blob, bool has_len) 
     a.code_off = (const int32_t *)(base + (size_t)a.code_off);
     a.const_off = (const int32_t *)(base + (size_t)a.const_off);
     a.consts = (const double *)base;
+}
+
+// A device entry's packed host arrays into the handle's buffer, on h->stream (h->d_score_prog is the copy afterwards).
+static int stage_programs(rovmpc_handle *h, std::vector<unsigned char> &blob) {
+    if (blob.size() > h->score_prog_bytes) {                  // (hipFree waits for the work that still reads the old copy)
+        if (h->d_score_prog) HIPCHK(h, hipFree(h->d_score_prog));
+        h->d_score_prog = nullptr; h->score_prog_bytes = 0;
+        HIPCHK(h, hipMalloc(&h->d_score_prog, blob.size()));
+        h->score_prog_bytes = blob.size();
+    }
+    // The source of the copy is kept in the handle until the copy has run: the caller's arrays may go when the call returns.
+    // Only a second call waits, and only for the copy of the call before (the stream orders the new copy behind that launch).
+    if (h->score_prog_ev) HIPCHK(h, hipEventSynchronize(h->score_prog_ev));
+    else HIPCHK(h, hipEventCreateWithFlags(&h->score_prog_ev, hipEventDisableTiming));
+    h->score_prog_host.swap(blob);
+    HIPCHK(h, hipMemcpyAsync(h->d_score_prog, h->score_prog_host.data(), h->score_prog_host.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->score_prog_ev, h->stream));
+    return ROVMPC_OK;
 }
 
 static void launch_score(rovmpc_handle *h, int32_t R, const ScoreArgs &a) {
@@ -697,21 +741,157 @@ extern "C" int rovmpc_score_rows_device(rovmpc_handle *h, const int32_t *code, c
                             d_scores, blob, a))
         return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (blob.size() > h->score_prog_bytes) {                  // (hipFree waits for the work that still reads the old copy)
-        if (h->d_score_prog) HIPCHK(h, hipFree(h->d_score_prog));
-        h->d_score_prog = nullptr; h->score_prog_bytes = 0;
-        HIPCHK(h, hipMalloc(&h->d_score_prog, blob.size()));
-        h->score_prog_bytes = blob.size();
-    }
-    // The source of the copy is kept in the handle until the copy has run: the caller's arrays may go when the call returns.
-    // Only a second call waits, and only for the copy of the call before (the stream orders the new copy behind that launch).
-    if (h->score_prog_ev) HIPCHK(h, hipEventSynchronize(h->score_prog_ev));
-    else HIPCHK(h, hipEventCreateWithFlags(&h->score_prog_ev, hipEventDisableTiming));
-    h->score_prog_host.swap(blob);
-    HIPCHK(h, hipMemcpyAsync(h->d_score_prog, h->score_prog_host.data(), h->score_prog_host.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->score_prog_ev, h->stream));
+    if (int rc = stage_programs(h, blob)) return rc;
     score_bind(a, (const unsigned char *)h->d_score_prog, len != nullptr);
     a.X = d_X; a.time = d_time; a.truth = d_truth; a.target = d_target; a.y0 = d_y0; a.scores = d_scores; a.est = d_est; a.pred = d_pred;
     launch_score(h, R, a);
     return launched(h, "row scoring");
+}
+
+// ---- constants of equation rows refitted on recordings (refit_kernels.h) -----------------------
+
+extern "C" void rovmpc_default_refit_params(rovmpc_refit_params *p) {
+    if (!p) return;
+    p->struct_size = (int32_t)sizeof(rovmpc_refit_params);
+    p->max_iter = 50;
+    p->gtol = 1e-10;
+    p->xtol = 1e-12;
+}
+
+namespace {
+// a checked call: the kernel's arguments with offsets into the packed copy where refit_bind puts device addresses
+struct RefitPlan {
+    ScoreArgs s;                                  // the programs and lengths, packed as for rovmpc_score_rows
+    size_t o_group, o_fidx, o_nfree;              // behind them: group offsets, free indices per row, their counts
+    bool has_len;
+    RefitArgs a;
+};
+}  // namespace
+
+// the checks both entries share; then everything the kernel reads from host arrays packed for one copy
+static int refit_args(rovmpc_handle *h, const char *entry, const int32_t *code, const int32_t *code_off, const double *consts,
+                      const int32_t *const_off, const uint8_t *free_mask, int32_t R, const void *X, int32_t F, const int64_t *len,
+                      int64_t T, int64_t B, const void *target, const int32_t *group_off, int32_t G, const rovmpc_refit_params *params,
+                      const void *consts_out, const void *out, std::vector<unsigned char> &blob, RefitPlan &plan) {
+    if (!code || !code_off || !const_off || !X || !target || !consts_out || !out)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (code, code_off, const_off, X, target, consts_out or out)", entry);
+    if (int rc = check_row_call(h, entry, R, F, T, B)) return rc;
+    if (int rc = check_programs(h, entry, code, code_off, consts, const_off, R, F)) return rc;
+    if (int rc = check_lengths(h, entry, len, T, B)) return rc;
+    if (G < 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: G must be >= 1 (got %d)", entry, G);
+    if ((int64_t)R * G > ((int64_t)1 << 24)) FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 (row, group) pairs in one call (got %d x %d)", entry, R, G);
+    if (!group_off && G != 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off is NULL, which pools all recordings: G must be 1 (got %d)", entry, G);
+    if (group_off) {
+        if (group_off[0] != 0 || (int64_t)group_off[G] != B)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off must run from 0 to B = %lld (got %d .. %d)", entry, (long long)B, group_off[0], group_off[G]);
+        for (int g = 0; g < G; ++g)
+            if (group_off[g + 1] <= group_off[g]) FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off must increase (group %d is empty or runs backwards)", entry, g);
+    }
+    rovmpc_refit_params p;
+    rovmpc_default_refit_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(rovmpc_refit_params))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: rovmpc_refit_params.struct_size %d != %d (ABI mismatch)", entry, params->struct_size, (int)sizeof(rovmpc_refit_params));
+        p = *params;
+    }
+    if (p.max_iter < 1 || p.max_iter > 1000) FAIL(h, ROVMPC_ERR_INVALID, "%s: max_iter must be in 1..1000 (got %d)", entry, p.max_iter);
+    if (!(p.gtol >= 0.0) || !(p.xtol >= 0.0)) FAIL(h, ROVMPC_ERR_INVALID, "%s: gtol and xtol must be >= 0 (got %g, %g)", entry, p.gtol, p.xtol);
+    // per row: the free constants in pool order, and the stack simulation once more with one bit per slot -- whether a free
+    // constant reaches the value -- for the exponent of a POW; its deepest point sizes the kernel's operand stacks
+    std::vector<int32_t> fidx((size_t)R * ROVMPC_REFIT_MAX_PARAMS, 0), nfree((size_t)R, 0);
+    int depth = 1;
+    for (int r = 0; r < R; ++r) {
+        const int k0 = const_off[r], nk = const_off[r + 1] - k0;
+        int P = 0;
+        for (int k = 0; k < nk; ++k) {
+            if (free_mask && !free_mask[k0 + k]) continue;
+            if (P < ROVMPC_REFIT_MAX_PARAMS) fidx[(size_t)r * ROVMPC_REFIT_MAX_PARAMS + P] = k;
+            ++P;
+        }
+        if (P > ROVMPC_REFIT_MAX_PARAMS)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: row %d: %d free constants (at most %d)", entry, r, P, ROVMPC_REFIT_MAX_PARAMS);
+        nfree[r] = P;
+        unsigned char st[ROVMPC_MAX_STACK];
+        int sp = 0;
+        for (int pc = code_off[r]; pc < code_off[r + 1]; ++pc) {
+            const int op = code[pc] & 0xff, arg = code[pc] >> 8;
+            if (op == ROVMPC_OP_PUSH_C) st[sp++] = !free_mask || free_mask[k0 + arg];
+            else if (op == ROVMPC_OP_PUSH_F) st[sp++] = 0;
+            else if ((op >= ROVMPC_OP_ADD && op <= ROVMPC_OP_DIV) || op == ROVMPC_OP_POW) {
+                if (op == ROVMPC_OP_POW && st[sp - 1]) FAIL(h, ROVMPC_ERR_INVALID, "%s: row %d: free constant in a POW exponent", entry, r);
+                st[sp - 2] = st[sp - 2] | st[sp - 1];
+                --sp;
+            }
+            if (sp > depth) depth = sp;
+        }
+    }
+    pack_programs(code, code_off, consts, const_off, R, F, len, T, B, blob, plan.s);
+    const size_t o_group = (blob.size() + 7) & ~(size_t)7, o_fidx = o_group + ((size_t)G + 1) * sizeof(int64_t),
+                 o_nfree = o_fidx + fidx.size() * sizeof(int32_t);
+    blob.resize(o_nfree + nfree.size() * sizeof(int32_t), 0);
+    int64_t *go = (int64_t *)(blob.data() + o_group);
+    for (int g = 0; g <= G; ++g) go[g] = group_off ? (int64_t)group_off[g] : (g ? B : 0);
+    memcpy(blob.data() + o_fidx, fidx.data(), fidx.size() * sizeof(int32_t));
+    memcpy(blob.data() + o_nfree, nfree.data(), nfree.size() * sizeof(int32_t));
+    plan.o_group = o_group; plan.o_fidx = o_fidx; plan.o_nfree = o_nfree; plan.has_len = len != nullptr;
+    RefitArgs &a = plan.a;
+    memset(&a, 0, sizeof(a));
+    a.T = T; a.B = B; a.G = G; a.nk = const_off[R]; a.F = F; a.depth = depth; a.max_iter = p.max_iter; a.gtol = p.gtol; a.xtol = p.xtol;
+    return ROVMPC_OK;
+}
+
+static void refit_bind(RefitPlan &plan, const unsigned char *d_blob) {
+    score_bind(plan.s, d_blob, plan.has_len);
+    RefitArgs &a = plan.a;
+    a.code = plan.s.code; a.code_off = plan.s.code_off; a.consts = plan.s.consts; a.const_off = plan.s.const_off; a.len = plan.s.len;
+    a.group_off = (const long long *)(d_blob + plan.o_group);
+    a.free_idx = (const int32_t *)(d_blob + plan.o_fidx);
+    a.n_free = (const int32_t *)(d_blob + plan.o_nfree);
+}
+
+static void launch_refit(rovmpc_handle *h, int32_t R, const RefitArgs &a) {
+    hipLaunchKernelGGL(refit_rows_kernel, dim3((unsigned)((int64_t)R * a.G)), dim3(SCORE_NT), refit_lds_bytes(a.depth), h->stream, a);
+}
+
+extern "C" int rovmpc_refit_rows(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                 const int32_t *const_off, const uint8_t *free_mask, int32_t R, const double *X, int32_t F,
+                                 const int64_t *len, int64_t T, int64_t B, const double *target, const int32_t *group_off, int32_t G,
+                                 const rovmpc_refit_params *params, double *consts_out, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    RefitPlan plan;
+    if (int rc = refit_args(h, "rovmpc_refit_rows", code, code_off, consts, const_off, free_mask, R, X, F, len, T, B, target, group_off, G,
+                            params, consts_out, out, blob, plan))
+        return rc;
+    HelperCall c(h);
+    const size_t n = (size_t)B * T;
+    const auto dP = c.upload((const unsigned char *)blob.data(), blob.size());
+    const auto dX = c.upload(X, n * F);
+    const auto dG = c.upload(target, n);
+    const auto dK = c.buffer<double>((size_t)G * (size_t)plan.a.nk);
+    const auto dO = c.buffer<double>((size_t)R * G * ROVMPC_REFIT_OUT);
+    refit_bind(plan, dP.p);
+    plan.a.X = dX.p; plan.a.target = dG.p; plan.a.consts_out = dK.p; plan.a.out = dO.p;
+    if (c.ok()) launch_refit(h, R, plan.a);
+    if (plan.a.nk > 0) c.download(consts_out, dK);
+    c.download(out, dO);
+    return c.finish();
+}
+
+extern "C" int rovmpc_refit_rows_device(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                        const int32_t *const_off, const uint8_t *free_mask, int32_t R, const double *d_X, int32_t F,
+                                        const int64_t *len, int64_t T, int64_t B, const double *d_target, const int32_t *group_off,
+                                        int32_t G, const rovmpc_refit_params *params, double *d_consts_out, double *d_out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    RefitPlan plan;
+    if (int rc = refit_args(h, "rovmpc_refit_rows_device", code, code_off, consts, const_off, free_mask, R, d_X, F, len, T, B, d_target,
+                            group_off, G, params, d_consts_out, d_out, blob, plan))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = stage_programs(h, blob)) return rc;
+    refit_bind(plan, (const unsigned char *)h->d_score_prog);
+    plan.a.X = d_X; plan.a.target = d_target; plan.a.consts_out = d_consts_out; plan.a.out = d_out;
+    launch_refit(h, R, plan.a);
+    return launched(h, "row refit");
 }

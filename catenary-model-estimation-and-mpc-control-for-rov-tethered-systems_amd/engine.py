@@ -1004,6 +1004,42 @@ class Engine:
         back = lambda t: None if t is None else t.cpu().numpy()
         return back(dS), back(dE), back(dP)
 
+    def refit_rows(self, programs, X, target, lengths=None, group_off=None, free=None, params=None, device: bool = False):
+        """The constants of R compiled rows refitted on G groups of recordings (rovmpc_refit_rows; law in include/rovmpc.h).
+        ``programs`` as in ``score_rows`` (the constants are the starts); X (B, T, F), target (B, T), lengths (B,) or None,
+        group_off int32 (G + 1,) or None (all recordings pooled), free: per row a uint8 mask over its constants, or None (all
+        free); params a RefitParams or None, checked and laid out by ``scoring.refit_rows``.  Returns (consts_out (G, NK) with
+        NK the constants of all rows, out (R, G, 6)).  ``device=True`` goes through rovmpc_refit_rows_device: the same bits."""
+        code_off, const_off = [0], [0]
+        for code, consts in programs:
+            code_off.append(code_off[-1] + len(code)); const_off.append(const_off[-1] + len(consts))
+        code = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in programs]), np.int32)
+        consts = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float64).reshape(-1) for _, k in programs] + [np.zeros(1)]))
+        mask = None if free is None else np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8).reshape(-1) for m in free] + [np.zeros(1, np.uint8)]))
+        code_off, const_off = np.asarray(code_off, np.int32), np.asarray(const_off, np.int32)
+        R, (B, T, F), NK = len(programs), X.shape, int(const_off[-1])
+        G = 1 if group_off is None else len(group_off) - 1
+        goff = None if group_off is None else np.ascontiguousarray(group_off, np.int32)
+        lens = None if lengths is None else np.ascontiguousarray(lengths, np.int64)
+        pref = None if params is None else C.byref(params)
+        if not device:
+            consts_out = np.empty((G, max(NK, 1)))
+            out = np.empty((R, G, _lib.REFIT_OUT))
+            self._check(self.lib.rovmpc_refit_rows(self._h, _ptr(code), _ptr(code_off), _ptr(consts), _ptr(const_off), _ptr(mask), R, _ptr(X),
+                                                   F, _ptr(lens), T, B, _ptr(target), _ptr(goff), G, pref, _ptr(consts_out), _ptr(out)))
+            return consts_out.reshape(-1)[:G * NK].reshape(G, NK), out
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        dX, dG = torch.tensor(X, device=dev), torch.tensor(target, device=dev)
+        dK = torch.empty((G, max(NK, 1)), dtype=torch.float64, device=dev)
+        dO = torch.empty((R, G, _lib.REFIT_OUT), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_refit_rows_device(self._h, _ptr(code), _ptr(code_off), _ptr(consts), _ptr(const_off), _ptr(mask), R,
+                                                      dX.data_ptr(), F, _ptr(lens), T, B, dG.data_ptr(), _ptr(goff), G, pref, dK.data_ptr(),
+                                                      dO.data_ptr()))
+        torch.cuda.synchronize(dev)                     # (the device: the refit runs on the handle's own stream)
+        return dK.cpu().numpy().reshape(-1)[:G * NK].reshape(G, NK), dO.cpu().numpy()
+
 
 _default_engine: Optional[Engine] = None
 

@@ -166,6 +166,59 @@ def compile_expression(text: str, consts: List[float], n_features: int = 18,
     return Program(c.code, c.max_depth, sorted(c.used), text.strip())
 
 
+def _number_node(v: float):
+    """The AST of a literal that ``_as_number`` folds back to exactly ``v`` (a negative one as -(|v|): unparse then brackets
+    it where the grammar needs that, as under ``**``)."""
+    v = float(v)
+    if v != v:
+        raise ExpressionError("a constant that is not a number cannot be written into an expression")
+    if np.signbit(v):
+        return ast.UnaryOp(op=ast.USub(), operand=ast.Constant(value=-v))
+    return ast.Constant(value=v)
+
+
+def _walk_constants(node, pool: List[float], new: Optional[Sequence[float]]):
+    """The compiler's traversal (``_Compiler.visit``: same order, same folding, same pooling) over the literals that become
+    constants.  Fills ``pool``; with ``new`` returns the tree with constant k replaced by ``new[k]``."""
+    num = _Compiler._as_number(node)
+    if num is not None:
+        v = float(num)
+        try:
+            idx = next(i for i, c in enumerate(pool) if c == v and np.signbit(c) == np.signbit(v))
+        except StopIteration:
+            idx = len(pool)
+            pool.append(v)
+        return node if new is None else _number_node(new[idx])
+    if isinstance(node, ast.UnaryOp):
+        node.operand = _walk_constants(node.operand, pool, new)
+    elif isinstance(node, ast.BinOp):
+        node.left = _walk_constants(node.left, pool, new)
+        e = _Compiler._as_number(node.right) if isinstance(node.op, ast.Pow) else None
+        if not (e is not None and float(e).is_integer() and abs(e) < (1 << 22)):    # (an integer exponent is no constant)
+            node.right = _walk_constants(node.right, pool, new)
+    elif isinstance(node, ast.Call):
+        node.args = [_walk_constants(a, pool, new) for a in node.args]
+    return node
+
+
+def rewrite_constants(text: str, consts: Sequence[float], variable_names: Optional[Sequence[str]] = None) -> str:
+    """The row ``text`` with constant k of its own pool (what ``compile_expression`` collects from it into an empty pool)
+    replaced by ``consts[k]``, written so that it reads back exactly (``repr``).  Compiling the result evaluates exactly as the
+    original code does with the new pool.  ``variable_names`` is accepted for symmetry: names are kept as they are."""
+    src = text.strip().replace("^", "**")
+    try:
+        tree = ast.parse(src, mode="eval")
+    except SyntaxError as e:
+        raise ExpressionError(f"cannot parse expression {text!r}: {e}") from None
+    pool: List[float] = []
+    _walk_constants(tree.body, pool, None)
+    new = [float(c) for c in np.asarray(consts, dtype=np.float64).reshape(-1)]
+    if len(new) != len(pool):
+        raise ExpressionError(f"the expression has {len(pool)} constants (got {len(new)})")
+    tree.body = _walk_constants(tree.body, [], new)
+    return ast.unparse(ast.fix_missing_locations(tree))
+
+
 def disassemble(program: Program, consts: Sequence[float]) -> str:
     inv = {v: k for k, v in OP.items()}
     out = []

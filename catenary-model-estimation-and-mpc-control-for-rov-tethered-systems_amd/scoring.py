@@ -8,16 +8,23 @@ itself) -- as ONE launch for R rows on B recordings, the scores reduced on the d
     s = score_rows(rows, X, time, truth, integrator="rk4")     # s.r2, s.rmse, ... each (R, B)
     order = s.rank("r2")                                        # row indices, best first
     model, s_theta, s_gamma = select_model(theta_rows, gamma_rows, X_raw, time, theta, gamma, mean, scale)
+
+The rows carry the constants PySR found on the reference's cable.  ``refit_rows`` tunes them to the caller's recordings
+(rovmpc_refit_rows: what the reference's trainers do for every candidate row, simply.py:65-98, for R given structures in one
+launch), and ``select_model(..., refit=True)`` scores and loads the refitted rows.
+
+    fit = refit_rows(rows, X, target)                           # fit.expressions[r][0], fit.loss, fit.status, ... (R, G)
 """
 from __future__ import annotations
 
+import enum
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from .expr import compile_expression
+from .expr import OP, compile_expression, rewrite_constants
 from .model import DynamicsModel
 
 INTEGRATORS = {"rk4": _lib.RK4, "euler": _lib.EULER, "double_euler": _lib.DOUBLE_EULER, "trapezoid": _lib.TRAPEZOID}
@@ -83,8 +90,9 @@ def row_text(row) -> str:
     raise ValueError(f"a row must be an expression string or a dict with 'sympy_format' / 'equation' (got {row!r})")
 
 
-def _recordings(X, time, truth, target, lengths, y0):
-    """Shapes checked, everything (B, ...) float64 C-contiguous; ``single``: X came as (T, F)."""
+def _recordings(X, time, truth, target, lengths, y0, names=("time", "truth")):
+    """Shapes checked, everything (B, ...) float64 C-contiguous; ``single``: X came as (T, F).  ``names``: what the two
+    required series are called in the messages."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     single = X.ndim == 2
     if single:
@@ -104,7 +112,7 @@ def _recordings(X, time, truth, target, lengths, y0):
         if a.shape != (B, T):
             raise ValueError(f"{name} must be {'(T,) or ' if single else ''}(B, T) = {(B, T)} (got {np.shape(v)})")
         return a
-    time, truth = series("time", time), series("truth", truth)
+    time, truth = series(names[0], time), series(names[1], truth)
     target = None if target is None else series("target", target)
     if lengths is not None:
         lengths = np.asarray(lengths)
@@ -149,19 +157,155 @@ def score_rows(rows, X, time, truth, integrator="rk4", target=None, lengths=None
     return RowScores.from_table(table, texts, est, pred)
 
 
+class RefitStatus(enum.IntEnum):
+    """``rovmpc_refit_status``: how a fit of ``refit_rows`` ended."""
+    CONVERGED = _lib.REFIT_CONVERGED
+    MAX_ITER = _lib.REFIT_MAX_ITER
+    STALLED = _lib.REFIT_STALLED
+    NONFINITE = _lib.REFIT_NONFINITE
+    NO_PARAMS = _lib.REFIT_NO_PARAMS
+
+
+@dataclass
+class RowRefit:
+    """What rovmpc_refit_rows returns for R rows on G groups.  ``consts[r]``: (G, P_r), all constants of row r (fitted and
+    frozen) per group; ``expressions[r][g]``: the row's text with them written in; the six columns each (R, G)."""
+    consts: list
+    expressions: list
+    loss0: np.ndarray
+    loss: np.ndarray
+    orth: np.ndarray
+    iters: np.ndarray
+    status: np.ndarray
+    n_params: np.ndarray
+
+
+def exponent_roles(code, n_consts: int):
+    """Per constant of a compiled row: (occurrences that reach the exponent operand of a POW, all occurrences).  The stack
+    simulation of the library's validation, with the set of PUSH_C occurrences behind every slot."""
+    stack, in_exp, seen = [], set(), {}
+    for pc, ins in enumerate(code):
+        op, arg = ins & 0xFF, ins >> 8
+        if op == OP["PUSH_C"]:
+            stack.append({pc}); seen.setdefault(arg, set()).add(pc)
+        elif op == OP["PUSH_F"]:
+            stack.append(set())
+        elif op in (OP["ADD"], OP["SUB"], OP["MUL"], OP["DIV"], OP["POW"]):
+            b = stack.pop()
+            if op == OP["POW"]:
+                in_exp |= b
+            stack[-1] = stack[-1] | b
+    return [(len(seen.get(k, set()) & in_exp), len(seen.get(k, ()))) for k in range(n_consts)]
+
+
+def default_free(code, n_consts: int, text: str = "") -> np.ndarray:
+    """The free mask ``refit_rows`` uses when none is given: every constant but those that occur only as POW exponents."""
+    free = np.ones(n_consts, dtype=np.uint8)
+    for k, (n_exp, n_all) in enumerate(exponent_roles(code, n_consts)):
+        if n_exp and n_exp < n_all:
+            raise ValueError(f"constant {k} of {text!r} is shared between a POW exponent and another place: give `free`")
+        if n_exp:
+            free[k] = 0
+    return free
+
+
+def refit_rows(rows, X, target, lengths=None, groups="pooled", free=None, max_iter: int = 50, gtol: float = 1e-10,
+               xtol: float = 1e-12, variable_names=None, engine=None, device: bool = False) -> RowRefit:
+    """Refit the constants of every row of ``rows`` to the derivative series ``target`` on the recordings X (T, F) or
+    (B, T, F) of already-scaled feature rows (rovmpc_refit_rows; law in include/rovmpc.h): Levenberg-Marquardt on the `loss`
+    column of ``score_rows``, all (row, group) problems in one launch.  ``groups``: "pooled" (one fit on all recordings),
+    "each" (one per recording) or an offsets array 0 .. B; ``free``: per row a boolean sequence over the row's constants
+    (default: all but those that occur only as POW exponents); ``lengths``: the rows of each recording that count.
+    ``expressions`` are the rows with the returned constants written in (``rewrite_constants``).  The library never moves a
+    constant that reaches a POW exponent (it refuses a free one), so an exponent keeps its value and ``x**2.5`` stays a POW;
+    were a pool edited by hand so that such an exponent became a whole number, the text would compile to POWI, another
+    operation sequence.  A start that is not a number is refused here, before the launch: it could not be written back."""
+    if isinstance(rows, (str, dict)):
+        raise ValueError("rows must be a sequence of rows, not a single row")
+    texts = [row_text(r) for r in rows]
+    if not texts:
+        raise ValueError("rows is empty")
+    if target is None:
+        raise ValueError("target is required: the derivative series the constants are fitted to")
+    X, _, target, _, lengths, _, _ = _recordings(X, target, target, None, lengths, None, names=("target", "target"))
+    B = X.shape[0]
+    if isinstance(groups, str):
+        if groups not in ("pooled", "each"):
+            raise ValueError(f"groups must be 'pooled', 'each' or an offsets array (got {groups!r})")
+        group_off = None if groups == "pooled" else np.arange(B + 1, dtype=np.int32)
+    else:
+        group_off = np.asarray(groups)
+        if group_off.ndim != 1 or len(group_off) < 2 or not np.issubdtype(group_off.dtype, np.integer) or group_off[0] != 0 or \
+                group_off[-1] != B or (np.diff(group_off) <= 0).any():
+            raise ValueError(f"groups must be offsets that run from 0 to B = {B} increasing (got {groups!r})")
+        group_off = np.ascontiguousarray(group_off, dtype=np.int32)
+    params = _lib.RefitParams.make(max_iter, gtol, xtol)
+    if free is not None and len(free) != len(texts):
+        raise ValueError(f"free must hold one mask per row ({len(texts)}; got {len(free)})")
+    programs, masks = [], []
+    for r, text in enumerate(texts):
+        consts: list = []
+        prog = compile_expression(text, consts, X.shape[2], variable_names)
+        if any(c != c for c in consts):
+            raise ValueError(f"row {r} starts from a constant that is not a number: {text!r}")      # (it could not be written back)
+        if free is None:
+            mask = default_free(prog.code, len(consts), text)
+        else:
+            mask = np.asarray(free[r]).astype(bool).astype(np.uint8).reshape(-1)
+            if mask.shape != (len(consts),):
+                raise ValueError(f"free[{r}] must hold one flag per constant of the row ({len(consts)}; got {mask.shape[0]})")
+        if int(mask.sum()) > _lib.REFIT_MAX_PARAMS:
+            raise ValueError(f"row {r} has {int(mask.sum())} free constants (at most {_lib.REFIT_MAX_PARAMS}): freeze some with `free`")
+        programs.append((prog.code, consts)); masks.append(mask)
+    if engine is None:
+        from .engine import default_engine
+        engine = default_engine()
+    consts_out, out = engine.refit_rows(programs, X, target, lengths, group_off, masks, params, device)
+    off = np.concatenate([[0], np.cumsum([len(k) for _, k in programs])]).astype(int)
+    per_row = [np.ascontiguousarray(consts_out[:, off[r]:off[r + 1]]) for r in range(len(texts))]
+    expressions = [[rewrite_constants(text, c, variable_names) for c in per_row[r]] for r, text in enumerate(texts)]
+    col = lambda k, t=np.float64: np.ascontiguousarray(out[..., k]).astype(t)
+    return RowRefit(per_row, expressions, col(0), col(1), col(2), col(3, np.int64), col(4, np.int64), col(5, np.int64))
+
+
+def _derivative_target(series, time, lengths):
+    """np.gradient(series, time) per recording over its counted rows (simply.py's target); 0 beyond them."""
+    series, time = np.asarray(series, dtype=np.float64), np.asarray(time, dtype=np.float64)
+    if series.shape != time.shape or series.ndim not in (1, 2):
+        raise ValueError(f"series and time must both be (T,) or (B, T) (got {series.shape}, {time.shape})")
+    s2, t2 = np.atleast_2d(series), np.atleast_2d(time)
+    out = np.zeros_like(s2)
+    for b in range(len(s2)):
+        n = s2.shape[1] if lengths is None else int(np.asarray(lengths)[b])
+        if n < 2:
+            raise ValueError(f"recording {b} has {n} counted rows: a derivative needs at least 2")
+        out[b, :n] = np.gradient(s2[b, :n], t2[b, :n])
+    return out.reshape(series.shape)
+
+
 def select_model(theta_rows, gamma_rows, X_raw, time, theta, gamma, mean, scale, integrator="rk4", metric: str = "r2",
-                 reduce: str = "mean", lengths=None, variable_names=None, engine=None):
+                 reduce: str = "mean", lengths=None, variable_names=None, engine=None, refit: bool = False):
     """Score both Pareto fronts on the recordings and return (the DynamicsModel of the two best rows, theta scores, gamma
     scores).  ``X_raw`` (T, F) or (B, T, F) are unscaled feature rows; they are scaled as the scaler does, (X - mean) / scale,
-    before the rows read them.  ``theta`` / ``gamma``: the measured series the replays are held against."""
+    before the rows read them.  ``theta`` / ``gamma``: the measured series the replays are held against.  ``refit=True``:
+    the constants of both fronts are first refitted (``refit_rows``, all recordings pooled) to np.gradient(series, time), the
+    reference's target (simply.py); the rewritten rows are scored -- with that target, so ``loss`` is theirs -- and loaded."""
     mean = np.asarray(mean, dtype=np.float64); scale = np.asarray(scale, dtype=np.float64)
     X_raw = np.asarray(X_raw, dtype=np.float64)
     if mean.ndim != 1 or mean.shape != scale.shape or X_raw.ndim not in (2, 3) or X_raw.shape[-1] != mean.shape[0]:
         raise ValueError(f"mean and scale must be (F,) with F = X_raw.shape[-1] (got {mean.shape}, {scale.shape}, {X_raw.shape})")
     Xs = (X_raw - mean) / scale
     kw = dict(integrator=integrator, lengths=lengths, variable_names=variable_names, engine=engine)
-    s_theta = score_rows(theta_rows, Xs, time, theta, **kw)
-    s_gamma = score_rows(gamma_rows, Xs, time, gamma, **kw)
+    if refit:
+        fronts = []
+        for rows, series in ((theta_rows, theta), (gamma_rows, gamma)):
+            target = _derivative_target(series, time, lengths)
+            fit = refit_rows(rows, Xs, target, lengths=lengths, variable_names=variable_names, engine=engine)
+            fronts.append(score_rows([e[0] for e in fit.expressions], Xs, time, series, target=target, **kw))
+        s_theta, s_gamma = fronts
+    else:
+        s_theta = score_rows(theta_rows, Xs, time, theta, **kw)
+        s_gamma = score_rows(gamma_rows, Xs, time, gamma, **kw)
     model = DynamicsModel(mean, scale, s_theta.expressions[s_theta.best(metric, reduce)],
                           s_gamma.expressions[s_gamma.best(metric, reduce)], variable_names=variable_names)
     return model, s_theta, s_gamma

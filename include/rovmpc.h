@@ -29,6 +29,7 @@
 #if !defined(__HIPCC_RTC__)
 #include <stdint.h>
 #else   /* hiprtc has no <stdint.h>: the compiler's own type macros give the same typedefs */
+typedef __UINT8_TYPE__ uint8_t;
 typedef __INT32_TYPE__ int32_t;
 typedef __UINT32_TYPE__ uint32_t;
 typedef __INT64_TYPE__ int64_t;
@@ -917,7 +918,8 @@ int rovmpc_replay(rovmpc_handle *h, const double *Xs, const double *time, int64_
  * F outside 1 .. ROVMPC_MAX_FEATURES, an integrator that is none of the four, offsets that do not start at 0 or decrease,
  * len[b] outside 1 .. T, a row that fails validation (its index is in the message).
  * Not provided: the N-step-ahead skill of a row pair fed its own predictions (the rollout's law), the double cumulative_trapezoid
- * without offset of dd_test_cluster.py:217-219 (no counterpart in rovmpc_replay), refitting constants, fp32. */
+ * without offset of dd_test_cluster.py:217-219 (no counterpart in rovmpc_replay), fp32.  Refitting the constants of the rows
+ * is rovmpc_refit_rows, below. */
 #define ROVMPC_SCORE_COLS 8
 #define ROVMPC_SCORE_TILE 128
 /* Host pointers.  Uploads, one launch, one synchronise. */
@@ -933,6 +935,81 @@ int rovmpc_score_rows_device(rovmpc_handle *h, const int32_t *code, const int32_
                              const int32_t *const_off, int32_t R, const double *d_X, int32_t F, const double *d_time,
                              const int64_t *len, int64_t T, int64_t B, const double *d_truth, const double *d_target,
                              const double *d_y0, int32_t integrator, double *d_scores, double *d_est, double *d_pred);
+
+/* ---- refit the constants of equation rows on recordings: what PySR does for every candidate row, as one launch ----------
+ * The reference's trainers tune the constants of an expression against the derivative target (simply.py:65-98 minimises the
+ * `loss` column, the mean of (g - f(x))^2).  This entry does that for R given structures on the caller's own recordings, by
+ * Levenberg-Marquardt, so that the rows rovmpc_score_rows ranks are fits to the caller's cable and not to the reference's.
+ * Programs, offsets, X[B][T][F], len and target[B][T] mean what they mean in rovmpc_score_rows; target is required; there is
+ * no time and no integrator: the objective is the derivative loss (column 4 there).  free[const_off[R]]: one byte per
+ * constant, non-zero = fitted (NULL: all).  A GROUP g is the set of recordings group_off[g] .. group_off[g + 1] pooled into one
+ * fit; group_off NULL with G = 1 pools all B recordings, G = B with unit steps fits every recording on its own.  A PROBLEM is
+ * one pair (row r, group g); problems are independent.
+ * Law (fp64 only).
+ *   parameters  the free constants of row r in pool order, P <= ROVMPC_REFIT_MAX_PARAMS.  consts is the start; frozen
+ *          constants are copied to consts_out bit for bit.
+ *   value  p_i = f_r(x_i; c) is the arithmetic of rovmpc_score_rows' pred bit for bit: what this entry calls loss is what
+ *          that entry calls loss.
+ *   tangents  forward mode through the same program in double, one rule per opcode (a, b the operands, da, db their
+ *          tangents): PUSH_C k: e_k if k is free, else 0; PUSH_F: 0; ADD SUB NEG: linear; MUL: da b + a db; DIV: (da - q db) / b
+ *          with q the quotient; SIN: da cos a; COS: -(da sin a); TANH: da (1 - t^2); ABS: da sign a (0 at 0); SQUARE: 2 a da;
+ *          EXP: da e; LOG: da / a; SQRT: da / (2 s); POWI e: e a^(e-1) da (0 for e = 0); SAFE_LOG: da sign a / (|a| + 1e-5);
+ *          SAFE_SQRT: da sign a / (2 sqrt|a|); POW: da b pow(a, b - 1) -- the exponent's tangent is not propagated, and a row
+ *          in which a free constant reaches the exponent operand of a POW is refused.  The rounding of the tangents is not
+ *          part of the law; their determinism is (below).
+ *   sums   with r_i = p_i - g_i and J_ij = dp_i / dc_j over every counted row of the group: F = sum r_i^2, A_jk = sum J_ij
+ *          J_ik, g_j = sum J_ij r_i, n = sum len.  Each as ROVMPC_SCORE_TILE partial sums -- lane j adds its terms i = j,
+ *          j + TILE, ... of recording after recording, in the group's order, from +0, products rounded before the addition --
+ *          then the tree of rovmpc_score_rows.  For a one-recording group F is that entry's sum of (g - p)^2 bit for bit.
+ *   step   mu starts at ROVMPC_REFIT_MU0.  (A + mu diag A) delta = -g by Cholesky; a pivot <= 0 or not a number is a rejected
+ *          trial.  The trial c + delta is ACCEPTED when its F and every entry of its J are finite and F_trial <= F: then
+ *          mu = max(mu / 10, ROVMPC_REFIT_MU_MIN).  Otherwise the iterate stays and mu = 10 mu.
+ *   stop   before a trial, in this order: F = 0, or orth = max_j |g_j| / sqrt(A_jj F) <= gtol over the j with A_jj > 0
+ *          (MINPACK's orthogonality test; 0 when there is no such j): CONVERGED; mu > ROVMPC_REFIT_MU_MAX: STALLED; max_iter
+ *          trial steps used: MAX_ITER.  After a trial with |delta_j| <= xtol (|c_j| + xtol) for all j, accepted or not:
+ *          CONVERGED (the rule of rovmpc_fit_theta_gamma; an accepted step is taken).
+ *   start  P = 0: NO_PARAMS, loss = loss0, orth = 0.  F or J not finite at the start: NONFINITE, consts_out holds the start,
+ *          loss and orth are NaN, loss0 is F / n as computed.
+ *   out[r][g][ROVMPC_REFIT_OUT] = loss0 = F_start / n, loss = F / n, orth at the returned constants, trial steps used,
+ *          status (a rovmpc_refit_status), P.  consts_out[g][const_off[r] ..] = the constants of row r fitted on group g.
+ *   determinism  the bits of out[r][g] and of the row's slice of consts_out[g] are a function of the row, the free mask, the
+ *          group's recordings in order and the params alone: not of R, G, B, T, the place in the call, or the entry.
+ *   One workgroup of ROVMPC_SCORE_TILE lanes per problem; a trial costs one pass for F and, where F lets it be accepted, P
+ *   passes of a dual-number interpreter for J (one tangent direction per pass).
+ * ROVMPC_ERR_INVALID with a message, before anything is launched and with nothing written: everything rovmpc_score_rows
+ * refuses; a null target, consts_out or out; G < 1 or R G > 2^24; group_off NULL with G != 1, or a group_off that does not run
+ * from 0 to B strictly increasing; more than ROVMPC_REFIT_MAX_PARAMS free constants in a row, or a free constant in a POW
+ * exponent (the row is named); a struct_size mismatch; max_iter outside 1 .. 1000; gtol or xtol negative or NaN.
+ * Not provided: an integrated-trajectory objective, robust losses, bounds on the constants, structure search, fp32. */
+#define ROVMPC_REFIT_MAX_PARAMS 8
+#define ROVMPC_REFIT_OUT 6
+#define ROVMPC_REFIT_MU0 1e-3
+#define ROVMPC_REFIT_MU_MIN 1e-12
+#define ROVMPC_REFIT_MU_MAX 1e12
+typedef enum rovmpc_refit_status {
+    ROVMPC_REFIT_CONVERGED = 0, ROVMPC_REFIT_MAX_ITER = 1, ROVMPC_REFIT_STALLED = 2, ROVMPC_REFIT_NONFINITE = 3,
+    ROVMPC_REFIT_NO_PARAMS = 4
+} rovmpc_refit_status;
+typedef struct rovmpc_refit_params {
+    int32_t struct_size;             /* = sizeof(rovmpc_refit_params), ABI check                         */
+    int32_t max_iter;                /* trial steps, 1 .. 1000; default 50                               */
+    double gtol;                     /* orthogonality test; default 1e-10                                */
+    double xtol;                     /* step test; default 1e-12                                         */
+} rovmpc_refit_params;
+void rovmpc_default_refit_params(rovmpc_refit_params *p);
+/* Host pointers; params NULL: the defaults.  Uploads, one launch, one synchronise. */
+int rovmpc_refit_rows(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                      const int32_t *const_off, const uint8_t *free, int32_t R, const double *X, int32_t F, const int64_t *len,
+                      int64_t T, int64_t B, const double *target, const int32_t *group_off, int32_t G,
+                      const rovmpc_refit_params *params, double *consts_out, double *out);
+/* X, target, consts_out and out in device memory (all double), enqueued on the handle's stream without a synchronise.  The
+ * programs (code, code_off, consts, const_off), free, len and group_off stay HOST arrays: they are checked here, before
+ * anything is launched, and copied into a buffer of the handle on the same stream; they may be freed when the call returns.
+ * (A second call on the handle waits on the host until the first call's copy of the programs has run, not for its kernel.) */
+int rovmpc_refit_rows_device(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                             const int32_t *const_off, const uint8_t *free, int32_t R, const double *d_X, int32_t F,
+                             const int64_t *len, int64_t T, int64_t B, const double *d_target, const int32_t *group_off,
+                             int32_t G, const rovmpc_refit_params *params, double *d_consts_out, double *d_out);
 
 /* solve_catenary(l, delta_H, L) (main_fun.py:418-431) and, if T_out != NULL, the tension
  * rule of main_fun.py:302-305 with cfg.cable_wet_weight. */
