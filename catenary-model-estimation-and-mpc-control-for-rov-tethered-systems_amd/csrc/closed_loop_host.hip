@@ -24,27 +24,18 @@ static int closed_loop_workspace(rovmpc_handle *h, HandoffArgs &p, hipStream_t s
     return ROVMPC_OK;
 }
 
-// ---- pipelined closed loop: one step per launch, launches alternating between two streams -----------------------
-template <typename T, int VT>
-static hipError_t launch_step(const rovmpc_handle *h, const RolloutArgs<T> &a, const HandoffArgs &p, hipStream_t s, bool probe, int *capacity) {
-    const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_BUILTIN, VT) * sizeof(T);
-    auto kern = (a.CK == 16 && a.ck_shift == 4) ? closed_loop_step_kernel16<T, MODEL_BUILTIN, VT> : closed_loop_step_kernel<T, MODEL_BUILTIN, VT>;   // (literal-CK instance: rollout_body, CKC)
-    if constexpr (sizeof(T) == 8) { if (a.CK == 16 && a.ck_shift == 4 && a.N == 20 && !getenv("ROVMPC_NO_LITERAL_N")) kern = closed_loop_step_kernel16_n20<T, MODEL_BUILTIN, VT>; }
-    if (probe) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        int per_cu = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, a.NT, lds);
-        if (e != hipSuccess) return e;
-        *capacity = per_cu * h->n_cu;
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(a.NT), lds, s, a, p);
-    return hipGetLastError();
+// Resolves the closed-loop step kernel for geometry g into k (setting its dynamic-LDS attribute, as the launches need) and
+// returns the workgroups of it the device holds at once: resident workgroups per CU x CUs; 0 if the model has no step kernel or
+// a query fails (*why: that query's error).
+static int step_kernel_capacity(rovmpc_handle *h, const Geo &g, Launchable &k, hipError_t *why = nullptr) {
+    int capacity = 0;
+    hipError_t e = rollout_launchable(h, LAUNCH_STEP, g, StepOpts(), k);
+    if (e == hipSuccess) e = launchable_capacity(h, k, g.NT, &capacity);
+    if (why) *why = e;
+    return capacity;
 }
 
+// ---- pipelined closed loop: one step per launch, launches alternating between two streams -----------------------
 template <typename T>
 static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_t T_steps, double *d_state, const void *d_pools,
                                    int32_t n_pools, int32_t feedback, double *d_results, hipStream_t s) {
@@ -72,7 +63,6 @@ static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_
     }
     if (!h->pipe_ev[0])
         for (auto &ev : h->pipe_ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const int vt = h->cfg.vt_mode;
     const size_t R = rovmpc_result_len(h);
     RolloutArgs<T> a;
     HandoffArgs p;
@@ -80,24 +70,13 @@ static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_
     if (rcw) return rcw;
     p.T = T_steps; p.exo = d_exo;
     const size_t pool_bytes = (size_t)h->cfg.K * h->cfg.N * 3 * sizeof(T);
-    int capacity = 0;
-    if (h->model_kind == MODEL_BUILTIN) {
-        h->plant_feedback = 0;
-        fill_args<T>(h, a, d_state, d_pools, nullptr, g, 1);
-        --*h->epoch_ctr;                                         // (the probe takes no epoch)
-        hipError_t e = vt == 0 ? launch_step<T, 0>(h, a, p, s, true, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, s, true, &capacity)
-                                                                                      : launch_step<T, 2>(h, a, p, s, true, &capacity);
-        if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
-    } else if (h->model_kind == MODEL_JIT) {
-        if (!h->jit_fn_step) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "the run-time specialised module has no pipelined entry");
-        const size_t lds = rollout_lds_elems<T>(h->cfg.N, g.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int per_cu = 0;
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_step, g.NT, lds) != hipSuccess) per_cu = 0;
-        capacity = per_cu * h->n_cu;
-    } else {
+    if (h->model_kind == MODEL_JIT && !h->jit_fn_step) FAIL(h, ROVMPC_ERR_UNSUPPORTED, "the run-time specialised module has no pipelined entry");
+    if (h->model_kind == MODEL_INTERP)
         FAIL(h, ROVMPC_ERR_UNSUPPORTED, "pipelined closed loop: compiled-in and hiprtc-specialised models only (the interpreter runs launch per step)");
-    }
+    Launchable k;
+    hipError_t e;
+    const int capacity = step_kernel_capacity(h, g, k, &e);
+    if (e != hipSuccess && !k.mod) FAIL(h, ROVMPC_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));      // (a module's failed query: capacity 0)
     if (2 * g.nblocks > capacity)
         FAIL(h, ROVMPC_ERR_UNSUPPORTED, "pipelined closed loop needs two grids resident at once: 2 x %d workgroups exceed the device's capacity %d "
                                         "(use rovmpc_closed_loop_device)", g.nblocks, capacity);
@@ -106,57 +85,19 @@ static int closed_loop_pipelined_t(rovmpc_handle *h, const double *d_exo, int64_
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->pipe_ev[2], s));
     HIPCHK(h, hipStreamWaitEvent(h->pipe_streams[1], h->pipe_ev[2], 0));
+    StepOpts o;
+    o.plant_feedback = feedback ? 1 : 0;
     for (int64_t i = 0; i < T_steps; ++i) {
         hipStream_t st = (i & 1) ? h->pipe_streams[1] : s;
-        h->plant_feedback = feedback ? 1 : 0;
-        fill_args<T>(h, a, d_state, (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes, nullptr, g, 1);   // one epoch per step
-        h->plant_feedback = 0;
-        a.result = d_results + (size_t)i * R; a.k_offset = 0; a.slots = nullptr; a.rank = 0; a.world = 1;
+        fill_args<T>(h, a, d_state, (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes, d_results + (size_t)i * R, g, o);
         a.sweeper = 0;
         p.step = i;
-        const HandoffArgs &pi = p;
-        hipError_t e;
-        if (h->model_kind == MODEL_JIT) {
-            const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            struct { RolloutArgs<T> a; HandoffArgs p; } both{a, pi};
-            size_t asz = sizeof(both);
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &both, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-            e = hipModuleLaunchKernel(h->jit_fn_step, a.nblocks, 1, 1, a.NT, 1, 1, (unsigned)lds, st, nullptr, extra);
-        } else {
-            e = vt == 0 ? launch_step<T, 0>(h, a, pi, st, false, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, pi, st, false, &capacity)
-                                                                                      : launch_step<T, 2>(h, a, pi, st, false, &capacity);
-        }
+        e = launch_rollout<T>(h, k, a, 1, st, &p);                                                           // one epoch per step
         if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "pipelined closed-loop launch failed: %s", hipGetErrorString(e));
     }
     HIPCHK(h, hipEventRecord(h->pipe_ev[1], h->pipe_streams[1]));
     HIPCHK(h, hipStreamWaitEvent(s, h->pipe_ev[1], 0));
     return ROVMPC_OK;
-}
-
-// Workgroups of the closed-loop step kernel (the instance launch_step / jit_fn_step would run, with its dynamic LDS) the
-// device holds at once: resident workgroups per CU x CUs; 0 if the model has no step kernel or the query fails.  Sets the
-// kernel's dynamic-LDS attribute on the way, as the launches need.
-template <typename T>
-static int step_kernel_capacity(rovmpc_handle *h, const Geo &g) {
-    const int vt = h->cfg.vt_mode;
-    int capacity = 0;
-    if (h->model_kind == MODEL_BUILTIN) {
-        RolloutArgs<T> a;
-        const HandoffArgs p{};
-        fill_args<T>(h, a, nullptr, nullptr, nullptr, g, 1);
-        --*h->epoch_ctr;                                         // (the probe takes no epoch)
-        hipError_t e = vt == 0 ? launch_step<T, 0>(h, a, p, nullptr, true, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, nullptr, true, &capacity)
-                                                                                              : launch_step<T, 2>(h, a, p, nullptr, true, &capacity);
-        if (e != hipSuccess) capacity = 0;
-    } else if (h->model_kind == MODEL_JIT && h->jit_fn_step) {
-        const size_t lds = rollout_lds_elems<T>(h->cfg.N, g.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int per_cu = 0;
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn_step, g.NT, lds) != hipSuccess) per_cu = 0;
-        capacity = per_cu * h->n_cu;
-    }
-    return capacity;
 }
 
 // ---- sharded closed loop with the state handed over on the GPU ----------------------------------------------------------
@@ -169,10 +110,9 @@ static int step_kernel_capacity(rovmpc_handle *h, const Geo &g) {
 // (world 1: 47.5 -> ~20 us).  Compiled-in and hiprtc models whose step-kernel grid is resident in one round (the caller,
 // rovmpc_closed_loop_device, checks that); records are the join-based loop's bit for bit.
 template <typename T>
-static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const double *d_exo, int64_t T_steps, double *d_state, const void *d_pools,
-                                         int32_t n_pools, int64_t k_offset, double *d_results, hipStream_t s) {
+static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const Launchable &k, const double *d_exo, int64_t T_steps, double *d_state,
+                                         const void *d_pools, int32_t n_pools, int64_t k_offset, double *d_results, hipStream_t s) {
     const Geo g = launch_geometry(h, 1);
-    const int vt = h->cfg.vt_mode;
     const size_t R = rovmpc_result_len(h);
     if (!h->comm_placed) {
         int rc = place_comm_streams(h, s);
@@ -185,48 +125,15 @@ static int closed_loop_sharded_handoff_t(rovmpc_handle *h, const double *d_exo, 
     const size_t pool_bytes = (size_t)h->cfg.K * h->cfg.N * 3 * sizeof(T);
     RolloutArgs<T> a;
     for (int64_t i = 0; i < T_steps; ++i) {
-        const int sp = h->comm_flip;
-        h->comm_flip = (h->comm_flip + 1) % rovmpc_handle::NSLOT;
-        if (h->slot_used[sp]) {
-            int rc = comm_wait_enqueued(h, sp);
-            if (rc) return rc;
-        }
-        h->slot_used[sp] = true;
-        const unsigned long long use = ++h->slot_uses[sp];
-        h->arg_flag_consumed = h->d_flags + rovmpc_handle::NSLOT + sp; h->arg_consumed_need = use - 1;
-        h->arg_flag_rolled = h->d_flags + sp; h->arg_rolled_seq = use;
-        h->arg_slot_bad = h->d_flags + 2 * rovmpc_handle::NSLOT + sp;
-        int inject = 0;
-        if (h->inject_skip_rolled > 0) { --h->inject_skip_rolled; inject |= 1; }
-        if (h->inject_skip_consumed > 0) { --h->inject_skip_consumed; inject |= 2; }
-        h->arg_inject = inject;
-        h->plant_feedback = 1;
-        fill_args<T>(h, a, d_state, (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes, nullptr, g, 1);   // one epoch per step
-        h->plant_feedback = 0;
-        h->arg_flag_consumed = nullptr; h->arg_flag_rolled = nullptr; h->arg_slot_bad = nullptr; h->arg_inject = 0;
-        a.result = h->d_result; a.k_offset = k_offset; a.slots = h->d_slots[sp]; a.rank = h->comm_rank; a.world = h->comm_world;
+        StepOpts o;
+        o.k_offset = k_offset; o.plant_feedback = 1;
+        int sp, rc = comm_take_slot(h, o, sp);
+        if (rc) return rc;
+        fill_args<T>(h, a, d_state, (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes, h->d_result, g, o);
         p.step = i;
-        hipError_t e;
-        int capacity = 0;     // (not probed here: the caller's step_kernel_capacity has set the LDS attribute)
-        if (h->model_kind == MODEL_JIT) {
-            const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            struct { RolloutArgs<T> a; HandoffArgs p; } both{a, p};
-            size_t asz = sizeof(both);
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &both, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-            e = hipModuleLaunchKernel(h->jit_fn_step, a.nblocks, 1, 1, a.NT, 1, 1, (unsigned)lds, s, nullptr, extra);
-        } else {
-            e = vt == 0 ? launch_step<T, 0>(h, a, p, s, false, &capacity) : vt == 1 ? launch_step<T, 1>(h, a, p, s, false, &capacity)
-                                                                          : launch_step<T, 2>(h, a, p, s, false, &capacity);
-        }
+        const hipError_t e = launch_rollout<T>(h, k, a, 1, s, &p);                                           // one epoch per step
         if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "sharded closed-loop launch failed: %s", hipGetErrorString(e));
-        {
-            std::lock_guard<std::mutex> lk(h->comm_mu);
-            h->comm_q.push_back({sp, d_results + (size_t)i * R, use, (int)(h->comm_rr++ % (unsigned long long)h->ncomm), inject,
-                                 i + 1 < T_steps ? p.ring : nullptr, p.seq_theta, (long long)(i + 1)});
-            ++h->comm_submitted[sp];
-        }
-        h->comm_cv.notify_all();
+        comm_submit(h, sp, o, d_results + (size_t)i * R, i + 1 < T_steps ? p.ring : nullptr, p.seq_theta, (long long)(i + 1));
     }
     int rc = rovmpc_comm_join(h, s);
     if (rc) return rc;
@@ -275,11 +182,10 @@ extern "C" int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, 
         HIPCHK(h, hipGetLastError());
         for (int64_t i = 0; i < T; ++i) {
             const void *U = (const char *)d_pools + (size_t)(i % n_pools) * pool_bytes;
-            h->plant_next = i + 1 < T ? d_exo + (size_t)(i + 1) * 16 : nullptr;
-            h->plant_state = d_state; h->plant_feedback = feedback ? 1 : 0;
-            rc = enqueue_step(h, d_state, U, nullptr, d_results + (size_t)i * R, 0, nullptr, 0, 1, s);
-            h->plant_next = nullptr; h->plant_state = nullptr; h->plant_feedback = 0;
-            if (rc) return rc;
+            StepOpts o;
+            o.plant_next = i + 1 < T ? d_exo + (size_t)(i + 1) * 16 : nullptr;
+            o.plant_state = d_state; o.plant_feedback = feedback ? 1 : 0;
+            if ((rc = enqueue_step(h, d_state, U, d_results + (size_t)i * R, s, o))) return rc;
         }
         return ROVMPC_OK;
     }
@@ -291,15 +197,16 @@ extern "C" int rovmpc_closed_loop_device(rovmpc_handle *h, const double *d_exo, 
         (h->model_kind == MODEL_BUILTIN || (h->model_kind == MODEL_JIT && h->jit_fn_step))) {
         HIPCHK(h, hipSetDevice(h->cfg.device));
         const Geo g = launch_geometry(h, 1);
-        const int capacity = h->cfg.dtype == ROVMPC_F64 ? step_kernel_capacity<double>(h, g) : step_kernel_capacity<float>(h, g);
+        Launchable k;
+        const int capacity = step_kernel_capacity(h, g, k);
         const bool one_round = capacity > 0 && g.nblocks <= capacity;
         if (getenv("ROVMPC_CL_VERBOSE"))
             fprintf(stderr, "[rovmpc] sharded closed loop: %d workgroups, %d resident at once -> %s\n", g.nblocks, capacity,
                     one_round ? "GPU-side hand-off" : "join per step");
         if (one_round) {
             h->cl_form = 4;
-            return h->cfg.dtype == ROVMPC_F64 ? closed_loop_sharded_handoff_t<double>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s)
-                                              : closed_loop_sharded_handoff_t<float>(h, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s);
+            return h->cfg.dtype == ROVMPC_F64 ? closed_loop_sharded_handoff_t<double>(h, k, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s)
+                                              : closed_loop_sharded_handoff_t<float>(h, k, d_exo, T, d_state, d_pools, n_pools, k_offset, d_results, s);
         }
     }
     h->cl_form = 3;

@@ -123,16 +123,45 @@ static int pick_ck(const rovmpc_config *c, int model, unsigned used, int n_cu, i
     return ck;
 }
 
+// ---- which instance a launch runs: the only place that names the rollout kernels ------------------------------------------
+struct Variant { LaunchKind kind; int N, CK; bool lean, literal_n; };       // {LAUNCH_PLAIN, 0, 0, false, false}: the generic kernel
+
+template <typename T, int MODEL, int VT> static const void *rollout_instance(const Variant &v) {
+    if constexpr (MODEL == MODEL_INTERP) {
+        return v.kind == LAUNCH_PLAIN ? (const void *)rollout_kernel<T, MODEL, VT> : nullptr;      // (one instance of the interpreter kernel)
+    } else {
+        // the literal-CK instances (see rollout_body, CKC), and with them the literal horizons of the BASELINE configurations
+        // (NC: N = 20 in double precision, N = 50 in single)
+        const bool ck16 = v.CK == 16, n20 = sizeof(T) == 8 && ck16 && v.N == 20 && v.literal_n;
+        if (v.kind == LAUNCH_SAMPLED) return (const void *)rollout_kernel_sampled<T, MODEL, VT>;
+        if (v.kind == LAUNCH_STEP) {
+            if constexpr (sizeof(T) == 8) { if (n20) return (const void *)closed_loop_step_kernel16_n20<T, MODEL, VT>; }
+            return ck16 ? (const void *)closed_loop_step_kernel16<T, MODEL, VT> : (const void *)closed_loop_step_kernel<T, MODEL, VT>;
+        }
+        if (3 * v.N + 2 > 64) {                                               // long horizons: see rollout_body, LONGH
+            if constexpr (sizeof(T) == 4) { if (v.lean && ck16 && v.N == 50 && v.literal_n) return (const void *)rollout_kernel_long_lean16_n50<T, MODEL, VT>; }
+            if (v.lean) return ck16 ? (const void *)rollout_kernel_long_lean16<T, MODEL, VT> : (const void *)rollout_kernel_long_lean<T, MODEL, VT>;
+            return ck16 ? (const void *)rollout_kernel_long16<T, MODEL, VT> : (const void *)rollout_kernel_long<T, MODEL, VT>;
+        }
+        if constexpr (sizeof(T) == 8) { if (n20) return v.lean ? (const void *)rollout_kernel_lean16_n20<T, MODEL, VT> : (const void *)rollout_kernel16_n20<T, MODEL, VT>; }
+        if (v.lean) return ck16 ? (const void *)rollout_kernel_lean16<T, MODEL, VT> : (const void *)rollout_kernel_lean<T, MODEL, VT>;
+        return ck16 ? (const void *)rollout_kernel16<T, MODEL, VT> : (const void *)rollout_kernel<T, MODEL, VT>;
+    }
+}
+
+template <typename T, int MODEL> static const void *instance_by_vt(int vt, const Variant &v) {
+    return vt == 0 ? rollout_instance<T, MODEL, 0>(v) : vt == 1 ? rollout_instance<T, MODEL, 1>(v) : rollout_instance<T, MODEL, 2>(v);
+}
+
+// model: MODEL_BUILTIN or MODEL_INTERP (the hiprtc module brings its own two functions)
+static const void *compiled_instance(const rovmpc_config &c, int model, const Variant &v) {
+    if (c.dtype == ROVMPC_F64) return model == MODEL_BUILTIN ? instance_by_vt<double, MODEL_BUILTIN>(c.vt_mode, v) : instance_by_vt<double, MODEL_INTERP>(c.vt_mode, v);
+    return model == MODEL_BUILTIN ? instance_by_vt<float, MODEL_BUILTIN>(c.vt_mode, v) : instance_by_vt<float, MODEL_INTERP>(c.vt_mode, v);
+}
+
 // Registers per lane of the compiled-in kernel for this handle's (dtype, vt_mode), from the code object.
 static int builtin_kernel_regs(const rovmpc_handle *h) {
-    const void *f = nullptr;
-    const int vt = h->cfg.vt_mode;
-    if (h->cfg.dtype == ROVMPC_F64)
-        f = vt == 0 ? (const void *)rollout_kernel<double, MODEL_BUILTIN, 0> : vt == 1 ? (const void *)rollout_kernel<double, MODEL_BUILTIN, 1>
-                                                                                     : (const void *)rollout_kernel<double, MODEL_BUILTIN, 2>;
-    else
-        f = vt == 0 ? (const void *)rollout_kernel<float, MODEL_BUILTIN, 0> : vt == 1 ? (const void *)rollout_kernel<float, MODEL_BUILTIN, 1>
-                                                                                    : (const void *)rollout_kernel<float, MODEL_BUILTIN, 2>;
+    const void *f = compiled_instance(h->cfg, MODEL_BUILTIN, {LAUNCH_PLAIN, 0, 0, false, false});
     hipFuncAttributes fa{};
     if (hipFuncGetAttributes(&fa, f) != hipSuccess || fa.numRegs <= 0) return 128;
     return fa.numRegs;
@@ -771,14 +800,18 @@ extern "C" int rovmpc_set_rotation_table(rovmpc_handle *h, const double *R) {
 
 // ---- launches -------------------------------------------------------------------------------
 
-template <typename T> void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, const double *d_state,
-                                            const void *d_U, void *d_traj_all, const Geo &g, int B) {
+// The argument block of one launch from the handle's model, workspace and geometry and from the launch's own options.  The
+// epoch is left to launch_rollout: an argument block that is never launched (a probe) takes none.
+template <typename T> void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, const double *d_state, const void *d_U,
+                                     double *d_result, const Geo &g, const StepOpts &o) {
     const rovmpc_config &c = h->cfg;
+    const int B = o.B;
     a.U = (const T *)d_U; a.state = d_state; a.k = (const RolloutConsts<T> *)h->d_k;
     a.code_th = h->d_code_th; a.code_ga = h->d_code_ga;
     a.consts = (const T *)h->d_consts; a.Rtab = (const T *)h->d_Rtab;
-    a.J = (T *)(h->arg_J ? h->arg_J : h->d_J); a.traj_all = (T *)d_traj_all;
-    a.blk_traj = h->d_blk_traj;
+    a.J = (T *)(o.J ? o.J : B > 1 ? h->d_Jb : h->d_J); a.traj_all = (T *)o.traj_all;
+    a.blk_traj = B > 1 ? h->d_blk_trajb : h->d_blk_traj;
+    a.result = d_result; a.k_offset = o.k_offset; a.slots = o.slots; a.rank = o.rank; a.world = o.world;
     a.N = c.N; a.K = c.K; a.CK = g.CK; a.M = c.n_shape_pts; a.n_th = h->n_th; a.n_ga = h->n_ga;
     a.prev_mode = c.prev_mode; a.integrator = c.integrator; a.debug = c.debug_flags; a.fmap = c.feature_map;
     a.used_planes = h->used_planes;
@@ -786,19 +819,17 @@ template <typename T> void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, 
     while ((1 << a.ck_shift) < g.CK) ++a.ck_shift;
     a.magic_3n = (unsigned)(4294967296ULL / (unsigned long long)(3 * c.N)) + 1u;
     a.granules = B > 1 ? h->d_granulesb : h->d_granules;
-    if (B > 1) { if (!h->arg_J) a.J = (T *)h->d_Jb; a.blk_traj = h->d_blk_trajb; }
     a.sweeper = (long long)B * g.nblocks <= h->n_cu ? 0 : g.nblocks - 1;
-    if (++*h->epoch_ctr == 0) ++*h->epoch_ctr;      // never 0 (the granules start zeroed)
-    a.epoch = *h->epoch_ctr;
+    a.epoch = 0;
     a.NT = g.NT; a.nblocks = g.nblocks;
-    a.plant_next = h->plant_next; a.plant_state = h->plant_state; a.plant_feedback = h->plant_feedback;
+    a.plant_next = o.plant_next; a.plant_state = o.plant_state; a.plant_feedback = o.plant_feedback;
     a.ring = nullptr; a.exo_cur = nullptr; a.seq_theta = nullptr; a.seq_gamma = nullptr;
     a.samp_seed = 0; a.samp_step = 0; a.samp_warm = nullptr; a.samp_best = nullptr; a.samp_blk_u = nullptr;
     a.step = 0; a.from_ring = 0; a.wait_theta = 0; a.publish = 0;
-    a.result_host = h->arg_result_host; a.done_flag = h->arg_done_flag; a.done_seq = h->arg_done_seq;
-    a.flag_consumed = h->arg_flag_consumed; a.flag_rolled = h->arg_flag_rolled;
-    a.consumed_need = h->arg_consumed_need; a.rolled_seq = h->arg_rolled_seq;
-    a.slot_bad = h->arg_slot_bad; a.err = h->d_err; a.inject = h->arg_inject;
+    a.result_host = o.result_host; a.done_flag = o.done_flag; a.done_seq = o.done_seq;
+    a.flag_consumed = o.flag_consumed; a.flag_rolled = o.flag_rolled;
+    a.consumed_need = o.consumed_need; a.rolled_seq = o.rolled_seq;
+    a.slot_bad = o.slot_bad; a.err = h->d_err; a.inject = o.inject;
     a.handoff_ticks = (unsigned long long)(h->handoff_timeout_ms * 1e5);      // 100 MHz clock
     a.stamps = h->d_stamps;
     // (single-problem launches only: a batch has a gamma path per problem)
@@ -806,76 +837,73 @@ template <typename T> void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, 
     a.gtab = (B == 1 && !no_gtab) ? (T *)h->d_gtab : nullptr;
     a.gtab_tag = B == 1 ? (unsigned long long *)((char *)h->d_gtab + (size_t)8 * (c.N + 1) * 8) : nullptr;
 }
-template void fill_args<double>(const rovmpc_handle *, RolloutArgs<double> &, const double *, const void *, void *, const Geo &, int);
-template void fill_args<float>(const rovmpc_handle *, RolloutArgs<float> &, const double *, const void *, void *, const Geo &, int);
+template void fill_args<double>(const rovmpc_handle *, RolloutArgs<double> &, const double *, const void *, double *, const Geo &, const StepOpts &);
+template void fill_args<float>(const rovmpc_handle *, RolloutArgs<float> &, const double *, const void *, double *, const Geo &, const StepOpts &);
 
-template <typename T, int MODEL, int VT>
-static hipError_t launch_one(const rovmpc_handle *h, const RolloutArgs<T> &a, int B, hipStream_t s) {
-    const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL, VT) * sizeof(T);
-    // the plain single-problem step of the compiled-in model takes the lean instantiation (see rollout_body)
-    const bool lean = MODEL == MODEL_BUILTIN && B == 1 && !a.slots && !a.flag_consumed && !a.flag_rolled && !a.result_host &&
-                      !a.done_flag && !a.plant_next;
-    auto kern = rollout_kernel<T, MODEL, VT>;
-    if constexpr (MODEL == MODEL_BUILTIN) {
-        // the literal-CK instances (see rollout_body, CKC), and with them the literal horizons of the BASELINE configurations
-        // (NC: N = 20 in double precision, N = 50 in single); ROVMPC_NO_LITERAL_N=1 keeps the horizon a run-time value
-        const bool ck16 = a.CK == 16 && a.ck_shift == 4;
-        const bool literal_n = !getenv("ROVMPC_NO_LITERAL_N");           // (read per launch: the parity tests switch it inside one process)
-        if (3 * a.N + 2 > 64) {                                                // long horizons: see rollout_body, LONGH
-            kern = lean ? (ck16 ? rollout_kernel_long_lean16<T, MODEL, VT> : rollout_kernel_long_lean<T, MODEL, VT>)
-                        : (ck16 ? rollout_kernel_long16<T, MODEL, VT> : rollout_kernel_long<T, MODEL, VT>);
-            if constexpr (sizeof(T) == 4) { if (lean && ck16 && a.N == 50 && literal_n) kern = rollout_kernel_long_lean16_n50<T, MODEL, VT>; }
-        } else if (lean) {
-            kern = ck16 ? rollout_kernel_lean16<T, MODEL, VT> : rollout_kernel_lean<T, MODEL, VT>;   // (no lean instance of the interpreter kernel)
-            if constexpr (sizeof(T) == 8) { if (ck16 && a.N == 20 && literal_n) kern = rollout_kernel_lean16_n20<T, MODEL, VT>; }
-        } else if (ck16) {
-            kern = rollout_kernel16<T, MODEL, VT>;
-            if constexpr (sizeof(T) == 8) { if (a.N == 20 && literal_n) kern = rollout_kernel16_n20<T, MODEL, VT>; }
-        }
+// What a launch of `kind` with geometry g and options o runs on this handle: the instance or the hiprtc function, with its
+// dynamic LDS; a kernel that needs more than 64 KiB of it is told so here.  ROVMPC_NO_LITERAL_N=1 keeps the horizon a run-time
+// value (read per call: the parity tests switch it inside one process).
+hipError_t rollout_launchable(const rovmpc_handle *h, LaunchKind kind, const Geo &g, const StepOpts &o, Launchable &k) {
+    const rovmpc_config &c = h->cfg;
+    k = Launchable();
+    if (h->model_kind == MODEL_JIT) {
+        k.mod = kind == LAUNCH_PLAIN ? h->jit_fn : kind == LAUNCH_STEP ? h->jit_fn_step : nullptr;
+        k.lds = lds_need(&c, g.CK, MODEL_JIT, jit_lds_planes(h->used_planes, c.vt_mode, c.feature_map), h->jit_gi);
+        if (!k.mod) return hipErrorInvalidDeviceFunction;
+        if (k.lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k.mod, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+        return hipSuccess;
     }
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const bool builtin = h->model_kind == MODEL_BUILTIN;
+    k.fn = compiled_instance(c, h->model_kind, {kind, c.N, g.CK, o.lean(), builtin && !getenv("ROVMPC_NO_LITERAL_N")});
+    k.lds = lds_need(&c, g.CK, h->model_kind);
+    if (!k.fn) return hipErrorInvalidDeviceFunction;
+    if (k.lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
         if (e != hipSuccess) return e;
     }
 #ifdef ROVMPC_STAMPS
     static bool told = false;
-    if (!told && getenv("ROVMPC_DIAG_OCCUPANCY")) {
+    if (!told && kind == LAUNCH_PLAIN && getenv("ROVMPC_DIAG_OCCUPANCY")) {
         told = true;
         int nb = -1; hipFuncAttributes fa{};
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, a.NT, lds);
-        hipFuncGetAttributes(&fa, (const void *)kern);
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, g.NT, k.lds);
+        hipFuncGetAttributes(&fa, k.fn);
         fprintf(stderr, "[rovmpc diag] NT %d lds %zu: resident workgroups/CU %d; regs %d static lds %zu scratch %zu maxThreads %d\n",
-                a.NT, lds, nb, fa.numRegs, fa.sharedSizeBytes, fa.localSizeBytes, fa.maxThreadsPerBlock);
+                g.NT, k.lds, nb, fa.numRegs, fa.sharedSizeBytes, fa.localSizeBytes, fa.maxThreadsPerBlock);
     }
 #endif
-    hipLaunchKernelGGL(kern, dim3(a.nblocks, B), dim3(a.NT), lds, s, a);
-    return hipGetLastError();
+    return hipSuccess;
 }
 
-template <typename T> static hipError_t launch_rollout_t(const rovmpc_handle *h, const double *d_state, const void *d_U,
-                                                         void *d_traj_all, double *d_result, long long k_offset,
-                                                         long long *d_slots, int rank, int world, hipStream_t s, int B = 1) {
-    RolloutArgs<T> a;
-    const Geo g = launch_geometry(h, B);
-    fill_args<T>(h, a, d_state, d_U, d_traj_all, g, B);
-    a.result = d_result; a.k_offset = k_offset; a.slots = d_slots; a.rank = rank; a.world = world;
-    const int vt = h->cfg.vt_mode;
-    if (h->model_kind == MODEL_JIT) {
-        const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_JIT, vt, jit_lds_planes(h->used_planes, vt, h->cfg.feature_map), h->jit_gi) * sizeof(T);
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)h->jit_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        size_t asz = sizeof(a);
-        void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-        return hipModuleLaunchKernel(h->jit_fn, a.nblocks, B, 1, a.NT, 1, 1, (unsigned)lds, s, nullptr, extra);
-    }
-    if (h->builtin) {
-        if (vt == 0) return launch_one<T, MODEL_BUILTIN, 0>(h, a, B, s);
-        if (vt == 1) return launch_one<T, MODEL_BUILTIN, 1>(h, a, B, s);
-        return launch_one<T, MODEL_BUILTIN, 2>(h, a, B, s);
-    }
-    if (vt == 0) return launch_one<T, MODEL_INTERP, 0>(h, a, B, s);
-    if (vt == 1) return launch_one<T, MODEL_INTERP, 1>(h, a, B, s);
-    return launch_one<T, MODEL_INTERP, 2>(h, a, B, s);
+// Workgroups of k the device holds at once with NT threads each: resident workgroups per CU x CUs.
+hipError_t launchable_capacity(const rovmpc_handle *h, const Launchable &k, int NT, int *capacity) {
+    int per_cu = 0;
+    const hipError_t e = k.mod ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.mod, NT, k.lds)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, NT, k.lds);
+    *capacity = e == hipSuccess ? per_cu * h->n_cu : 0;
+    return e;
 }
+
+// The launch itself; it takes the launch epoch (the tag of the granules this launch writes).  p: the second argument of the
+// closed-loop step kernels.
+template <typename T> hipError_t launch_rollout(const rovmpc_handle *h, const Launchable &k, RolloutArgs<T> &a, int B, hipStream_t s,
+                                                const HandoffArgs *p) {
+    if (++*h->epoch_ctr == 0) ++*h->epoch_ctr;      // never 0 (the granules start zeroed)
+    a.epoch = *h->epoch_ctr;
+    if (k.mod) {
+        struct { RolloutArgs<T> a; HandoffArgs p; } both;
+        void *buf = &a;
+        size_t asz = sizeof(a);
+        if (p) { both.a = a; both.p = *p; buf = &both; asz = sizeof(both); }
+        void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, buf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
+        return hipModuleLaunchKernel(k.mod, a.nblocks, B, 1, a.NT, 1, 1, (unsigned)k.lds, s, nullptr, extra);
+    }
+    void *args[] = {&a, const_cast<HandoffArgs *>(p)};
+    (void)hipLaunchKernel(k.fn, dim3(a.nblocks, B), dim3(a.NT), args, k.lds, s);
+    return hipGetLastError();
+}
+template hipError_t launch_rollout<double>(const rovmpc_handle *, const Launchable &, RolloutArgs<double> &, int, hipStream_t, const HandoffArgs *);
+template hipError_t launch_rollout<float>(const rovmpc_handle *, const Launchable &, RolloutArgs<float> &, int, hipStream_t, const HandoffArgs *);
 
 int check_ready(rovmpc_handle *h) {
     if (!h->has_model) FAIL(h, ROVMPC_ERR_NO_MODEL, "rovmpc_set_model has not been called");
@@ -887,17 +915,25 @@ int check_ready(rovmpc_handle *h) {
     return ROVMPC_OK;
 }
 
-int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, void *d_traj_all, double *d_result,
-                        long long k_offset, long long *d_slots, int rank, int world, hipStream_t s, int B) {
+template <typename T> static hipError_t launch_plain_t(const rovmpc_handle *h, const double *d_state, const void *d_U, double *d_result,
+                                                       hipStream_t s, const StepOpts &o) {
+    RolloutArgs<T> a;
+    Launchable k;
+    const Geo g = launch_geometry(h, o.B);
+    fill_args<T>(h, a, d_state, d_U, d_result, g, o);
+    const hipError_t e = rollout_launchable(h, LAUNCH_PLAIN, g, o, k);
+    return e != hipSuccess ? e : launch_rollout<T>(h, k, a, o.B, s);
+}
+
+int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, double *d_result, hipStream_t s, const StepOpts &o) {
     int rc = check_ready(h);
     if (rc) return rc;
     const bool time_it = h->timing && h->ev_used + 2 <= (int)h->ev.size();
     if (time_it) HIPCHK(h, hipEventRecord(h->ev[h->ev_used], s));
-    hipError_t e = h->cfg.dtype == ROVMPC_F64
-                       ? launch_rollout_t<double>(h, d_state, d_U, d_traj_all, d_result, k_offset, d_slots, rank, world, s, B)
-                       : launch_rollout_t<float>(h, d_state, d_U, d_traj_all, d_result, k_offset, d_slots, rank, world, s, B);
+    hipError_t e = h->cfg.dtype == ROVMPC_F64 ? launch_plain_t<double>(h, d_state, d_U, d_result, s, o)
+                                              : launch_plain_t<float>(h, d_state, d_U, d_result, s, o);
     if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "rollout kernel launch failed: %s", hipGetErrorString(e));
-    h->last_batch = B;
+    if (!o.J) h->last_batch = o.B;                  // (rovmpc_batch_costs_device: the last launch that wrote the handle's own costs)
     if (time_it) { HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], s)); h->ev_used += 2; }
     return ROVMPC_OK;
 }
@@ -905,7 +941,7 @@ int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, void 
 extern "C" int rovmpc_step_device(rovmpc_handle *h, const double *d_state, const void *d_U, double *d_result, void *stream) {
     if (!h) return ROVMPC_ERR_INVALID;
     if (!d_state || !d_U || !d_result) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_step_device: null pointer");
-    return enqueue_step(h, d_state, d_U, nullptr, d_result, 0, nullptr, 0, 1, (hipStream_t)stream);
+    return enqueue_step(h, d_state, d_U, d_result, (hipStream_t)stream);
 }
 
 // Workspace of a batched launch: costs, per-workgroup trajectories and hand-off granules for B problems.  The larger set is
@@ -939,11 +975,13 @@ extern "C" int rovmpc_step_batch_device(rovmpc_handle *h, int32_t B, const doubl
     if (!h) return ROVMPC_ERR_INVALID;
     if (B < 1 || B > 65535) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_step_batch_device: B must be in 1..65535 (got %d)", B);
     if (!d_states || !d_U || !d_results) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_step_batch_device: null pointer");
-    if (B == 1) return enqueue_step(h, d_states, d_U, nullptr, d_results, 0, nullptr, 0, 1, (hipStream_t)stream);
+    if (B == 1) return enqueue_step(h, d_states, d_U, d_results, (hipStream_t)stream);
     int rc = check_ready(h);
     if (rc) return rc;
     if ((rc = ensure_batch(h, B))) return rc;
-    return enqueue_step(h, d_states, d_U, nullptr, d_results, 0, nullptr, 0, 1, (hipStream_t)stream, B);
+    StepOpts o;
+    o.B = B;
+    return enqueue_step(h, d_states, d_U, d_results, (hipStream_t)stream, o);
 }
 
 extern "C" int rovmpc_batch_costs_device(rovmpc_handle *h, const void **d_J) {
@@ -1028,36 +1066,23 @@ extern "C" int rovmpc_sample_candidates_device(rovmpc_handle *h, uint64_t seed, 
 
 // Compiled-in model: the rollout kernel draws its candidates itself (rollout_kernel_sampled) -- no sampler launch, no
 // candidate tensor, the state in the kernel arguments.
-template <typename T, int VT>
-static hipError_t launch_sampled(const rovmpc_handle *h, const RolloutArgs<T> &a, hipStream_t s) {
-    const size_t lds = rollout_lds_elems<T>(a.N, a.CK, MODEL_BUILTIN, VT) * sizeof(T);
-    auto kern = rollout_kernel_sampled<T, MODEL_BUILTIN, VT>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(a.NT), lds, s, a);
-    return hipGetLastError();
-}
-
 template <typename T>
 static int fused_sampled_step_t(rovmpc_handle *h, const rovmpc_state *state, uint64_t seed, uint64_t step, const double *mean3,
-                                const double *std3, int warm, unsigned long long seq) {
+                                const double *std3, int warm, const StepOpts &o) {
     const int cur = (int)(h->samp_steps & 1);
     const size_t row = (size_t)h->cfg.N * 3;
     RolloutArgs<T> a;
+    Launchable k;
     const Geo g = launch_geometry(h, 1);
-    fill_args<T>(h, a, h->d_state, nullptr, nullptr, g, 1);
-    a.result = h->d_result; a.k_offset = 0; a.slots = nullptr; a.rank = 0; a.world = 1;
-    a.result_host = h->samp_box.d_out; a.done_flag = h->samp_box.d_done; a.done_seq = seq;
+    fill_args<T>(h, a, h->d_state, nullptr, h->d_result, g, o);
     a.samp_seed = seed; a.samp_step = step;
     for (int i = 0; i < 3; ++i) { a.samp_mean[i] = mean3[i]; a.samp_std[i] = std3[i]; }
     a.samp_warm = warm ? h->d_best + (size_t)(cur ^ 1) * row : nullptr;
     a.samp_best = h->d_best + (size_t)cur * row;
     a.samp_blk_u = h->d_blk_u;
     memcpy(a.samp_state, state, sizeof(a.samp_state));
-    const int vt = h->cfg.vt_mode;
-    hipError_t e = vt == 0 ? launch_sampled<T, 0>(h, a, h->stream) : vt == 1 ? launch_sampled<T, 1>(h, a, h->stream) : launch_sampled<T, 2>(h, a, h->stream);
+    hipError_t e = rollout_launchable(h, LAUNCH_SAMPLED, g, o, k);
+    if (e == hipSuccess) e = launch_rollout<T>(h, k, a, 1, h->stream);
     if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "fused sampling launch failed: %s", hipGetErrorString(e));
     return ROVMPC_OK;
 }
@@ -1078,7 +1103,9 @@ extern "C" int rovmpc_mpc_step_sampled(rovmpc_handle *h, const rovmpc_state *sta
     const bool prev_fused = h->samp_steps > 0 && h->last_fused;
     h->last_seed = seed; h->last_step = step; h->last_warm = warm; h->last_fused = fused;
     for (int i = 0; i < 3; ++i) { h->last_mean[i] = mean3[i]; h->last_std[i] = std3[i]; }
-    unsigned long long seq = h->samp_steps + 1;
+    const unsigned long long seq = h->samp_steps + 1;
+    StepOpts o;                                  // either way the step publishes its record into the sampled step's mailbox
+    o.result_host = h->samp_box.d_out; o.done_flag = h->samp_box.d_done; o.done_seq = seq;
     if (fused) {
         if (!h->d_best) {
             const size_t max_blocks = h->cfg.candidates_per_block > 0 ? (size_t)((h->cfg.K + h->cfg.candidates_per_block - 1) / h->cfg.candidates_per_block) : (size_t)h->cfg.K;
@@ -1088,18 +1115,15 @@ extern "C" int rovmpc_mpc_step_sampled(rovmpc_handle *h, const rovmpc_state *sta
             HIPCHK(h, hipMalloc((void **)&h->d_blk_u, max_blocks * (size_t)h->cfg.N * 9 * sizeof(unsigned long long)));
             HIPCHK(h, hipMemset(h->d_blk_u, 0, max_blocks * (size_t)h->cfg.N * 9 * sizeof(unsigned long long)));
         }
-        rc = h->cfg.dtype == ROVMPC_F64 ? fused_sampled_step_t<double>(h, state, seed, step, mean3, std3, warm, seq)
-                                        : fused_sampled_step_t<float>(h, state, seed, step, mean3, std3, warm, seq);
+        rc = h->cfg.dtype == ROVMPC_F64 ? fused_sampled_step_t<double>(h, state, seed, step, mean3, std3, warm, o)
+                                        : fused_sampled_step_t<float>(h, state, seed, step, mean3, std3, warm, o);
         ++h->samp_steps;
         if (rc) return rc;
     } else {
-    const double *warm_seq = (warm && prev_fused) ? h->d_best + (size_t)(cur ^ 1) * h->cfg.N * 3 : nullptr;
-    if ((rc = launch_sampler(h, state, seed, step, mean3, std3, warm, h->d_Us[cur], h->d_Us[cur ^ 1], h->stream, warm_seq))) return rc;
-    seq = ++h->samp_steps;
-    h->arg_result_host = h->samp_box.d_out; h->arg_done_flag = h->samp_box.d_done; h->arg_done_seq = seq;
-    rc = enqueue_step(h, h->d_state, h->d_Us[cur], nullptr, h->d_result, 0, nullptr, 0, 1, h->stream);
-    h->arg_result_host = nullptr; h->arg_done_flag = nullptr;
-    if (rc) return rc;
+        const double *warm_seq = (warm && prev_fused) ? h->d_best + (size_t)(cur ^ 1) * h->cfg.N * 3 : nullptr;
+        if ((rc = launch_sampler(h, state, seed, step, mean3, std3, warm, h->d_Us[cur], h->d_Us[cur ^ 1], h->stream, warm_seq))) return rc;
+        ++h->samp_steps;
+        if ((rc = enqueue_step(h, h->d_state, h->d_Us[cur], h->d_result, h->stream, o))) return rc;
     }
     if ((rc = mailbox_wait(h, h->samp_box, seq, "step"))) return rc;
     memcpy(record_out, h->samp_box.h_out, (size_t)rovmpc_result_len(h) * sizeof(double));
@@ -1152,7 +1176,9 @@ extern "C" int rovmpc_step_device_sharded(rovmpc_handle *h, const double *d_stat
     if (!h) return ROVMPC_ERR_INVALID;
     if (!d_state || !d_U || !d_slots) FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_step_device_sharded: null pointer");
     if (world < 1 || rank < 0 || rank >= world) FAIL(h, ROVMPC_ERR_INVALID, "bad rank/world %d/%d", rank, world);
-    return enqueue_step(h, d_state, d_U, nullptr, h->d_result, k_offset, (long long *)d_slots, rank, world, (hipStream_t)stream);
+    StepOpts o;
+    o.k_offset = k_offset; o.slots = (long long *)d_slots; o.rank = rank; o.world = world;
+    return enqueue_step(h, d_state, d_U, h->d_result, (hipStream_t)stream, o);
 }
 
 extern "C" int rovmpc_select_device(rovmpc_handle *h, const int64_t *d_slots, int32_t world, double *d_result, void *stream) {
@@ -1179,7 +1205,7 @@ extern "C" int rovmpc_step(rovmpc_handle *h, const rovmpc_state *state, const vo
     int rc = check_ready(h);
     if (rc) return rc;
     if ((rc = stage_inputs(h, state, U))) return rc;
-    if ((rc = enqueue_step(h, h->d_state, h->d_U, nullptr, h->d_result, 0, nullptr, 0, 1, h->stream))) return rc;
+    if ((rc = enqueue_step(h, h->d_state, h->d_U, h->d_result, h->stream))) return rc;
     const size_t R = rovmpc_result_len(h);
     HIPCHK(h, hipMemcpyAsync(h->h_result, h->d_result, R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1198,7 +1224,9 @@ extern "C" int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state,
     if ((rc = stage_inputs(h, state, U))) return rc;
     const size_t tbytes = (size_t)h->cfg.K * (h->cfg.N + 1) * 2 * h->esz;
     if (traj_all && !h->d_traj_all) HIPCHK(h, hipMalloc(&h->d_traj_all, tbytes));
-    if ((rc = enqueue_step(h, h->d_state, h->d_U, traj_all ? h->d_traj_all : nullptr, nullptr, 0, nullptr, 0, 1, h->stream))) return rc;
+    StepOpts o;
+    o.traj_all = traj_all ? h->d_traj_all : nullptr;
+    if ((rc = enqueue_step(h, h->d_state, h->d_U, nullptr, h->stream, o))) return rc;
     HIPCHK(h, hipMemcpyAsync(J_out, h->d_J, (size_t)h->cfg.K * h->esz, hipMemcpyDeviceToHost, h->stream));
     if (traj_all) HIPCHK(h, hipMemcpyAsync(traj_all, h->d_traj_all, tbytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1518,6 +1546,8 @@ static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, c
     if (c.B > 1 && (rc = ensure_batch(h, c.B))) return rc;     // an early-out unless a failed growth elsewhere took it away
     if (h->tether_on && (rc = ensure_tether_traj(h, c.B))) return rc;      // the batch grew after the setting was made
     void *const traj_all = h->tether_on ? h->d_tether_traj : nullptr;
+    StepOpts rollout;                            // the rollouts write the controller's own costs, not the handle's
+    rollout.J = c.J; rollout.traj_all = traj_all; rollout.B = c.B;
     const size_t B = (size_t)c.B, half = B * 3 * (size_t)h->cfg.N, exo_stride = (size_t)loop.T * ROVMPC_STATE_LEN;
     if (!c.single) {
         if (states) memcpy(c.h_stage, states, B * sizeof(rovmpc_state));
@@ -1545,12 +1575,7 @@ static int plan_step(rovmpc_handle *h, PlanCtl &c, const rovmpc_state *states, c
                                           c.state, loop.feedback, loop.W, exo_stride};
             }
             if ((rc = sample(it))) return rc;
-            const int last_batch = h->last_batch;       // rovmpc_batch_costs_device keeps naming the last launch that used the
-            h->arg_J = c.J;                             // handle's own cost buffers; this one writes the controller's J
-            rc = enqueue_step(h, c.state, c.U, traj_all, c.record, 0, nullptr, 0, 1, h->stream, c.B);
-            h->arg_J = nullptr;
-            h->last_batch = last_batch;
-            if (rc) return rc;
+            if ((rc = enqueue_step(h, c.state, c.U, c.record, h->stream, rollout))) return rc;
             if (h->nav_on && (rc = launch_nav_cost(h, c.state, c.U, c.J, nullptr, step + (uint64_t)t, c.B,
                                                    !c.single && h->nav_Bt == c.B ? 3 * (size_t)h->nav_Tr : 0, h->stream))) return rc;
             if (traj_all && (rc = launch_tether_cost(h, c.state, c.U, traj_all, c.J, nullptr, nullptr, c.B, h->stream))) return rc;
@@ -2351,6 +2376,41 @@ int place_comm_streams(rovmpc_handle *h, hipStream_t caller) {
     return ROVMPC_OK;
 }
 
+// Takes the next collective slot p for one sharded step and writes the step's sharding and slot hand-off options into o.
+// Slot buffer p is free once the select of NSLOT steps ago has read it.  On the host: that job has been handed
+// to the collective stream (bounds the queue).  On the GPU: the rollout's last workgroup waits for
+// consumed[p] >= uses - 1 before it writes the row and then publishes rolled[p] = uses; the collective stream
+// polls that (wait_rolled_kernel).  The caller's stream carries rollout kernels only.
+int comm_take_slot(rovmpc_handle *h, StepOpts &o, int &p) {
+    p = h->comm_flip;
+    h->comm_flip = (h->comm_flip + 1) % rovmpc_handle::NSLOT;
+    if (h->slot_used[p]) {
+        int rc = comm_wait_enqueued(h, p);
+        if (rc) return rc;
+    }
+    h->slot_used[p] = true;
+    const unsigned long long use = ++h->slot_uses[p];
+    o.slots = h->d_slots[p]; o.rank = h->comm_rank; o.world = h->comm_world;
+    o.flag_consumed = h->d_flags + rovmpc_handle::NSLOT + p; o.consumed_need = use - 1;
+    o.flag_rolled = h->d_flags + p; o.rolled_seq = use;
+    o.slot_bad = h->d_flags + 2 * rovmpc_handle::NSLOT + p;
+    o.inject = 0;
+    if (h->inject_skip_rolled > 0) { --h->inject_skip_rolled; o.inject |= 1; }
+    if (h->inject_skip_consumed > 0) { --h->inject_skip_consumed; o.inject |= 2; }
+    return ROVMPC_OK;
+}
+
+// Hands the collective and select of the step launched with o on slot p to the worker thread; the global record goes to
+// d_result.  Closed loop: the select also hands theta over to step `step_next` through ring / seq_theta.
+void comm_submit(rovmpc_handle *h, int p, const StepOpts &o, double *d_result, double *ring, unsigned long long *seq_theta, long long step_next) {
+    {
+        std::lock_guard<std::mutex> lk(h->comm_mu);
+        h->comm_q.push_back({p, d_result, o.rolled_seq, (int)(h->comm_rr++ % (unsigned long long)h->ncomm), o.inject, ring, seq_theta, step_next});
+        ++h->comm_submitted[p];
+    }
+    h->comm_cv.notify_all();
+}
+
 extern "C" int rovmpc_step_device_allreduce(rovmpc_handle *h, const double *d_state, const void *d_U, int64_t k_offset,
                                             double *d_result, void *stream) {
     if (!h) return ROVMPC_ERR_INVALID;
@@ -2361,34 +2421,12 @@ extern "C" int rovmpc_step_device_allreduce(rovmpc_handle *h, const double *d_st
         int rc = place_comm_streams(h, s);
         if (rc) return rc;
     }
-    const int p = h->comm_flip;
-    h->comm_flip = (h->comm_flip + 1) % rovmpc_handle::NSLOT;
-    // Slot buffer p is free once the select of NSLOT steps ago has read it.  On the host: that job has been handed
-    // to the collective stream (bounds the queue).  On the GPU: the rollout's last workgroup waits for
-    // consumed[p] >= uses - 1 before it writes the row and then publishes rolled[p] = uses; the collective stream
-    // polls that (wait_rolled_kernel).  The caller's stream carries rollout kernels only.
-    if (h->slot_used[p]) {
-        int rc = comm_wait_enqueued(h, p);
-        if (rc) return rc;
-    }
-    h->slot_used[p] = true;
-    const unsigned long long use = ++h->slot_uses[p];
-    h->arg_flag_consumed = h->d_flags + rovmpc_handle::NSLOT + p; h->arg_consumed_need = use - 1;
-    h->arg_flag_rolled = h->d_flags + p; h->arg_rolled_seq = use;
-    h->arg_slot_bad = h->d_flags + 2 * rovmpc_handle::NSLOT + p;
-    int inject = 0;
-    if (h->inject_skip_rolled > 0) { --h->inject_skip_rolled; inject |= 1; }
-    if (h->inject_skip_consumed > 0) { --h->inject_skip_consumed; inject |= 2; }
-    h->arg_inject = inject;
-    int rc = enqueue_step(h, d_state, d_U, nullptr, h->d_result, k_offset, h->d_slots[p], h->comm_rank, h->comm_world, s);
-    h->arg_flag_consumed = nullptr; h->arg_flag_rolled = nullptr; h->arg_slot_bad = nullptr; h->arg_inject = 0;
+    StepOpts o;
+    o.k_offset = k_offset;
+    int p, rc = comm_take_slot(h, o, p);
     if (rc) return rc;
-    {
-        std::lock_guard<std::mutex> lk(h->comm_mu);
-        h->comm_q.push_back({p, d_result, use, (int)(h->comm_rr++ % (unsigned long long)h->ncomm), inject, nullptr, nullptr, 0});
-        ++h->comm_submitted[p];
-    }
-    h->comm_cv.notify_all();
+    if ((rc = enqueue_step(h, d_state, d_U, h->d_result, s, o))) return rc;
+    comm_submit(h, p, o, d_result);
     return ROVMPC_OK;
 }
 

@@ -1,5 +1,6 @@
 // rovmpc_internal.h -- what the host units of librovmpc.so (rovmpc.hip, helpers_host.hip, closed_loop_host.hip) share: the handle and its parts,
-// the error macros and the host functions that more than one unit calls.  Nothing declared here is exported from the library.
+// the error macros, the options of one rollout launch (StepOpts), what a launch runs (Launchable) and the host functions that
+// more than one unit calls.  Nothing declared here is exported from the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -99,11 +100,6 @@ struct rovmpc_handle {
     unsigned *epoch_ctr = nullptr;            // launches issued (host counter; tag of the next launch = ++*epoch_ctr, never 0)
     unsigned long long *d_stamps = nullptr;   // diagnostic library only
     void *d_gtab = nullptr;                   // shared gamma table of a launch (long horizons) + its epoch tag behind it
-    const unsigned long long *arg_flag_consumed = nullptr;   // hand-off flags of the step being enqueued (native collective)
-    unsigned long long *arg_flag_rolled = nullptr;
-    unsigned long long arg_consumed_need = 0, arg_rolled_seq = 0;
-    unsigned long long *arg_slot_bad = nullptr;
-    int arg_inject = 0;
     // error word: pinned host memory mapped into the device (ERR_* bits of rollout_kernels.h), raised at system scope by
     // the kernels' give-up paths, read and cleared by rovmpc_comm_sync / rovmpc_device_status
     unsigned *h_err = nullptr, *d_err = nullptr;
@@ -123,8 +119,6 @@ struct rovmpc_handle {
     unsigned long long *d_blk_u = nullptr;       // [max_blocks][6 N] tagged granules + [max_blocks][3 N] doubles: per-workgroup best controls of a fused-sampling step
     // what the last sampled step drew with (rovmpc_sampled_candidates re-draws the tensor for inspection)
     unsigned long long last_seed = 0, last_step = 0; double last_mean[3] = {}, last_std[3] = {}; int last_warm = 0; bool last_fused = false;
-    double *arg_result_host = nullptr; unsigned long long *arg_done_flag = nullptr; unsigned long long arg_done_seq = 0;
-    void *arg_J = nullptr;                       // costs of the launch being enqueued go here instead of d_J (null: d_J)
     // MPPI (rovmpc_mppi_*): mailbox [record, nu*, stats]; CEM (rovmpc_cem_*): [record, mu*, sigma*, stats, elite list]
     PlanCtl mppi{"MPPI", "mppi", true}, cem{"CEM", "cem", true};
     PlanCtl mppi_b{"MPPI", "mppi", false}, cem_b{"CEM", "cem", false};
@@ -150,11 +144,8 @@ struct rovmpc_handle {
     void *d_tether_traj = nullptr;
     int tether_cap = 0;                          // problems d_tether_traj holds
     // batched launches: workspace for `batch_cap` problems
-    int batch_cap = 0, last_batch = 1;
+    int batch_cap = 0, last_batch = 1;           // last_batch: B of the last launch that wrote the handle's own cost buffers
     void *d_Jb = nullptr; double *d_blk_trajb = nullptr; unsigned long long *d_granulesb = nullptr;
-    const double *plant_next = nullptr;       // closed loop: plant update fused into the step being enqueued
-    double *plant_state = nullptr;
-    int plant_feedback = 0;
     double *h_result = nullptr;      // pinned
     // native collective (rovmpc_comm_*)
     ncclComm_t comm = nullptr;
@@ -218,16 +209,51 @@ struct rovmpc_handle {
 // Geometry of one launch: B problems of K candidates each in the grid (B = 1: the handle's own geometry).
 struct Geo { int CK, NT, nblocks; };
 
+// What one rollout launch is asked for beyond state, candidates and record, in the groups of RolloutArgs.  The default is the
+// plain single step; a launch reads its options from this value alone, never from the handle.
+struct StepOpts {
+    void *J = nullptr, *traj_all = nullptr;      // costs (null: the handle's d_J, d_Jb of a batch), every candidate's trajectory
+    long long k_offset = 0;                      // sharding: first global candidate, slot row image, rank / world
+    long long *slots = nullptr;
+    int rank = 0, world = 1;
+    double *result_host = nullptr;               // mailbox the step publishes its record into, with done_seq behind it
+    unsigned long long *done_flag = nullptr, done_seq = 0;
+    const unsigned long long *flag_consumed = nullptr;      // slot hand-off of the native collective (comm_take_slot)
+    unsigned long long consumed_need = 0;
+    unsigned long long *flag_rolled = nullptr, rolled_seq = 0, *slot_bad = nullptr;
+    int inject = 0;
+    const double *plant_next = nullptr;          // closed loop: plant update fused into the step's epilogue
+    double *plant_state = nullptr;
+    int plant_feedback = 0;
+    int B = 1;                                   // problems in the grid
+    // the plain single-problem step takes the lean instantiation of the compiled-in kernel (see rollout_body)
+    bool lean() const { return B == 1 && !slots && !flag_consumed && !flag_rolled && !result_host && !done_flag && !plant_next; }
+};
+
+// Which kernel a launch runs and what it is launched with.
+enum LaunchKind { LAUNCH_PLAIN, LAUNCH_SAMPLED, LAUNCH_STEP };     // rollout_kernel*, rollout_kernel_sampled, closed_loop_step_kernel*
+struct Launchable {
+    const void *fn = nullptr;        // instance compiled into the library (compiled-in model or interpreter), or
+    hipFunction_t mod = nullptr;     // function of the hiprtc module
+    size_t lds = 0;                  // dynamic LDS, bytes
+};
+
 // ---- rovmpc.hip ----
 Geo launch_geometry(const rovmpc_handle *h, int B);
 const char *validate_code(const int32_t *code, int n, int n_feat, int n_consts);
+hipError_t rollout_launchable(const rovmpc_handle *h, LaunchKind kind, const Geo &g, const StepOpts &o, Launchable &k);
+hipError_t launchable_capacity(const rovmpc_handle *h, const Launchable &k, int NT, int *capacity);
 template <typename T> void fill_args(const rovmpc_handle *h, RolloutArgs<T> &a, const double *d_state, const void *d_U,
-                                     void *d_traj_all, const Geo &g, int B);      // T = double, float
+                                     double *d_result, const Geo &g, const StepOpts &o);      // T = double, float
+template <typename T> hipError_t launch_rollout(const rovmpc_handle *h, const Launchable &k, RolloutArgs<T> &a, int B, hipStream_t s,
+                                                const HandoffArgs *p = nullptr);
 int check_ready(rovmpc_handle *h);
-int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, void *d_traj_all, double *d_result, long long k_offset,
-                 long long *d_slots, int rank, int world, hipStream_t s, int B = 1);
+int enqueue_step(rovmpc_handle *h, const double *d_state, const void *d_U, double *d_result, hipStream_t s, const StepOpts &o = StepOpts());
 int launched(rovmpc_handle *h, const char *what);
 int comm_wait_enqueued(rovmpc_handle *h, int p);
+int comm_take_slot(rovmpc_handle *h, StepOpts &o, int &p);
+void comm_submit(rovmpc_handle *h, int p, const StepOpts &o, double *d_result, double *ring = nullptr, unsigned long long *seq_theta = nullptr,
+                 long long step_next = 0);
 int choose_side_streams(rovmpc_handle *h, hipStream_t caller, const std::vector<hipStream_t> &seed, int want,
                         std::vector<hipStream_t> &chosen, std::string &log);
 int place_comm_streams(rovmpc_handle *h, hipStream_t caller);
