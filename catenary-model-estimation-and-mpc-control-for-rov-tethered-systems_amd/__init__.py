@@ -23,6 +23,6 @@ from .trajgen import generate_rov_trajectories, trajectory_csv
 from ._lib import MPPIParams, CEMParams, FitParams, TrackParams, RefitParams
 from .mpc import MPC, MPPI, CEM, BatchedMPPI, BatchedCEM, NavCost, TetherCost, PlanLoopResult, GaussianSampler, DeviceGaussianSampler, synthetic_problem
 from .closed_loop import run_plan_closed_loop
-from .scoring import score_rows, select_model, RowScores, refit_rows, RowRefit, RefitStatus
+from .scoring import score_rows, select_model, RowScores, refit_rows, RowRefit, RefitStatus, score_pairs, PairSkill
 
 __version__ = "0.1.0"

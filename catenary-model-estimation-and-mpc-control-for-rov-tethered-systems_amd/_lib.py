@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 import os
 from typing import Optional
 
@@ -316,6 +317,51 @@ class RefitParams(C.Structure):
         return p
 
 
+HORIZON_COLS = 9
+HORIZON_TILE = 128
+HORIZON_NAMES = ("rmse_theta", "rmse_gamma", "max_abs_theta", "max_abs_gamma", "n_ok", "ss_theta", "ss_gamma", "ss_hold_theta",
+                 "ss_hold_gamma")
+HORIZON_SLOTS = ("theta", "gamma", "theta_prev", "gamma_prev", "cos_theta", "sin_gamma")
+# the reference's two first-order feature maps: which slots of a row the pair's own state is written to (-1: none)
+FEATURE_MAPS = {"gen1": (14, 15, 16, 17, -1, -1), "gen2": (12, 13, -1, -1, 14, 15)}
+
+
+class HorizonParams(C.Structure):
+    """Mirror of ``rovmpc_horizon_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("integrator", C.c_int32), ("prev_mode", C.c_int32), ("H", C.c_int32), ("stride", C.c_int32)] + \
+               [("slot_" + n, C.c_int32) for n in HORIZON_SLOTS]
+
+    @classmethod
+    def make(cls, H: int = 20, stride: int = 1, integrator: int = RK4, prev_mode: int = PREV_INTERP, slots=FEATURE_MAPS["gen1"],
+             F: Optional[int] = None) -> "HorizonParams":
+        for name, v in (("horizon", H), ("stride", stride)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= int(v) < 2 ** 31:
+                raise ValueError(f"{name} must be an integer >= 1 (got {v!r})")
+        if integrator not in (RK4, EULER):
+            raise ValueError(f"integrator must be RK4 or EULER (got {integrator!r}; the second-order maps are not provided)")
+        if prev_mode not in (PREV_INTERP, PREV_HOLD):
+            raise ValueError(f"prev_mode must be PREV_INTERP or PREV_HOLD (got {prev_mode!r})")
+        slots = tuple(slots)
+        if len(slots) != len(HORIZON_SLOTS) or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in slots):
+            raise ValueError(f"slots must be {len(HORIZON_SLOTS)} integers {HORIZON_SLOTS} (got {slots!r})")
+        slots = tuple(int(v) for v in slots)
+        if slots[0] == -1 or slots[1] == -1:
+            raise ValueError("the theta and gamma slots are required")
+        used = [v for v in slots if v != -1]
+        if any(v < 0 or (F is not None and v >= F) for v in used):
+            raise ValueError(f"a named slot is outside 0..{'F - 1' if F is None else F - 1} (got {slots!r})")
+        if len(set(used)) != len(used):
+            raise ValueError(f"two names on one slot (got {slots!r})")
+        p = cls()
+        p.struct_size, p.integrator, p.prev_mode, p.H, p.stride = C.sizeof(cls), int(integrator), int(prev_mode), int(H), int(stride)
+        for n, v in zip(HORIZON_SLOTS, slots):
+            setattr(p, "slot_" + n, v)
+        return p
+
+    def slots(self):
+        return tuple(getattr(self, "slot_" + n) for n in HORIZON_SLOTS)
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     "rovmpc_version": (C.c_char_p, []),
@@ -399,6 +445,11 @@ _SIGNATURES = {
                                     C.POINTER(RefitParams), _P, _P]),
     "rovmpc_refit_rows_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P,
                                            C.c_int32, C.POINTER(RefitParams), _P, _P]),
+    "rovmpc_default_horizon_params": (None, [C.POINTER(HorizonParams)]),
+    "rovmpc_score_pairs": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P,
+                                     C.c_int64, C.c_int64, _P, _P, C.POINTER(HorizonParams), _P, _P]),
+    "rovmpc_score_pairs_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P,
+                                            _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(HorizonParams), _P, _P]),
     "rovmpc_solve_catenary": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, _P, _P]),
     "rovmpc_rodrigues": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     "rovmpc_catenary_points": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, C.c_int32, _P, _P, _P]),

@@ -6,6 +6,7 @@
 #include "track_kernels.h"
 #include "score_kernels.h"
 #include "refit_kernels.h"
+#include "horizon_kernels.h"
 
 // ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
 
@@ -894,4 +895,166 @@ extern "C" int rovmpc_refit_rows_device(rovmpc_handle *h, const int32_t *code, c
     plan.a.X = d_X; plan.a.target = d_target; plan.a.consts_out = d_consts_out; plan.a.out = d_out;
     launch_refit(h, R, plan.a);
     return launched(h, "row refit");
+}
+
+// ---- (theta, gamma) row pairs scored by closed-loop N-step-ahead skill (horizon_kernels.h) -----
+
+extern "C" void rovmpc_default_horizon_params(rovmpc_horizon_params *p) {
+    if (!p) return;
+    p->struct_size = (int32_t)sizeof(rovmpc_horizon_params);
+    p->integrator = ROVMPC_RK4;
+    p->prev_mode = ROVMPC_PREV_INTERP;
+    p->H = 20;
+    p->stride = 1;
+    p->slot_theta = 14; p->slot_gamma = 15; p->slot_theta_prev = 16; p->slot_gamma_prev = 17;
+    p->slot_cos_theta = -1; p->slot_sin_gamma = -1;
+}
+
+// one front of a pair call: its offsets and its rows, named by the front in the message
+static int check_front(rovmpc_handle *h, const char *entry, const char *front, const int32_t *code, const int32_t *code_off,
+                       const double *consts, const int32_t *const_off, int32_t R, int32_t F) {
+    if (code_off[0] != 0 || const_off[0] != 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: %s front: code_off[0] and const_off[0] must be 0", entry, front);
+    for (int r = 0; r < R; ++r)
+        if (code_off[r + 1] < code_off[r] || const_off[r + 1] < const_off[r] || code_off[r + 1] - code_off[r] > ROVMPC_MAX_CODE ||
+            const_off[r + 1] - const_off[r] > ROVMPC_MAX_CODE)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: offsets of %s row %d are not monotone (or the row is longer than %d)", entry, front, r, ROVMPC_MAX_CODE);
+    if (const_off[R] > 0 && !consts) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (consts of the %s front)", entry, front);
+    for (int r = 0; r < R; ++r)
+        if (const char *why = validate_code(code + code_off[r], code_off[r + 1] - code_off[r], F, const_off[r + 1] - const_off[r]))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: %s row %d: %s", entry, front, r, why);
+    return ROVMPC_OK;
+}
+
+namespace {
+// a checked call: the kernel's arguments with offsets into the packed copy where horizon_bind puts device addresses
+struct HorizonPlan {
+    HorizonArgs a;
+    size_t o_g, o_pairs;                          // behind the theta front: the gamma front, the pairs
+    bool has_len;
+};
+}  // namespace
+
+// the checks both entries share; then everything the kernel reads from host arrays packed for one copy
+static int horizon_args(rovmpc_handle *h, const char *entry, const int32_t *code_t, const int32_t *code_off_t, const double *consts_t,
+                        const int32_t *const_off_t, int32_t Rt, const int32_t *code_g, const int32_t *code_off_g, const double *consts_g,
+                        const int32_t *const_off_g, int32_t Rg, const int32_t *pairs, int32_t Q, const void *X, int32_t F,
+                        const double *mean, const double *scale, const void *time, const int64_t *len, int64_t T, int64_t B,
+                        const void *theta, const void *gamma, const rovmpc_horizon_params *params, const void *skill,
+                        std::vector<unsigned char> &blob, HorizonPlan &plan) {
+    if (!code_t || !code_off_t || !const_off_t || !code_g || !code_off_g || !const_off_g || !pairs || !X || !mean || !scale || !time ||
+        !theta || !gamma || !skill)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (a front's code, code_off or const_off, pairs, X, mean, scale, time, theta, gamma or skill)", entry);
+    if (Q < 1 || B < 1 || T < 1 || Rt < 1 || Rg < 1)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: Q, B, T, Rt and Rg must be >= 1 (got %d, %lld, %lld, %d, %d)", entry, Q, (long long)B, (long long)T, Rt, Rg);
+    if ((int64_t)Q * B > ((int64_t)1 << 24)) FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 (pair, recording) problems in one call (got %d x %lld)", entry, Q, (long long)B);
+    if (F < 1 || F > ROVMPC_MAX_FEATURES) FAIL(h, ROVMPC_ERR_INVALID, "%s: F must be in 1..%d (got %d)", entry, ROVMPC_MAX_FEATURES, F);
+    rovmpc_horizon_params p;
+    rovmpc_default_horizon_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(rovmpc_horizon_params))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: rovmpc_horizon_params.struct_size %d != %d (ABI mismatch)", entry, params->struct_size, (int)sizeof(rovmpc_horizon_params));
+        p = *params;
+    }
+    if (p.H < 1 || p.stride < 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: H and stride must be >= 1 (got %d, %d)", entry, p.H, p.stride);
+    if (p.integrator != ROVMPC_RK4 && p.integrator != ROVMPC_EULER)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: integrator must be ROVMPC_RK4 or ROVMPC_EULER (got %d; the second-order maps are not provided)", entry, p.integrator);
+    if (p.prev_mode != ROVMPC_PREV_INTERP && p.prev_mode != ROVMPC_PREV_HOLD) FAIL(h, ROVMPC_ERR_INVALID, "%s: unknown prev_mode %d", entry, p.prev_mode);
+    for (int q = 0; q < Q; ++q)
+        if (pairs[2 * q] < 0 || pairs[2 * q] >= Rt || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= Rg)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: pair %d = (%d, %d) is outside the fronts (%d theta rows, %d gamma rows)", entry, q, pairs[2 * q], pairs[2 * q + 1], Rt, Rg);
+    static const char *const names[HZ_SLOTS] = {"slot_theta", "slot_gamma", "slot_theta_prev", "slot_gamma_prev", "slot_cos_theta", "slot_sin_gamma"};
+    const int32_t slots[HZ_SLOTS] = {p.slot_theta, p.slot_gamma, p.slot_theta_prev, p.slot_gamma_prev, p.slot_cos_theta, p.slot_sin_gamma};
+    if (p.slot_theta == -1 || p.slot_gamma == -1) FAIL(h, ROVMPC_ERR_INVALID, "%s: slot_theta and slot_gamma are required (got %d, %d)", entry, p.slot_theta, p.slot_gamma);
+    for (int k = 0; k < HZ_SLOTS; ++k) {
+        if (slots[k] == -1) continue;
+        if (slots[k] < 0 || slots[k] >= F) FAIL(h, ROVMPC_ERR_INVALID, "%s: %s = %d is outside 0..%d", entry, names[k], slots[k], F - 1);
+        for (int m = 0; m < k; ++m)
+            if (slots[m] == slots[k]) FAIL(h, ROVMPC_ERR_INVALID, "%s: %s and %s both name slot %d", entry, names[m], names[k], slots[k]);
+        if (scale[slots[k]] == 0.0 || !std::isfinite(scale[slots[k]]) || !std::isfinite(mean[slots[k]]))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: mean and scale of %s (slot %d) must be finite, the scale not 0 (got %g, %g)", entry, names[k], slots[k],
+                 mean[slots[k]], scale[slots[k]]);
+    }
+    if (int rc = check_front(h, entry, "theta", code_t, code_off_t, consts_t, const_off_t, Rt, F)) return rc;
+    if (int rc = check_front(h, entry, "gamma", code_g, code_off_g, consts_g, const_off_g, Rg, F)) return rc;
+    if (int rc = check_lengths(h, entry, len, T, B)) return rc;
+    HorizonArgs &a = plan.a;
+    memset(&a, 0, sizeof(a));
+    std::vector<unsigned char> blob_g;
+    pack_programs(code_t, code_off_t, consts_t, const_off_t, Rt, F, len, T, B, blob, a.t);
+    pack_programs(code_g, code_off_g, consts_g, const_off_g, Rg, F, nullptr, T, B, blob_g, a.g);
+    plan.o_g = (blob.size() + 7) & ~(size_t)7;
+    plan.o_pairs = plan.o_g + ((blob_g.size() + 7) & ~(size_t)7);
+    blob.resize(plan.o_pairs + (size_t)Q * 2 * sizeof(int32_t), 0);
+    memcpy(blob.data() + plan.o_g, blob_g.data(), blob_g.size());
+    memcpy(blob.data() + plan.o_pairs, pairs, (size_t)Q * 2 * sizeof(int32_t));
+    plan.has_len = len != nullptr;
+    a.H = p.H; a.stride = p.stride; a.integrator = p.integrator; a.prev_mode = p.prev_mode;
+    a.W = horizon_windows(T, p.H, p.stride);
+    for (int k = 0; k < HZ_SLOTS; ++k) {
+        a.slot[k] = slots[k];
+        a.mean[k] = slots[k] >= 0 ? mean[slots[k]] : 0.0;
+        a.scale[k] = slots[k] >= 0 ? scale[slots[k]] : 1.0;
+    }
+    return ROVMPC_OK;
+}
+
+static void horizon_bind(HorizonPlan &plan, const unsigned char *d_blob) {
+    score_bind(plan.a.t, d_blob, plan.has_len);
+    score_bind(plan.a.g, d_blob + plan.o_g, false);
+    plan.a.pairs = (const int32_t *)(d_blob + plan.o_pairs);
+}
+
+static void launch_horizon(rovmpc_handle *h, int32_t Q, const HorizonArgs &a) {
+    hipLaunchKernelGGL(score_pairs_kernel, dim3((unsigned)((int64_t)Q * a.t.B)), dim3(HORIZON_NT), horizon_lds_bytes(a.t.F), h->stream, a);
+}
+
+extern "C" int rovmpc_score_pairs(rovmpc_handle *h, const int32_t *code_t, const int32_t *code_off_t, const double *consts_t,
+                                  const int32_t *const_off_t, int32_t Rt, const int32_t *code_g, const int32_t *code_off_g,
+                                  const double *consts_g, const int32_t *const_off_g, int32_t Rg, const int32_t *pairs, int32_t Q,
+                                  const double *X, int32_t F, const double *mean, const double *scale, const double *time,
+                                  const int64_t *len, int64_t T, int64_t B, const double *theta, const double *gamma,
+                                  const rovmpc_horizon_params *params, double *skill, double *pred) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    HorizonPlan plan;
+    if (int rc = horizon_args(h, "rovmpc_score_pairs", code_t, code_off_t, consts_t, const_off_t, Rt, code_g, code_off_g, consts_g, const_off_g,
+                              Rg, pairs, Q, X, F, mean, scale, time, len, T, B, theta, gamma, params, skill, blob, plan))
+        return rc;
+    HelperCall c(h);
+    HorizonArgs &a = plan.a;
+    const size_t n = (size_t)B * T, problems = (size_t)Q * B, n_pred = problems * (size_t)a.W * a.H * 2;
+    const auto dP = c.upload((const unsigned char *)blob.data(), blob.size());
+    const auto dX = c.upload(X, n * F);
+    const auto dT = c.upload(time, n);
+    const auto dA = c.upload(theta, n);
+    const auto dG = c.upload(gamma, n);
+    const auto dS = c.buffer<double>(problems * a.H * ROVMPC_HORIZON_COLS);
+    const auto dR = pred && n_pred ? c.buffer<double>(n_pred) : DevArray<double>{nullptr, 0};
+    horizon_bind(plan, dP.p);
+    a.t.X = dX.p; a.t.time = dT.p; a.theta = dA.p; a.gamma = dG.p; a.skill = dS.p; a.pred = dR.p;
+    if (c.ok()) launch_horizon(h, Q, a);
+    c.download(skill, dS);
+    if (dR.p) c.download(pred, dR);
+    return c.finish();
+}
+
+extern "C" int rovmpc_score_pairs_device(rovmpc_handle *h, const int32_t *code_t, const int32_t *code_off_t, const double *consts_t,
+                                         const int32_t *const_off_t, int32_t Rt, const int32_t *code_g, const int32_t *code_off_g,
+                                         const double *consts_g, const int32_t *const_off_g, int32_t Rg, const int32_t *pairs, int32_t Q,
+                                         const double *d_X, int32_t F, const double *mean, const double *scale, const double *d_time,
+                                         const int64_t *len, int64_t T, int64_t B, const double *d_theta, const double *d_gamma,
+                                         const rovmpc_horizon_params *params, double *d_skill, double *d_pred) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    HorizonPlan plan;
+    if (int rc = horizon_args(h, "rovmpc_score_pairs_device", code_t, code_off_t, consts_t, const_off_t, Rt, code_g, code_off_g, consts_g,
+                              const_off_g, Rg, pairs, Q, d_X, F, mean, scale, d_time, len, T, B, d_theta, d_gamma, params, d_skill, blob, plan))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = stage_programs(h, blob)) return rc;
+    HorizonArgs &a = plan.a;
+    horizon_bind(plan, (const unsigned char *)h->d_score_prog);
+    a.t.X = d_X; a.t.time = d_time; a.theta = d_theta; a.gamma = d_gamma; a.skill = d_skill; a.pred = a.W > 0 ? d_pred : nullptr;
+    launch_horizon(h, Q, a);
+    return launched(h, "pair scoring");
 }

@@ -1040,6 +1040,46 @@ class Engine:
         torch.cuda.synchronize(dev)                     # (the device: the refit runs on the handle's own stream)
         return dK.cpu().numpy().reshape(-1)[:G * NK].reshape(G, NK), dO.cpu().numpy()
 
+    def score_pairs(self, theta_programs, gamma_programs, pairs, X, time, theta, gamma, mean, scale, params, lengths=None,
+                    return_pred: bool = False, device: bool = False):
+        """Q (theta row, gamma row) pairs rolled ``params.H`` steps on their own predictions from every start row of B
+        recordings (rovmpc_score_pairs; law in include/rovmpc.h).  The two fronts as ``programs`` of ``score_rows``; pairs
+        int32 (Q, 2); X (B, T, F) scaled rows, time, theta, gamma (B, T), mean and scale (F,), params a HorizonParams, lengths
+        (B,) or None, checked and laid out by ``scoring.score_pairs``.  Returns (skill (Q, B, H, 9), pred (Q, B, W, H, 2) or
+        None).  ``device=True`` goes through rovmpc_score_pairs_device on torch buffers: the same bits."""
+        def front(programs):
+            code_off, const_off = [0], [0]
+            for code, consts in programs:
+                code_off.append(code_off[-1] + len(code)); const_off.append(const_off[-1] + len(consts))
+            code = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in programs]), np.int32)
+            consts = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float64).reshape(-1) for _, k in programs] + [np.zeros(1)]))
+            return code, np.asarray(code_off, np.int32), consts, np.asarray(const_off, np.int32), len(programs)
+        ct, cot, kt, kot, Rt = front(theta_programs)
+        cg, cog, kg, kog, Rg = front(gamma_programs)
+        pairs = np.ascontiguousarray(pairs, np.int32)
+        mean, scale = np.ascontiguousarray(mean, np.float64), np.ascontiguousarray(scale, np.float64)
+        Q, (B, T, F), H = len(pairs), X.shape, int(params.H)
+        W = (T - 1 - H) // int(params.stride) + 1 if T - 1 - H >= 0 else 0
+        lens = None if lengths is None else np.ascontiguousarray(lengths, np.int64)
+        head = (self._h, _ptr(ct), _ptr(cot), _ptr(kt), _ptr(kot), Rt, _ptr(cg), _ptr(cog), _ptr(kg), _ptr(kog), Rg, _ptr(pairs), Q)
+        if not device:
+            skill = np.empty((Q, B, H, _lib.HORIZON_COLS))
+            pred = np.empty((Q, B, W, H, 2)) if return_pred else None
+            self._check(self.lib.rovmpc_score_pairs(*head, _ptr(X), F, _ptr(mean), _ptr(scale), _ptr(time), _ptr(lens), T, B, _ptr(theta),
+                                                    _ptr(gamma), C.byref(params), _ptr(skill), _ptr(pred) if W else None))
+            return skill, pred
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        dX, dT, dA, dG = (torch.tensor(x, device=dev) for x in (X, time, theta, gamma))
+        dS = torch.empty((Q, B, H, _lib.HORIZON_COLS), dtype=torch.float64, device=dev)
+        dP = torch.empty((Q, B, W, H, 2), dtype=torch.float64, device=dev) if return_pred else None
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_score_pairs_device(*head, dX.data_ptr(), F, _ptr(mean), _ptr(scale), dT.data_ptr(), _ptr(lens), T, B,
+                                                       dA.data_ptr(), dG.data_ptr(), C.byref(params), dS.data_ptr(),
+                                                       dP.data_ptr() if return_pred and W else None))
+        torch.cuda.synchronize(dev)                     # (the device: the scoring runs on the handle's own stream)
+        return dS.cpu().numpy(), None if dP is None else dP.cpu().numpy()
+
 
 _default_engine: Optional[Engine] = None
 

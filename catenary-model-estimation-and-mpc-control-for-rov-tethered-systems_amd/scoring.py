@@ -14,6 +14,13 @@ The rows carry the constants PySR found on the reference's cable.  ``refit_rows`
 launch), and ``select_model(..., refit=True)`` scores and loads the refitted rows.
 
     fit = refit_rows(rows, X, target)                           # fit.expressions[r][0], fit.loss, fit.status, ... (R, G)
+
+Those scores are open loop: a row is integrated along measured feature rows and never reads its own prediction.  ``score_pairs``
+rolls a theta row and a gamma row together on their own predictions, as the controller does, from every start row of a
+recording for ``horizon`` steps (rovmpc_score_pairs), and ``select_model(..., horizon=H)`` picks the pair to load by that.
+
+    sk = score_pairs(theta_rows, gamma_rows, X, time, theta, gamma, mean, scale, horizon=20)   # sk.skill_theta, ... (Q, B, H)
+    it, ig = sk.pairs[sk.best()]
 """
 from __future__ import annotations
 
@@ -268,6 +275,183 @@ def refit_rows(rows, X, target, lengths=None, groups="pooled", free=None, max_it
     return RowRefit(per_row, expressions, col(0), col(1), col(2), col(3, np.int64), col(4, np.int64), col(5, np.int64))
 
 
+PREV_MODES = {"interp": _lib.PREV_INTERP, "hold": _lib.PREV_HOLD}
+# metric -> whether larger is better ("skill": the mean of skill_theta and skill_gamma)
+PAIR_METRICS = {"skill": True, "skill_theta": True, "skill_gamma": True, "coverage": True, "n_ok": True, "rmse_theta": False,
+                "rmse_gamma": False, "max_abs_theta": False, "max_abs_gamma": False, "ss_theta": False, "ss_gamma": False}
+
+
+@dataclass
+class PairSkill:
+    """What rovmpc_score_pairs returns for Q pairs on B recordings over H horizon steps.  ``pairs`` (Q, 2): theta row, gamma
+    row; ``expressions[q]``: the pair's two texts; the nine columns each (Q, B, H); ``windows`` (B,): the windows W_b of each
+    recording; ``pred`` (Q, B, W, H, 2) where it was asked for."""
+    pairs: np.ndarray
+    expressions: Sequence
+    rmse_theta: np.ndarray
+    rmse_gamma: np.ndarray
+    max_abs_theta: np.ndarray
+    max_abs_gamma: np.ndarray
+    n_ok: np.ndarray
+    ss_theta: np.ndarray
+    ss_gamma: np.ndarray
+    ss_hold_theta: np.ndarray
+    ss_hold_gamma: np.ndarray
+    windows: np.ndarray
+    pred: Optional[np.ndarray] = None
+
+    @classmethod
+    def from_table(cls, table, pairs, expressions, windows, pred=None) -> "PairSkill":
+        table = np.asarray(table, dtype=np.float64)
+        if table.ndim != 4 or table.shape[3] != _lib.HORIZON_COLS:
+            raise ValueError(f"skill must be (Q, B, H, {_lib.HORIZON_COLS}) (got {table.shape})")
+        cols = [np.ascontiguousarray(table[..., k]) for k in range(_lib.HORIZON_COLS)]
+        cols[4] = cols[4].astype(np.int64)
+        return cls(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), tuple(expressions), *cols,
+                   windows=np.asarray(windows, dtype=np.int64), pred=pred)
+
+    def table(self) -> np.ndarray:
+        return np.stack([np.asarray(getattr(self, n), dtype=np.float64) for n in _lib.HORIZON_NAMES], axis=-1)
+
+    @staticmethod
+    def _skill(ss, hold, n_ok):
+        with np.errstate(all="ignore"):
+            return np.where((hold == 0) | (n_ok == 0), np.nan, 1.0 - ss / hold)
+
+    @property
+    def skill_theta(self) -> np.ndarray:
+        """1 - ss_theta / ss_hold_theta: 1 is perfect, 0 the persistence forecast; NaN where ss_hold = 0 or n_ok = 0."""
+        return self._skill(self.ss_theta, self.ss_hold_theta, self.n_ok)
+
+    @property
+    def skill_gamma(self) -> np.ndarray:
+        return self._skill(self.ss_gamma, self.ss_hold_gamma, self.n_ok)
+
+    @property
+    def skill(self) -> np.ndarray:
+        return (self.skill_theta + self.skill_gamma) / 2
+
+    @property
+    def coverage(self) -> np.ndarray:
+        """n_ok / W_b, the share of a recording's windows that were counted (NaN where it has none)."""
+        with np.errstate(all="ignore"):
+            return self.n_ok / np.where(self.windows > 0, self.windows, np.nan)[None, :, None]
+
+    def rank(self, metric: str = "skill", at: Optional[int] = None, reduce: str = "mean") -> np.ndarray:
+        """Pair indices, best first: the metric at horizon step ``at`` (1 .. H; default H, the last) reduced over the
+        recordings (a NaN on any recording makes the pair's value NaN), NaN pairs last, ties to the lower index."""
+        if metric not in PAIR_METRICS:
+            raise ValueError(f"metric must be one of {sorted(PAIR_METRICS)} (got {metric!r})")
+        if reduce not in REDUCERS:
+            raise ValueError(f"reduce must be one of {REDUCERS} (got {reduce!r})")
+        H = self.n_ok.shape[2]
+        at = H if at is None else at
+        if isinstance(at, bool) or int(at) != at or not 1 <= int(at) <= H:
+            raise ValueError(f"at must be a horizon step in 1..{H} (got {at!r})")
+        v = np.asarray(getattr(self, metric), dtype=np.float64)[:, :, int(at) - 1]
+        with np.errstate(all="ignore"):
+            v = getattr(np, reduce)(v, axis=1)
+        key = -v if PAIR_METRICS[metric] else v
+        key = np.where(np.isnan(key), np.inf, key)
+        return np.lexsort((np.arange(len(v)), key, np.isnan(v))).astype(np.int64)
+
+    def best(self, metric: str = "skill", at: Optional[int] = None, reduce: str = "mean") -> int:
+        return int(self.rank(metric, at, reduce)[0])
+
+
+def _pair_list(pairs, Rt: int, Rg: int) -> np.ndarray:
+    if isinstance(pairs, str):
+        if pairs == "product":
+            return np.stack(np.meshgrid(np.arange(Rt), np.arange(Rg), indexing="ij"), axis=-1).reshape(-1, 2).astype(np.int32)
+        if pairs == "zip":
+            if Rt != Rg:
+                raise ValueError(f"pairs='zip' needs as many theta rows as gamma rows (got {Rt}, {Rg})")
+            return np.stack([np.arange(Rt), np.arange(Rt)], axis=-1).astype(np.int32)
+        raise ValueError(f"pairs must be 'product', 'zip' or a list of (theta row, gamma row) (got {pairs!r})")
+    try:
+        arr = np.asarray(pairs)
+    except Exception:
+        arr = None
+    if arr is None or arr.ndim != 2 or arr.shape[1] != 2 or len(arr) < 1 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"pairs must be 'product', 'zip' or a non-empty list of integer (theta row, gamma row) (got {pairs!r})")
+    if (arr < 0).any() or (arr[:, 0] >= Rt).any() or (arr[:, 1] >= Rg).any():
+        raise ValueError(f"a pair is outside the fronts ({Rt} theta rows, {Rg} gamma rows)")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def score_pairs(theta_rows, gamma_rows, X, time, theta, gamma, mean, scale, horizon, stride: int = 1, pairs="product",
+                integrator="rk4", prev_mode="interp", feature_map="gen1", lengths=None, variable_names=None,
+                return_pred: bool = False, engine=None, device: bool = False) -> PairSkill:
+    """Closed-loop N-step-ahead skill of (theta row, gamma row) pairs on recordings (rovmpc_score_pairs; law in
+    include/rovmpc.h).  From every ``stride``-th row of a recording the pair is rolled ``horizon`` steps on its own
+    predictions -- its (theta, gamma) written into the state slots of every RK4 stage row, the other slots taken from the
+    recording -- and the error after 1 .. horizon steps is reduced over the windows, beside that of the persistence forecast.
+    X (T, F) or (B, T, F): already-scaled feature rows; time, theta, gamma (T,) or (B, T): theta and gamma measured and
+    UNSCALED; mean, scale (F,): the scaler (read at the state slots).  ``pairs``: "product" (every theta row with every gamma
+    row, theta-major), "zip" or a list of (theta row, gamma row); ``feature_map``: "gen1" (slots 14, 15 and the delay slots
+    16, 17), "gen2" (12, 13 and cos theta, sin gamma at 14, 15) or a dict {"theta", "gamma", "theta_prev", "gamma_prev",
+    "cos_theta", "sin_gamma"} -> slot; ``integrator``: "rk4" or "euler"; ``prev_mode``: "interp" or "hold".  One launch."""
+    if isinstance(integrator, str):
+        if integrator not in ("rk4", "euler"):
+            raise ValueError(f"integrator must be 'rk4' or 'euler' (got {integrator!r}; the second-order maps are not provided)")
+        integrator = INTEGRATORS[integrator]
+    if isinstance(prev_mode, str):
+        if prev_mode not in PREV_MODES:
+            raise ValueError(f"prev_mode must be one of {sorted(PREV_MODES)} (got {prev_mode!r})")
+        prev_mode = PREV_MODES[prev_mode]
+    if isinstance(feature_map, str):
+        if feature_map not in _lib.FEATURE_MAPS:
+            raise ValueError(f"feature_map must be one of {sorted(_lib.FEATURE_MAPS)} or a dict of slots (got {feature_map!r})")
+        slots = _lib.FEATURE_MAPS[feature_map]
+    elif isinstance(feature_map, dict):
+        unknown = set(feature_map) - set(_lib.HORIZON_SLOTS)
+        if unknown:
+            raise ValueError(f"feature_map names {sorted(unknown)}; the slots are {_lib.HORIZON_SLOTS}")
+        slots = tuple(-1 if feature_map.get(n) is None else feature_map[n] for n in _lib.HORIZON_SLOTS)
+    else:
+        raise ValueError(f"feature_map must be one of {sorted(_lib.FEATURE_MAPS)} or a dict of slots (got {feature_map!r})")
+    fronts = []
+    for name, rows in (("theta_rows", theta_rows), ("gamma_rows", gamma_rows)):
+        if isinstance(rows, (str, dict)):
+            raise ValueError(f"{name} must be a sequence of rows, not a single row")
+        texts = [row_text(r) for r in rows]
+        if not texts:
+            raise ValueError(f"{name} is empty")
+        fronts.append(texts)
+    X, time, theta, gamma, lengths, _, _ = _recordings(X, time, theta, gamma, lengths, None, names=("time", "theta"))
+    if gamma is None:
+        raise ValueError("gamma is required")
+    B, T, F = X.shape
+    params = _lib.HorizonParams.make(horizon, stride, integrator, prev_mode, slots, F)
+    mean, scale = np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(scale, dtype=np.float64)
+    if mean.shape != (F,) or scale.shape != (F,):
+        raise ValueError(f"mean and scale must be (F,) = ({F},) (got {mean.shape}, {scale.shape})")
+    used = [v for v in params.slots() if v >= 0]
+    if not np.isfinite(mean[used]).all() or not np.isfinite(scale[used]).all() or (scale[used] == 0).any():
+        raise ValueError("mean and scale must be finite, the scale not 0, at the state slots")
+    pair_arr = _pair_list(pairs, len(fronts[0]), len(fronts[1]))
+    if len(pair_arr) * B > 1 << 24:
+        raise ValueError(f"more than 2^24 (pair, recording) problems in one call (got {len(pair_arr)} x {B})")
+    programs = []
+    for texts in fronts:
+        progs = []
+        for text in texts:
+            consts: list = []
+            prog = compile_expression(text, consts, F, variable_names)
+            progs.append((prog.code, consts))
+        programs.append(progs)
+    if engine is None:
+        from .engine import default_engine
+        engine = default_engine()
+    table, pred = engine.score_pairs(programs[0], programs[1], pair_arr, X, time, theta, gamma, mean, scale, params, lengths,
+                                     return_pred, device)
+    n = np.full(B, T, dtype=np.int64) if lengths is None else lengths
+    H, stride = int(params.H), int(params.stride)
+    windows = np.where(n - 1 - H >= 0, (n - 1 - H) // stride + 1, 0)
+    expressions = [(fronts[0][it], fronts[1][ig]) for it, ig in pair_arr]
+    return PairSkill.from_table(table, pair_arr, expressions, windows, pred)
+
+
 def _derivative_target(series, time, lengths):
     """np.gradient(series, time) per recording over its counted rows (simply.py's target); 0 beyond them."""
     series, time = np.asarray(series, dtype=np.float64), np.asarray(time, dtype=np.float64)
@@ -284,12 +468,19 @@ def _derivative_target(series, time, lengths):
 
 
 def select_model(theta_rows, gamma_rows, X_raw, time, theta, gamma, mean, scale, integrator="rk4", metric: str = "r2",
-                 reduce: str = "mean", lengths=None, variable_names=None, engine=None, refit: bool = False):
+                 reduce: str = "mean", lengths=None, variable_names=None, engine=None, refit: bool = False, horizon=None,
+                 stride: int = 1, shortlist: int = 4):
     """Score both Pareto fronts on the recordings and return (the DynamicsModel of the two best rows, theta scores, gamma
     scores).  ``X_raw`` (T, F) or (B, T, F) are unscaled feature rows; they are scaled as the scaler does, (X - mean) / scale,
     before the rows read them.  ``theta`` / ``gamma``: the measured series the replays are held against.  ``refit=True``:
     the constants of both fronts are first refitted (``refit_rows``, all recordings pooled) to np.gradient(series, time), the
-    reference's target (simply.py); the rewritten rows are scored -- with that target, so ``loss`` is theirs -- and loaded."""
+    reference's target (simply.py); the rewritten rows are scored -- with that target, so ``loss`` is theirs -- and loaded.
+    ``horizon=H``: the open-loop ranking only shortlists.  The ``shortlist`` best rows of each front (refitted first with
+    ``refit=True``) form shortlist^2 pairs, ``score_pairs`` rolls every pair H steps on its own predictions from every
+    ``stride``-th row (generation-1 slots; "rk4" or "euler"), the pair with the best closed-loop skill at step H is loaded,
+    and the PairSkill -- its ``pairs`` index the fronts' rows -- is returned as a fourth value."""
+    if horizon is not None and (isinstance(shortlist, bool) or int(shortlist) != shortlist or int(shortlist) < 1):
+        raise ValueError(f"shortlist must be an integer >= 1 (got {shortlist!r})")
     mean = np.asarray(mean, dtype=np.float64); scale = np.asarray(scale, dtype=np.float64)
     X_raw = np.asarray(X_raw, dtype=np.float64)
     if mean.ndim != 1 or mean.shape != scale.shape or X_raw.ndim not in (2, 3) or X_raw.shape[-1] != mean.shape[0]:
@@ -306,6 +497,15 @@ def select_model(theta_rows, gamma_rows, X_raw, time, theta, gamma, mean, scale,
     else:
         s_theta = score_rows(theta_rows, Xs, time, theta, **kw)
         s_gamma = score_rows(gamma_rows, Xs, time, gamma, **kw)
-    model = DynamicsModel(mean, scale, s_theta.expressions[s_theta.best(metric, reduce)],
-                          s_gamma.expressions[s_gamma.best(metric, reduce)], variable_names=variable_names)
-    return model, s_theta, s_gamma
+    if horizon is None:
+        model = DynamicsModel(mean, scale, s_theta.expressions[s_theta.best(metric, reduce)],
+                              s_gamma.expressions[s_gamma.best(metric, reduce)], variable_names=variable_names)
+        return model, s_theta, s_gamma
+    top_t, top_g = s_theta.rank(metric, reduce)[:int(shortlist)], s_gamma.rank(metric, reduce)[:int(shortlist)]
+    skill = score_pairs([s_theta.expressions[r] for r in top_t], [s_gamma.expressions[r] for r in top_g], Xs, time, theta, gamma,
+                        mean, scale, horizon, stride=stride, integrator=integrator, lengths=lengths, variable_names=variable_names,
+                        engine=engine)
+    skill.pairs = np.stack([top_t[skill.pairs[:, 0]], top_g[skill.pairs[:, 1]]], axis=-1)      # rows of the fronts, not of the shortlists
+    it, ig = skill.pairs[skill.best(reduce=reduce)]
+    model = DynamicsModel(mean, scale, s_theta.expressions[it], s_gamma.expressions[ig], variable_names=variable_names)
+    return model, s_theta, s_gamma, skill

@@ -917,9 +917,9 @@ int rovmpc_replay(rovmpc_handle *h, const double *Xs, const double *time, int64_
  * (code, code_off, consts when any row has constants, const_off, X, time, truth, scores), R < 1, B < 1, T < 1, R B > 2^24,
  * F outside 1 .. ROVMPC_MAX_FEATURES, an integrator that is none of the four, offsets that do not start at 0 or decrease,
  * len[b] outside 1 .. T, a row that fails validation (its index is in the message).
- * Not provided: the N-step-ahead skill of a row pair fed its own predictions (the rollout's law), the double cumulative_trapezoid
- * without offset of dd_test_cluster.py:217-219 (no counterpart in rovmpc_replay), fp32.  Refitting the constants of the rows
- * is rovmpc_refit_rows, below. */
+ * Not provided: the double cumulative_trapezoid without offset of dd_test_cluster.py:217-219 (no counterpart in rovmpc_replay),
+ * fp32.  Refitting the constants of the rows is rovmpc_refit_rows, below; the N-step-ahead skill of a row pair fed its own
+ * predictions (the rollout's law) is rovmpc_score_pairs, below that. */
 #define ROVMPC_SCORE_COLS 8
 #define ROVMPC_SCORE_TILE 128
 /* Host pointers.  Uploads, one launch, one synchronise. */
@@ -1010,6 +1010,88 @@ int rovmpc_refit_rows_device(rovmpc_handle *h, const int32_t *code, const int32_
                              const int32_t *const_off, const uint8_t *free, int32_t R, const double *d_X, int32_t F,
                              const int64_t *len, int64_t T, int64_t B, const double *d_target, const int32_t *group_off,
                              int32_t G, const rovmpc_refit_params *params, double *d_consts_out, double *d_out);
+
+/* ---- score (theta, gamma) row pairs by closed-loop N-step-ahead skill on recordings ----------------------------------------
+ * rovmpc_score_rows is open loop: a row is integrated along measured feature rows, never reads its own prediction, and the
+ * theta row and the gamma row never meet.  The controller rolls a theta row and a gamma row TOGETHER for N steps with the
+ * pair's own (theta, gamma) written back into the state slots at every RK4 stage.  This entry scores that, for Q pairs on B
+ * recordings in one launch: from every start row of a recording the pair is rolled H steps on its own predictions, the
+ * exogenous slots taken from the recording, and the error after 1 .. H steps is reduced per horizon step on the device.
+ * Two fronts of programs, laid out as in rovmpc_score_rows: Rt theta rows (code_t, code_off_t, consts_t, const_off_t) and Rg
+ * gamma rows (code_g, ...); pair q is theta row pairs[q][0] with gamma row pairs[q][1] (int32 [Q][2]).
+ * Law (fp64 only).
+ *   recording  b has n = len[b] counted rows (len NULL: n = T) of X[b][T][F], scaled rows; time[b][T]; theta[b][T] and
+ *          gamma[b][T], measured and UNSCALED.  The named slots of X (params->slot_*) are never read.
+ *   windows    start at s_w = w stride for w = 0 .. W_b - 1 while s_w + H <= n - 1.  pred is sized by W = that count for
+ *          n = T; entries of pred that belong to no window are NaN.
+ *   state      of window w at node i = s_w: (th, ga) = (theta[s], gamma[s]); the previous node (thm, gam) =
+ *          (theta[max(s - 1, 0)], gamma[max(s - 1, 0)]).
+ *   step       j = 1 .. H goes from row i - 1 to row i = s + j with dt = time[i] - time[i - 1].
+ *   stage row  a stage at c in {0, 1/2, 1} with stage state (yth, yga) builds one row x of F values:
+ *          every unnamed slot f: c = 0: X[i-1][f];  c = 1/2: (X[i-1][f] + X[i][f]) / 2;  c = 1: X[i][f]
+ *          slot_theta <- (yth - mean) / scale, slot_gamma <- (yga - mean) / scale  (mean, scale of that slot; IEEE division)
+ *          slot_cos_theta <- (cos yth - mean) / scale, slot_sin_gamma <- (sin yga - mean) / scale, the library's own m_cos / m_sin
+ *          slot_theta_prev, with a = (thm - mean) / scale and b = (th - mean) / scale, th the state of node i - 1 (mean, scale
+ *          of the prev slot): a when prev_mode is ROVMPC_PREV_HOLD or c = 0; b when c = 1; (a + b) / 2 when c = 1/2.
+ *          slot_gamma_prev likewise from gam, ga.
+ *          (stage() of the oracle's rollout_scalar with the exogenous slots taken from the recording.)  Both rows of the
+ *          pair are evaluated on x by the interpreter of rovmpc_eval_expression, bit for bit: k = (f_theta(x), f_gamma(x)).
+ *   integrator RK4: k1 at (y, 0), k2 at (y + (dt / 2) k1, 1/2), k3 at (y + (dt / 2) k2, 1/2), k4 at (y + dt k3, 1);
+ *          y <- y + (dt / 6) (((k1 + 2 k2) + 2 k3) + k4).  Euler: y <- y + k1 dt.  No contraction: each product is rounded,
+ *          then the sum.  After the step (thm, gam) <- the old (th, ga).
+ *   ties       for a pair whose rows read no named slot k3 = k2 and the update is that of rovmpc_replay: the prediction of
+ *          the single window s = 0, H = n - 1 is bit for bit what rovmpc_replay returns for the two expressions from
+ *          (theta[0], gamma[0]), for RK4 and for Euler.
+ *   pred[q][b][w][j - 1][2] = (th, ga) after step j of window w (optional).
+ *   skill[q][b][j - 1][ROVMPC_HORIZON_COLS] for horizon step j, e = prediction - truth at row s_w + j:
+ *          0 rmse_theta   1 rmse_gamma   2 max_abs_theta   3 max_abs_gamma   4 n_ok   5 ss_theta = sum e_theta^2   6 ss_gamma
+ *          7 ss_hold_theta = sum (theta[s_w] - theta[s_w + j])^2 over the same counted windows (the persistence forecast)
+ *          8 ss_hold_gamma
+ *   counting   a window is counted at step j if and only if both its predictions are finite at every step 1 .. j and both
+ *          truths at s_w + j are finite.  rmse = sqrt(ss / n_ok).  n_ok = 0 (also W_b = 0): columns 0-3 and 5-8 are NaN.
+ *   summation order  per (q, b, j): windows in tiles of ROVMPC_HORIZON_TILE consecutive w, an uncounted window contributes
+ *          +0; inside a tile the tree v[l] += v[l + s] for s = 64, 32, ..., 1; the tile sums added in increasing tile order
+ *          from +0.  Squares, differences and sums are rounded one by one.
+ *          So skill[q][b] is a function of the two rows, the n rows of recording b and params alone: not of Q, Rt, Rg, B, T,
+ *          the place of the pair or the recording in the call, or the entry.
+ *   One workgroup of ROVMPC_HORIZON_TILE lanes per (pair, recording) walks its tiles; the lane is the window.
+ * ROVMPC_ERR_INVALID with a message, before anything is launched and with nothing written: a null handle or required pointer
+ * (the two fronts' code, code_off, const_off, consts where the front has constants; pairs, X, mean, scale, time, theta,
+ * gamma, skill); Q, B, T, Rt or Rg < 1; Q B > 2^24; F outside 1 .. ROVMPC_MAX_FEATURES; H < 1 or stride < 1; an integrator other
+ * than ROVMPC_RK4 or ROVMPC_EULER; a prev_mode that is none of ROVMPC_PREV_*; a pair index out of range; slot_theta or
+ * slot_gamma absent (-1); a named slot outside 0 .. F - 1, or two names on one slot; scale = 0 or not finite, or a mean not
+ * finite, at a named slot; offsets that do not start at 0 or decrease; len[b] outside 1 .. T; a row that fails the
+ * validation of rovmpc_eval_expression (the message names the front and the index); a struct_size mismatch.
+ * Not provided: the second-order maps (ROVMPC_DOUBLE_EULER, ROVMPC_TRAPEZOID and the generation-3 state), fp32, costs. */
+#define ROVMPC_HORIZON_COLS 9
+#define ROVMPC_HORIZON_TILE 128
+typedef struct rovmpc_horizon_params {
+    int32_t struct_size;             /* = sizeof(rovmpc_horizon_params), ABI check                       */
+    int32_t integrator;              /* ROVMPC_RK4 | ROVMPC_EULER                                        */
+    int32_t prev_mode;               /* ROVMPC_PREV_*                                                    */
+    int32_t H;                       /* horizon steps, >= 1; default 20                                  */
+    int32_t stride;                  /* rows between window starts, >= 1; default 1                      */
+    int32_t slot_theta, slot_gamma, slot_theta_prev, slot_gamma_prev, slot_cos_theta, slot_sin_gamma;   /* -1: the map has none */
+} rovmpc_horizon_params;
+/* The generation-1 map: slots 14, 15, 16, 17, -1, -1; ROVMPC_RK4; ROVMPC_PREV_INTERP; H 20; stride 1. */
+void rovmpc_default_horizon_params(rovmpc_horizon_params *p);
+/* Host pointers; params NULL: the defaults.  mean[F], scale[F]: the scaler (read at the named slots only).  Uploads, one
+ * launch, one synchronise. */
+int rovmpc_score_pairs(rovmpc_handle *h, const int32_t *code_t, const int32_t *code_off_t, const double *consts_t,
+                       const int32_t *const_off_t, int32_t Rt, const int32_t *code_g, const int32_t *code_off_g,
+                       const double *consts_g, const int32_t *const_off_g, int32_t Rg, const int32_t *pairs, int32_t Q,
+                       const double *X, int32_t F, const double *mean, const double *scale, const double *time, const int64_t *len,
+                       int64_t T, int64_t B, const double *theta, const double *gamma, const rovmpc_horizon_params *params,
+                       double *skill, double *pred);
+/* X, time, theta, gamma, skill and pred in device memory (all double), enqueued on the handle's stream without a
+ * synchronise.  The programs, pairs, len, mean and scale stay HOST arrays, checked here before anything is launched and
+ * staged as rovmpc_score_rows_device stages its programs (the same buffer of the handle, the same rule for a second call). */
+int rovmpc_score_pairs_device(rovmpc_handle *h, const int32_t *code_t, const int32_t *code_off_t, const double *consts_t,
+                              const int32_t *const_off_t, int32_t Rt, const int32_t *code_g, const int32_t *code_off_g,
+                              const double *consts_g, const int32_t *const_off_g, int32_t Rg, const int32_t *pairs, int32_t Q,
+                              const double *d_X, int32_t F, const double *mean, const double *scale, const double *d_time,
+                              const int64_t *len, int64_t T, int64_t B, const double *d_theta, const double *d_gamma,
+                              const rovmpc_horizon_params *params, double *d_skill, double *d_pred);
 
 /* solve_catenary(l, delta_H, L) (main_fun.py:418-431) and, if T_out != NULL, the tension
  * rule of main_fun.py:302-305 with cfg.cable_wet_weight. */
