@@ -1038,10 +1038,14 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             T Ax, Ay, Az;
             if (n == 0) { Ax = A0x; Ay = A0y; Az = A0z; }
             else { Ax = (Vx - Wx) * kk.inv_h; Ay = (Vy - Wy) * kk.inv_h; Az = (Vz - Wz) * kk.inv_h; }
-            const T row[10] = {sway_n, surge_n, a_sway, a_surge, kk.vs * Vx, kk.vs * Vy, kk.vs * Vz, kk.vs * Ax, kk.vs * Ay, kk.vs * Az};
+            {
+#pragma clang fp contract(on)
+                // (each product rounded before the scaling: see integrate_dd's store_row)
+                const T row[10] = {sway_n, surge_n, a_sway, a_surge, kk.vs * Vx, kk.vs * Vy, kk.vs * Vz, kk.vs * Ax, kk.vs * Ay, kk.vs * Az};
 #pragma unroll
-            for (int p = 0; p < 10; ++p)
-                if (uses(p)) RV_PX(p, n, c) = (row[p] - sMean[4 + p]) * sInv[4 + p];
+                for (int p = 0; p < 10; ++p)
+                    if (uses(p)) RV_PX(p, n, c) = (row[p] - sMean[4 + p]) * sInv[4 + p];
+            }
             return;
         }
         const T tension = m_clip(nr, T(1e-5), T(10));                        // :27
@@ -1626,7 +1630,12 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
             T Vx = V0x, Vy = V0y, Vz = V0z, sway_p = T(0), surge_p = T(0);
             if (VT == ROVMPC_VT_COMPOSE)
                 dd_surge_sway<T>(vs_reg * Vx, vs_reg * Vy, vs_reg * Vz, RV_PL(sA, 5, 0, c), RV_PL(sA, 6, 0, c), RV_PL(sA, 7, 0, c), sway_p, surge_p);
+            // The row is (fl(v_scale V) - mean) inv, each product rounded as the oracle's.  Under the default contraction mode a
+            // build may fuse v_scale V into the subtraction, and a slot that is an exact zero -- V_x at the scaler mean, which
+            // the rows dividing by V_x turn into NaN -- was 0 in one hiprtc build and 1e-17 in another: language-level fusion
+            // only in the three blocks that scale a features_dd row (here, integrate_dd_jit's row, phase 2's node_item).
             auto store_row = [&](int node, T sway, T surge, T a_sway, T a_surge, T vx, T vy, T vz, T ax, T ay, T az) {
+#pragma clang fp contract(on)
                 const T row[10] = {sway, surge, a_sway, a_surge, vs_reg * vx, vs_reg * vy, vs_reg * vz, vs_reg * ax, vs_reg * ay, vs_reg * az};
 #pragma unroll
                 for (int p = 0; p < 10; ++p)
@@ -2017,6 +2026,8 @@ RV_DEV void rollout_body(const RolloutArgs<T> &a) {
 #pragma unroll
             for (int p = 0; p < 14; ++p) { dmean[p] = dinv[p] = T(0); if (p < 4 || uses(p - 4)) { dmean[p] = sMean[p]; dinv[p] = sInv[p]; } }
             auto row = [&](T *x, T sway, T surge, T a_sway, T a_surge, T vx, T vy, T vz, T ax, T ay, T az) {
+#pragma clang fp contract(on)
+                // (each product rounded before the scaling: see integrate_dd's store_row)
                 const T r[10] = {sway, surge, a_sway, a_surge, vs_reg * vx, vs_reg * vy, vs_reg * vz, vs_reg * ax, vs_reg * ay, vs_reg * az};
 #pragma unroll
                 for (int p = 0; p < 10; ++p) if (uses(p)) x[p] = (r[p] - dmean[4 + p]) * dinv[4 + p];

@@ -66,6 +66,7 @@ def c_lib(name, F):
     return NP_MODEL[(name, F.name)] + 1.0
 
 
+@lru_cache(maxsize=None)
 def _half_ulp_lo(F, pair):
     K = dm.sincos_constants(F.dm) if pair else dm.sin_constants(F.dm)
     return float(K["hi"]), 0.5 * float(dm.ulp(float(K["lo"]), F.dm))

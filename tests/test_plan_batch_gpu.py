@@ -165,15 +165,20 @@ def test_wide_rows(rv, dtype):
 
 
 # ---- 3. model paths --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", ["builtin", "force_interpreter", "gen2_f32"])
+@pytest.mark.parametrize("kind", ["builtin", "force_interpreter", "gen2_f32", "gen3", "gen3_f32"])
 def test_model_paths(rv, kind):
+    """(The second-order kinds read the rates (dtheta, dgamma) from slots 14 / 15 of problems(): non-zero in every problem.)"""
     N, K = 10, 128
     if kind == "gen2_f32":
         model, cfg = rv.generation2_model(), dict(N=N, K=K, dtype="f32", feature_map=rv.FEATURES_GEN2)
+    elif kind in ("gen3", "gen3_f32"):
+        model, cfg = rv.generation3_model(), dict(N=N, K=K, dtype=kind[5:] or "f64", jit=True, feature_map=rv.FEATURES_GEN3)
+        assert np.all(problems(rv, 2, K, N, 0)[:, 14:16] != 0.0)
     else:
         model, cfg = rv.default_model(), dict(N=N, K=K, force_interpreter=(kind == "force_interpreter"))
     with rv.Engine(rv.MPCConfig(**cfg), model) as e:
-        assert e.model_path == {"builtin": "builtin", "force_interpreter": "interpreter", "gen2_f32": "jit"}[kind]
+        assert e.model_path == {"builtin": "builtin", "force_interpreter": "interpreter", "gen2_f32": "jit", "gen3": "jit",
+                                "gen3_f32": "jit"}[kind]
     check_mppi(rv, cfg, 2, 2, model=model)
     check_cem(rv, cfg, 2, 2, n_elite=8, model=model)
 
