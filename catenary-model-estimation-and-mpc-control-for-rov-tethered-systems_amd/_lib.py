@@ -262,6 +262,34 @@ class FitParams(C.Structure):
         return p
 
 
+CALIB_GROUP_OUT = 8
+CALIB_FRAME_OUT = 5
+
+
+class CalibParams(C.Structure):
+    """Mirror of ``rovmpc_calib_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("max_iter", C.c_int32), ("free_length", C.c_int32), ("reserved_", C.c_int32),
+                ("L0", C.c_double), ("L_lo", C.c_double), ("L_hi", C.c_double), ("tol", C.c_double), ("tol_L", C.c_double)]
+
+    @classmethod
+    def make(cls, L0=None, free_length: bool = True, L_lo: float = 0.0, L_hi: float = float("inf"), tol: float = 1e-12,
+             tol_L: float = 1e-12, max_iter: int = 60) -> "CalibParams":
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) <= 1000:
+            raise ValueError(f"max_iter must be an integer in 1..1000 (got {max_iter!r})")
+        tol, tol_L, L_lo, L_hi = float(tol), float(tol_L), float(L_lo), float(L_hi)
+        if not tol >= 0 or not tol_L >= 0:
+            raise ValueError(f"tol and tol_L must be >= 0 (got {tol!r}, {tol_L!r})")
+        if L0 is not None and not (math.isfinite(float(L0)) and float(L0) > 0):
+            raise ValueError(f"L0 must be positive and finite (got {L0!r})")
+        if not L_lo < L_hi:
+            raise ValueError(f"the box (L_lo, L_hi) is empty (got {L_lo!r}, {L_hi!r})")
+        p = cls()
+        p.struct_size, p.max_iter, p.free_length = C.sizeof(cls), int(max_iter), int(bool(free_length))
+        p.L0 = float("nan") if L0 is None else float(L0)
+        p.L_lo, p.L_hi, p.tol, p.tol_L = L_lo, L_hi, tol, tol_L
+        return p
+
+
 TRACK_MAX_STARTS = 8
 TRACK_OUT = 9
 TRACK_DEFAULT_STARTS = ((0.0, 0.0), (0.3, 0.0), (-0.3, 0.0), (0.6, 0.0), (-0.6, 0.0))
@@ -398,6 +426,10 @@ _SIGNATURES = {
     "rovmpc_default_fit_params": (None, [C.POINTER(FitParams)]),
     "rovmpc_fit_theta_gamma": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.POINTER(FitParams), _P]),
     "rovmpc_fit_theta_gamma_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.POINTER(FitParams), _P]),
+    "rovmpc_default_calib_params": (None, [C.POINTER(CalibParams)]),
+    "rovmpc_calibrate_cable": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(CalibParams), _P, _P]),
+    "rovmpc_calibrate_cable_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(CalibParams), _P, _P]),
+    "rovmpc_cable_markers": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P]),
     "rovmpc_default_track_params": (None, [C.POINTER(TrackParams)]),
     "rovmpc_track_markers": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.POINTER(TrackParams), _P]),
     "rovmpc_track_markers_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.POINTER(TrackParams), _P, _P]),

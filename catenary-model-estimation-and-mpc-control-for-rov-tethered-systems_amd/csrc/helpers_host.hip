@@ -3,6 +3,7 @@
 
 #include "util_kernels.h"
 #include "fit_kernels.h"
+#include "calib_kernels.h"
 #include "track_kernels.h"
 #include "score_kernels.h"
 #include "refit_kernels.h"
@@ -512,6 +513,201 @@ extern "C" int rovmpc_fit_theta_gamma_device(rovmpc_handle *h, const double *d_P
     a.P0 = d_P0; a.P1 = d_P1; a.Y = d_Y; a.guess = d_guess; a.out = d_out;
     launch_fit(h, a);
     return launched(h, "marker fit");
+}
+
+// ---- the cable length from marker recordings, markers by arc length (calib_kernels.h) ----------
+
+extern "C" void rovmpc_default_calib_params(rovmpc_calib_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(rovmpc_calib_params);
+    p->max_iter = 60;
+    p->free_length = 1;
+    p->L0 = NAN;
+    p->L_lo = 0.0; p->L_hi = INFINITY;
+    p->tol = 1e-12; p->tol_L = 1e-12;
+}
+
+// The handle's working buffers of the calibration: one device block [records | group records | done words | offsets], the
+// host copy the offsets are uploaded from and the event behind that upload (the copy is not rewritten before it).
+struct CalibWork {
+    void *d = nullptr;
+    size_t bytes = 0;
+    std::vector<int32_t> off_host;
+    hipEvent_t ev = nullptr;
+};
+
+void calib_free(rovmpc_handle *h) {
+    if (!h->calib) return;
+    if (h->calib->ev) (void)hipEventDestroy(h->calib->ev);
+    if (h->calib->d) (void)hipFree(h->calib->d);
+    delete h->calib;
+    h->calib = nullptr;
+}
+
+// `arc` as the law wants it, into the kernel's argument
+static int calib_arc(rovmpc_handle *h, const char *entry, const double *arc, int32_t M, double *dst, int *has_arc) {
+    *has_arc = arc != nullptr;
+    for (int m = 0; m < ROVMPC_FIT_MAX_MARKERS; ++m) dst[m] = 0.0;
+    if (!arc) return ROVMPC_OK;
+    for (int m = 0; m < M; ++m) {
+        if (!std::isfinite(arc[m]) || (m > 0 && !(arc[m] > arc[m - 1])))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: arc must be finite and strictly increasing (arc[%d] = %g)", entry, m, arc[m]);
+        dst[m] = arc[m];
+    }
+    if (arc[0] != 0.0 || arc[M - 1] != 1.0) FAIL(h, ROVMPC_ERR_INVALID, "%s: arc must run from 0 to 1 (got %g .. %g)", entry, arc[0], arc[M - 1]);
+    return ROVMPC_OK;
+}
+
+// the checks both entries share, then the kernel's arguments but for the pointers
+static int calib_args(rovmpc_handle *h, const char *entry, const void *P0, const void *P1, const void *Y, int64_t F, int32_t M,
+                      const int32_t *group_off, int32_t G, const double *arc, const rovmpc_calib_params *params, const void *out_group,
+                      const void *out_frame, CalibArgs &a) {
+    rovmpc_calib_params p;
+    rovmpc_default_calib_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(rovmpc_calib_params))
+            FAIL(h, ROVMPC_ERR_INVALID, "rovmpc_calib_params.struct_size %d != %d (ABI mismatch)", params->struct_size, (int)sizeof(rovmpc_calib_params));
+        p = *params;
+    }
+    if (F < 0 || G < 0) FAIL(h, ROVMPC_ERR_INVALID, "%s: F and G must be >= 0 (got %lld, %d)", entry, (long long)F, G);
+    if (F > (int64_t)1 << 24) FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 frames in one call (got %lld)", entry, (long long)F);
+    if (M < 3 || M > ROVMPC_FIT_MAX_MARKERS) FAIL(h, ROVMPC_ERR_INVALID, "%s: M must be in 3..%d (got %d)", entry, ROVMPC_FIT_MAX_MARKERS, M);
+    if (!(p.tol >= 0) || !(p.tol_L >= 0)) FAIL(h, ROVMPC_ERR_INVALID, "%s: tol and tol_L must be >= 0 (got %g, %g)", entry, p.tol, p.tol_L);
+    if (p.max_iter < 1 || p.max_iter > 1000) FAIL(h, ROVMPC_ERR_INVALID, "%s: max_iter must be in 1..1000 (got %d)", entry, p.max_iter);
+    const rovmpc_config &c = h->cfg;
+    const bool f64 = c.dtype == ROVMPC_F64;
+    memset(&a, 0, sizeof(a));
+    a.L0 = std::isnan(p.L0) ? (f64 ? c.L : (double)(float)c.L) : p.L0;
+    if (!(a.L0 > 0) || !std::isfinite(a.L0)) FAIL(h, ROVMPC_ERR_INVALID, "%s: L0 must be positive and finite (got %g)", entry, p.L0);
+    if (!(p.L_lo < p.L_hi)) FAIL(h, ROVMPC_ERR_INVALID, "%s: the box (L_lo, L_hi) is empty (got %g, %g)", entry, p.L_lo, p.L_hi);
+    if (p.free_length && !(p.L_lo < a.L0 && a.L0 < p.L_hi))
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: L0 = %g lies outside the box (%g, %g)", entry, a.L0, p.L_lo, p.L_hi);
+    if (int rc = calib_arc(h, entry, arc, M, a.arc, &a.has_arc)) return rc;
+    if (F > 0 && G > 0) {
+        if (!P0 || !P1 || !Y || !group_off || !out_group || !out_frame)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (P0, P1, Y, group_off, out_group or out_frame)", entry);
+        if (group_off[0] != 0 || (int64_t)group_off[G] != F)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off must run from 0 to F = %lld (got %d .. %d)", entry, (long long)F, group_off[0], group_off[G]);
+        for (int g = 0; g < G; ++g)
+            if (group_off[g + 1] < group_off[g]) FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off decreases at group %d", entry, g);
+    }
+    a.L_lo = p.L_lo; a.L_hi = p.L_hi;
+    a.c_lo = f64 ? c.c_lo : (double)(float)c.c_lo; a.c_hi = f64 ? c.c_hi : (double)(float)c.c_hi;
+    a.up = c.frame == ROVMPC_ENU ? 1.0 : -1.0;
+    a.tol = p.tol; a.tol_L = p.tol_L; a.F = F; a.G = G; a.M = M; a.max_iter = p.max_iter; a.free_length = p.free_length != 0;
+    return ROVMPC_OK;
+}
+
+// The working buffers for F frames in G groups, grown on demand, and the offsets uploaded behind whatever the stream holds.
+static int calib_bind(rovmpc_handle *h, const int32_t *group_off, CalibArgs &a) {
+    if (!h->calib) h->calib = new CalibWork();
+    CalibWork &w = *h->calib;
+    const size_t n_rec = (size_t)CF_FIELDS * a.F, n_grp = (size_t)CG_FIELDS * a.G;
+    const size_t bytes = (n_rec + n_grp) * sizeof(double) + ((size_t)a.G + (size_t)a.G + 1) * sizeof(int);
+    if (!w.ev) HIPCHK(h, hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+    else HIPCHK(h, hipEventSynchronize(w.ev));                              // the upload of the call before has read off_host
+    if (bytes > w.bytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));                         // (growth only: a call before may still use the old block)
+        if (w.d) (void)hipFree(w.d);
+        w.d = nullptr; w.bytes = 0;
+        HIPCHK(h, hipMalloc(&w.d, bytes));
+        w.bytes = bytes;
+    }
+    a.rec = (double *)w.d;
+    a.grp = a.rec + n_rec;
+    a.done = (int *)(a.grp + n_grp);
+    int *d_off = a.done + a.G;
+    a.group_off = d_off;
+    w.off_host.assign(group_off, group_off + a.G + 1);
+    HIPCHK(h, hipMemcpyAsync(d_off, w.off_host.data(), ((size_t)a.G + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(w.ev, h->stream));
+    return ROVMPC_OK;
+}
+
+static void launch_calib_pair(rovmpc_handle *h, CalibArgs &a, int k) {
+    a.launch = k;
+    hipLaunchKernelGGL(calib_frames_kernel, dim3(grid_for(a.F, FIT_FRAMES)), dim3(FIT_NT), 0, h->stream, a);
+    hipLaunchKernelGGL(calib_reduce_kernel, dim3((unsigned)a.G), dim3(CALIB_RNT), 0, h->stream, a);
+}
+
+constexpr int CALIB_BATCH = 8;               // pairs the host entry enqueues between two looks at the done words
+
+extern "C" int rovmpc_calibrate_cable(rovmpc_handle *h, const double *P0, const double *P1, const double *Y, int64_t F, int32_t M,
+                                      const int32_t *group_off, int32_t G, const double *guess, const double *arc,
+                                      const rovmpc_calib_params *params, double *out_group, double *out_frame) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    CalibArgs a;
+    if (int rc = calib_args(h, "rovmpc_calibrate_cable", P0, P1, Y, F, M, group_off, G, arc, params, out_group, out_frame, a)) return rc;
+    if (F == 0 || G == 0) return ROVMPC_OK;
+    HelperCall c(h);
+    if (!c.ok()) return c.finish();
+    if (int rc = calib_bind(h, group_off, a)) return rc;
+    const auto d0 = c.upload(P0, (size_t)F * 3);
+    const auto d1 = c.upload(P1, (size_t)F * 3);
+    const auto dY = c.upload(Y, (size_t)F * M * 3);
+    const auto dG = guess ? c.upload(guess, (size_t)F * 2) : DevArray<double>{nullptr, 0};
+    const auto dOg = c.buffer<double>((size_t)G * ROVMPC_CALIB_GROUP_OUT);
+    const auto dOf = c.buffer<double>((size_t)F * ROVMPC_CALIB_FRAME_OUT);
+    a.P0 = d0.p; a.P1 = d1.p; a.Y = dY.p; a.guess = dG.p; a.out_group = dOg.p; a.out_frame = dOf.p;
+    std::vector<int> done((size_t)G);
+    for (int k = 0; c.ok() && k <= a.max_iter;) {
+        for (int i = 0; i < CALIB_BATCH && k <= a.max_iter; ++i, ++k) launch_calib_pair(h, a, k);
+        if (k > a.max_iter) break;
+        hipError_t e = hipMemcpyAsync(done.data(), a.done, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) FAIL(h, ROVMPC_ERR_HIP, "reading the done words failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        bool all = true;
+        for (int g = 0; g < G; ++g) all = all && done[g] != 0;
+        if (all) break;
+    }
+    c.download(out_group, dOg);
+    c.download(out_frame, dOf);
+    return c.finish();
+}
+
+extern "C" int rovmpc_calibrate_cable_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t F,
+                                             int32_t M, const int32_t *group_off, int32_t G, const double *d_guess, const double *arc,
+                                             const rovmpc_calib_params *params, double *d_out_group, double *d_out_frame) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    CalibArgs a;
+    if (int rc = calib_args(h, "rovmpc_calibrate_cable_device", d_P0, d_P1, d_Y, F, M, group_off, G, arc, params, d_out_group, d_out_frame, a))
+        return rc;
+    if (F == 0 || G == 0) return ROVMPC_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = calib_bind(h, group_off, a)) return rc;
+    a.P0 = d_P0; a.P1 = d_P1; a.Y = d_Y; a.guess = d_guess; a.out_group = d_out_group; a.out_frame = d_out_frame;
+    for (int k = 0; k <= a.max_iter; ++k) launch_calib_pair(h, a, k);
+    return launched(h, "cable calibration");
+}
+
+extern "C" int rovmpc_cable_markers(rovmpc_handle *h, const double *P0, const double *P1, const double *theta, const double *gamma,
+                                    const double *L, const double *arc, int64_t B, int32_t M, double *out) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    const char *entry = "rovmpc_cable_markers";
+    if (B < 0 || B > (int64_t)1 << 24) FAIL(h, ROVMPC_ERR_INVALID, "%s: B must be in 0..2^24 (got %lld)", entry, (long long)B);
+    if (M < 3 || M > ROVMPC_FIT_MAX_MARKERS) FAIL(h, ROVMPC_ERR_INVALID, "%s: M must be in 3..%d (got %d)", entry, ROVMPC_FIT_MAX_MARKERS, M);
+    MarkersArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = calib_arc(h, entry, arc, M, a.arc, &a.has_arc)) return rc;
+    if (B > 0 && (!P0 || !P1 || !theta || !gamma || !out)) FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (P0, P1, theta, gamma or out)", entry);
+    if (B == 0) return ROVMPC_OK;
+    const rovmpc_config &cf = h->cfg;
+    const bool f64 = cf.dtype == ROVMPC_F64;
+    a.L = f64 ? cf.L : (double)(float)cf.L; a.c_lo = f64 ? cf.c_lo : (double)(float)cf.c_lo; a.c_hi = f64 ? cf.c_hi : (double)(float)cf.c_hi;
+    a.up = cf.frame == ROVMPC_ENU ? 1.0 : -1.0;
+    a.B = B; a.M = M;
+    HelperCall c(h);
+    const auto d0 = c.upload(P0, (size_t)B * 3);
+    const auto d1 = c.upload(P1, (size_t)B * 3);
+    const auto dt = c.upload(theta, (size_t)B);
+    const auto dg = c.upload(gamma, (size_t)B);
+    const auto dL = L ? c.upload(L, (size_t)B) : DevArray<double>{nullptr, 0};
+    const auto dO = c.buffer<double>((size_t)B * M * 3);
+    a.P0 = d0.p; a.P1 = d1.p; a.theta = dt.p; a.gamma = dg.p; a.Lb = dL.p; a.out = dO.p;
+    if (c.ok()) hipLaunchKernelGGL(cable_markers_kernel, dim3(grid_for(B * M, 256)), dim3(256), 0, h->stream, a);
+    c.download(out, dO);
+    return c.finish();
 }
 
 // ---- (theta, gamma) along marker recordings (track_kernels.h) ----------------------------------

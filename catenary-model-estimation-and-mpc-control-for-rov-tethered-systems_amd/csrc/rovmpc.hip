@@ -371,6 +371,7 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
                     h->d_nav_track, h->d_nav_spheres, h->d_tether_spheres, h->d_tether_traj, h->d_score_prog};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->score_prog_ev) (void)hipEventDestroy(h->score_prog_ev);
+    calib_free(h);
     if (h->pipe_stream_owned && h->pipe_streams[1]) (void)hipStreamDestroy(h->pipe_streams[1]);
     mailbox_free(h->samp_box);
     if (h->h_err) (void)hipHostFree(h->h_err);

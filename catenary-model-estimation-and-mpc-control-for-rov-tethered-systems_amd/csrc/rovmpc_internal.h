@@ -110,6 +110,7 @@ struct rovmpc_handle {
     size_t score_prog_bytes = 0;              // their host copy (the source of the upload) and the event behind that upload
     std::vector<unsigned char> score_prog_host;
     hipEvent_t score_prog_ev = nullptr;
+    struct CalibWork *calib = nullptr;        // rovmpc_calibrate_cable*: its working buffers, grown on demand (helpers_host.hip)
     // rovmpc_mpc_step_sampled: two candidate tensors (the sampler of step s+1 reads the winner of step s for the warm
     // start) and the mailbox of the record (its sequence numbers are samp_steps)
     void *d_Us[2] = {nullptr, nullptr};
@@ -237,6 +238,9 @@ struct Launchable {
     hipFunction_t mod = nullptr;     // function of the hiprtc module
     size_t lds = 0;                  // dynamic LDS, bytes
 };
+
+// ---- helpers_host.hip ----
+void calib_free(rovmpc_handle *h);           // the working buffers of rovmpc_calibrate_cable*, for rovmpc_destroy
 
 // ---- rovmpc.hip ----
 Geo launch_geometry(const rovmpc_handle *h, int B);

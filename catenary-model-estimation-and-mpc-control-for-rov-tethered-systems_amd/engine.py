@@ -905,6 +905,67 @@ class Engine:
         torch.cuda.synchronize(dev)                     # (the device: the fit runs on the handle's own stream)
         return self._fit_result(dO.cpu().numpy(), single)
 
+    def calibrate_cable(self, P0, P1, markers, group_off, guess=None, arc=None, L0=None, free_length: bool = True, L_lo: float = 0.0,
+                        L_hi: float = float("inf"), tol: float = 1e-12, tol_L: float = 1e-12, max_iter: int = 60, device: bool = False):
+        """The cable length of every group of frames (rovmpc_calibrate_cable; law in include/rovmpc.h): P0, P1 (F, 3),
+        ``markers`` (F, M, 3), ``group_off`` (G + 1,) offsets, ``guess`` (F, 2) or None, ``arc`` (M,) or None (the index
+        rule).  Returns (out_group (G, 8), out_frame (F, 5)) as the entry leaves them; ``rovmpc.calibrate_cable`` shapes the
+        arguments and names the columns.  ``device``: through rovmpc_calibrate_cable_device on torch buffers, the same bits."""
+        Y = np.ascontiguousarray(markers, np.float64)
+        if Y.ndim != 3 or Y.shape[2] != 3:
+            raise ValueError(f"markers must be (F, M, 3), got {Y.shape}")
+        F, M = Y.shape[:2]
+        P0 = np.ascontiguousarray(np.broadcast_to(np.asarray(P0, np.float64), (F, 3)))
+        P1 = np.ascontiguousarray(np.broadcast_to(np.asarray(P1, np.float64), (F, 3)))
+        G_ = None if guess is None else np.ascontiguousarray(np.broadcast_to(np.asarray(guess, np.float64), (F, 2)))
+        off = np.ascontiguousarray(group_off, np.int32)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("group_off must hold G + 1 offsets")
+        G = off.size - 1
+        s = None if arc is None else np.ascontiguousarray(arc, np.float64)
+        if s is not None and s.shape != (M,):
+            raise ValueError(f"arc must be ({M},), got {s.shape}")
+        params = _lib.CalibParams.make(L0, free_length, L_lo, L_hi, tol, tol_L, max_iter)
+        if not device:
+            og, of = np.full((G, _lib.CALIB_GROUP_OUT), np.nan), np.full((F, _lib.CALIB_FRAME_OUT), np.nan)
+            self._check(self.lib.rovmpc_calibrate_cable(self._h, _ptr(P0), _ptr(P1), _ptr(Y), F, M, _ptr(off), G, _ptr(G_), _ptr(s),
+                                                        C.byref(params), _ptr(og), _ptr(of)))
+            return og, of
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        d0, d1, dY = (torch.tensor(x, device=dev) for x in (P0, P1, Y))
+        dG = None if G_ is None else torch.tensor(G_, device=dev)
+        dog = torch.full((G, _lib.CALIB_GROUP_OUT), float("nan"), dtype=torch.float64, device=dev)
+        dof = torch.full((F, _lib.CALIB_FRAME_OUT), float("nan"), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_calibrate_cable_device(self._h, d0.data_ptr(), d1.data_ptr(), dY.data_ptr(), F, M, _ptr(off), G,
+                                                           None if dG is None else dG.data_ptr(), _ptr(s), C.byref(params),
+                                                           dog.data_ptr(), dof.data_ptr()))
+        torch.cuda.synchronize(dev)                     # (the device: the calibration runs on the handle's own stream)
+        return dog.cpu().numpy(), dof.cpu().numpy()
+
+    def cable_markers(self, P0, P1, theta, gamma, L=None, arc=None, M: int = 16) -> np.ndarray:
+        """The markers of the cable between P0 and P1 at (theta, gamma) (rovmpc_cable_markers; law in include/rovmpc.h): the
+        forward model of ``calibrate_cable``.  theta, gamma scalars or (B,); P0, P1 (3,) or (B, 3); ``L`` None (the
+        config's), a scalar or (B,); ``arc`` (M,) fractions of the length from 0 to 1, None = the index rule.  Returns
+        (M, 3) for scalars, else (B, M, 3)."""
+        th = np.asarray(theta, np.float64)
+        single = th.ndim == 0 and np.ndim(gamma) == 0 and np.ndim(P0) == 1 and np.ndim(P1) == 1 and np.ndim(L) == 0
+        shape = np.broadcast_shapes(np.shape(theta), np.shape(gamma), np.shape(P0)[:-1], np.shape(P1)[:-1], np.shape(0.0 if L is None else L))
+        if len(shape) > 1:
+            raise ValueError(f"theta, gamma, L must be scalars or (B,) and P0, P1 (3,) or (B, 3) (got a batch of shape {shape})")
+        B = int(shape[0]) if shape else 1
+        c = lambda x, sh: np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), sh))
+        P0, P1, th, ga = c(P0, (B, 3)), c(P1, (B, 3)), c(theta, (B,)), c(gamma, (B,))
+        Lb = None if L is None else c(L, (B,))
+        M = int(M)
+        s = None if arc is None else np.ascontiguousarray(arc, np.float64)
+        if s is not None and s.shape != (M,):
+            raise ValueError(f"arc must be ({M},), got {s.shape}")
+        out = np.full((B, M, 3), np.nan)
+        self._check(self.lib.rovmpc_cable_markers(self._h, _ptr(P0), _ptr(P1), _ptr(th), _ptr(ga), _ptr(Lb), _ptr(s), B, M, _ptr(out)))
+        return out[0] if single else out
+
     def _track_inputs(self, P0, P1, markers, carry):
         Y = np.ascontiguousarray(markers, np.float64)
         single = Y.ndim == 3

@@ -698,6 +698,107 @@ int rovmpc_track_markers(rovmpc_handle *h, const double *P0, const double *P1, c
 int rovmpc_track_markers_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t B, int64_t T,
                                 int32_t M, double *d_carry, const rovmpc_track_params *params, double *d_out, double *d_exo);
 
+/* ---- the cable length from marker recordings; markers placed by arc length ----------------------------------------------
+ * The fit above takes the cable length on trust and matches marker m to the sample at t_m = m / (M - 1), uniform along the
+ * chord.  A physical marker sits at a fixed arc length, and a user's cable need not be the reference's 3 m.  These entries
+ * place the markers by arc length and estimate L from a recording, pooled over its frames, with every frame's (theta, gamma)
+ * as nuisance parameters.  rovmpc_fit_theta_gamma and rovmpc_track_markers are unchanged and keep the index rule.
+ * Law.  All arithmetic in double; c_lo = (T) cfg.c_lo, c_hi = (T) cfg.c_hi and up as the fit holds them; the length L is a
+ * double VARIABLE here (it starts at L0, by default (T) cfg.L).
+ *   placement: `arc` = s[M] with s_0 = 0, s_{M-1} = 1, strictly increasing, finite: marker m sits at the arc length s_m L
+ *             from A.  With the node parameters of the tether law (u = C' l' / 2, ath = atanh(dH' / L), 2 / C') the cable's
+ *             arc from A to the chord parameter t is (2 / C') sinh(u t) cosh(u (t - 1) + ath) (= L at t = 1), so with
+ *             w = u (-) ath the sample of marker m sits at
+ *                 t_m = (w + asinh(s_m ((2 L) / (2 / C')) - sinh(w))) / (2 u),     t_0 = 0 and t_{M-1} = 1 set exactly,
+ *             and the point is the tether law's sample formula at that t.  On the chord (no root inside the bracket) t_m =
+ *             s_m.  asinh(x) = sign(x) log1p(|x| + x^2 / (1 + sqrt(1 + x^2))).  arc = NULL is the fit's rule t_m =
+ *             m / (M - 1), by the tether law's own sample function;
+ *   group:    one problem = one group, a run of consecutive frames group_off[g] .. group_off[g + 1] - 1 that share L.  The
+ *             unknowns are L and (theta_t, gamma_t) of every frame of the group;
+ *   frame sums at (theta, gamma, L): a, b, c, g_0, g_1, F exactly as the fit forms them (the theta (+/-) 2^-20 central
+ *             difference, dX/dgamma = k_gamma x (X - A), the dot products and the 16-lane butterfly), at the length L.  With
+ *             j_L,m = (X_m(theta, gamma, L (+) h) - X_m(theta, gamma, L (-) h)) 2^19, h = 2^-20 m:  p_0 = sum w j_theta . j_L,
+ *             p_1 = sum w j_gamma . j_L, d = sum w j_L . j_L, g_L = sum w j_L . r, taken the same way (all four are 0 with
+ *             free_length = 0).  A point is USABLE when theta, theta (+/-) h and, with a free length, L (+/-) h are all
+ *             catenaries and finite;
+ *   classes:  decided once at the start (theta_0, gamma_0) from `guess` or (0, 0), at L0, by the fit's own order: NONFINITE,
+ *             TOO_FEW, DEGENERATE (a vertical start, or a c - b^2 <= 2^-80 a c there), CHORD.  Such a frame is left out for
+ *             the whole run, contributes nothing, and reports the fit's outputs for that status at L0.  The others are ACTIVE;
+ *   sums over frames (of F, d, the Schur sums below, the count N_w of valid markers): over the group's frames in index
+ *             order, a frame that is not active contributing 0; tiles of ROVMPC_SCORE_TILE consecutive frames (counted
+ *             from the group's first) are added by the tree of rovmpc_score_rows, the tile sums in tile order from +0: a
+ *             function of the group alone;
+ *   step at damping mu (from ROVMPC_FIT_MU0):  per frame y' = -A'^-1 g and z' = -A'^-1 p with A' = [[a (1 + mu), b], [b, c (1 +
+ *             mu)]], both by the fit's expressions for (dtheta, dgamma) (p in the place of g for z');
+ *                 S = fma(1 + mu, sum d, sum fma(p_0, z'_0, p_1 z'_1)),   R = sum g_L + sum fma(p_0, y'_0, p_1 y'_1),
+ *                 dL = -R / S  (0 with free_length = 0),   (dtheta_t, dgamma_t) = y'_t  (+ z'_t dL by one fma with a free length).
+ *             Roundings, as the fit's kernel makes them: with a' = a (1 + mu), c' = c (1 + mu), 1 / d = 1 / fma(a', c', -(b b)),
+ *             n = (fma(b, g_1, -(g_0 c')), fma(b, g_0, -(g_1 a'))): y' = n (1 / d) rounded, and with a fixed length the trial
+ *             angle is the single fma(n, 1 / d, theta) (the fit's); with a free length it is theta (+) dtheta.
+ *             The trial (L + dL, theta_t + dtheta_t, gamma_t + dgamma_t) is ACCEPTED when every active frame is usable
+ *             there, L_lo < L + dL < L_hi (free length only), and sum F' <= fma(ROVMPC_FIT_SLACK L, sqrt(N_w sum F), sum F)
+ *             (the fit's slack): it becomes the iterate and mu = max(mu / 10, ROVMPC_FIT_MU_MIN); otherwise the iterate
+ *             stays and mu = 10 mu.  One frame that leaves the bracket at the trial point rejects the step for the whole
+ *             group: give a recording a bracket its frames stay inside;
+ *   stop:     after a trial step with max_t max(|dtheta_t|, |dgamma_t|) <= tol and |dL| <= tol_L, accepted or not (an accepted
+ *             one is taken): CONVERGED.  Else DEGENERATE, returning the iterate, when at the start or after an accepted
+ *             step S > 2^-80 (1 + mu) sum d fails (free length only) or, after an accepted step, an active frame's a c -
+ *             b^2 > 2^-80 a c fails.  Else after max_iter trial steps MAX_ITER; else with mu > ROVMPC_CALIB_MU_MAX = 1e12
+ *             STALLED.  NO_FRAMES when no frame of the group is active.  With noisy markers an angle step has a rounding
+ *             floor (the central difference over 2^-19 turns the points' 2^-52 L into 2^-33 L in a Jacobian entry: about
+ *             1e-12 rad at 1 mm rms), and a long recording's frames are never all below the default tol at once: raise
+ *             tol and tol_L to 1e-9 or so for such data, far below sigma_L.
+ * out_group[g] = [L^, rms = sqrt(sum F / N_w) over the active frames, rms0 = the same at the start, sigma_L, trial steps,
+ * status, active frames, N_w];  sigma_L = sqrt(sum F / (3 N_w - 2 n_active - 1) / S_0) with S_0 the Schur sum at mu = 0 at
+ * the estimate, NaN when the degrees of freedom are <= 0 or free_length = 0; rms, rms0 NaN with NO_FRAMES.
+ * out_frame[f] = [theta, gamma, rms_f, rms0_f, status]: of an active frame the group's status, else the frame's class.
+ * The tie.  A group of one frame with free_length = 0, arc = NULL and L0 = (T) cfg.L is the fit's iteration (a one-frame
+ * tile sum adds only zeros): the frame's columns and the trial-step count equal rovmpc_fit_theta_gamma's out bit for bit
+ * (as long as that fit does not reject 16 trial steps in a row: there this entry answers STALLED).
+ * The bits of a group's and its frames' outputs are a function of the group's frames, the parameters and the config alone:
+ * not of G, the group's place among the others, or the entry.
+ * Bad arguments (a null handle or required pointer, a struct_size mismatch, F < 0, G < 0, M outside 3 ..
+ * ROVMPC_FIT_MAX_MARKERS, offsets that do not run non-decreasing from 0 to F, an `arc` not as above, L0 not positive and
+ * finite (NaN = the default), L_lo >= L_hi or NaN, with a free length L0 outside (L_lo, L_hi), tol or tol_L < 0 or NaN,
+ * max_iter outside 1 .. 1000, F > 2^24) give ROVMPC_ERR_INVALID with a message and launch nothing; F = 0 or G = 0 is
+ * ROVMPC_OK and launches nothing.
+ * Not provided: unknown marker positions s_m, unknown end points, robust losses; a frame whose chord is longer than the L0
+ * it starts from is a chord, hence left out, although it is evidence that L0 is too small (the caller raises L0); the arc
+ * rule inside rovmpc_fit_theta_gamma / rovmpc_track_markers. */
+#define ROVMPC_CALIB_GROUP_OUT 8
+#define ROVMPC_CALIB_FRAME_OUT 5
+#define ROVMPC_CALIB_MU_MAX 1e12
+#define ROVMPC_CALIB_STALLED 6       /* beyond rovmpc_fit_status, whose values the status columns share */
+#define ROVMPC_CALIB_NO_FRAMES 7
+typedef struct rovmpc_calib_params {
+    int32_t struct_size;             /* = sizeof(rovmpc_calib_params), ABI check                         */
+    int32_t max_iter;                /* 1..1000 trial steps, default 60                                  */
+    int32_t free_length;             /* 0: L stays L0; default 1                                         */
+    int32_t reserved_;               /* 0                                                                */
+    double  L0;                      /* metres, > 0; NaN (the default) = (T) cfg.L                       */
+    double  L_lo, L_hi;              /* the box of L, both exclusive; defaults 0, +inf                   */
+    double  tol;                     /* radians, >= 0, default 1e-12                                     */
+    double  tol_L;                   /* metres, >= 0, default 1e-12                                      */
+} rovmpc_calib_params;
+void rovmpc_default_calib_params(rovmpc_calib_params *p);
+/* Host pointers: P0[F][3], P1[F][3], Y[F][M][3], group_off[G + 1], guess[F][2] or NULL, arc[M] or NULL, params or NULL (the
+ * defaults), out_group[G][ROVMPC_CALIB_GROUP_OUT], out_frame[F][ROVMPC_CALIB_FRAME_OUT].  A trial step is a pair of
+ * launches (a wave per frame, then a workgroup per group); the host enqueues them in batches, reads the groups' done words
+ * in between and stops once every group has ended.  Working buffers belong to the handle. */
+int rovmpc_calibrate_cable(rovmpc_handle *h, const double *P0, const double *P1, const double *Y, int64_t F, int32_t M,
+                           const int32_t *group_off, int32_t G, const double *guess, const double *arc,
+                           const rovmpc_calib_params *params, double *out_group, double *out_frame);
+/* The same on device pointers (all double; group_off, arc and params stay host pointers), max_iter + 1 pairs of launches
+ * enqueued on the handle's stream without a synchronise: the pairs of a group that has ended return at once. */
+int rovmpc_calibrate_cable_device(rovmpc_handle *h, const double *d_P0, const double *d_P1, const double *d_Y, int64_t F,
+                                  int32_t M, const int32_t *group_off, int32_t G, const double *d_guess, const double *arc,
+                                  const rovmpc_calib_params *params, double *d_out_group, double *d_out_frame);
+/* The forward model alone, for synthesis and plots: out[b][m] = the marker m of the cable between P0[b] and P1[b] at
+ * (theta[b], gamma[b]) with the length L[b] (L = NULL: (T) cfg.L) and the placement `arc` (NULL: the index rule, where the
+ * points are those of the fit's model bit for bit, plus P0).  Host pointers; B = 0 is ROVMPC_OK; bad arguments as above. */
+int rovmpc_cable_markers(rovmpc_handle *h, const double *P0, const double *P1, const double *theta, const double *gamma,
+                         const double *L, const double *arc, int64_t B, int32_t M, double *out);
+
 /* Parity/debug: all K costs (and, if traj_all != NULL, all K trajectories [K][N+1][2]). */
 int rovmpc_rollout_costs(rovmpc_handle *h, const rovmpc_state *state, const void *U,
                          void *J_out, void *traj_all);
