@@ -21,9 +21,10 @@ from .features import extract_features, extract_features_arrays, features_dd, fe
 from .lagrangian import euler_lagrange, el_residuals, lagrangian_rollout, differentiate, EulerLagrange
 from .trajgen import generate_rov_trajectories, trajectory_csv
 from .calibration import calibrate_cable, cable_markers, CableCalibration, CalibStatus
-from ._lib import MPPIParams, CEMParams, FitParams, TrackParams, RefitParams, CalibParams
+from ._lib import MPPIParams, CEMParams, FitParams, TrackParams, RefitParams, CalibParams, DiscoverParams
 from .mpc import MPC, MPPI, CEM, BatchedMPPI, BatchedCEM, NavCost, TetherCost, PlanLoopResult, GaussianSampler, DeviceGaussianSampler, synthetic_problem
 from .closed_loop import run_plan_closed_loop
-from .scoring import score_rows, select_model, RowScores, refit_rows, RowRefit, RefitStatus, score_pairs, PairSkill
+from .scoring import score_rows, select_model, RowScores, refit_rows, RowRefit, RefitStatus, score_pairs, PairSkill, \
+    discover_rows, term_library, RowFront, DiscoverStatus
 
 __version__ = "0.1.0"

@@ -345,6 +345,28 @@ class RefitParams(C.Structure):
         return p
 
 
+DISCOVER_MAX_TERMS = 64
+DISCOVER_MAX_SIZE = 8
+DISCOVER_CHUNK = 1024
+DISCOVER_FULL, DISCOVER_MIN_GAIN, DISCOVER_EXHAUSTED, DISCOVER_NONFINITE = range(4)
+
+
+class DiscoverParams(C.Structure):
+    """Mirror of ``rovmpc_discover_params``.  ``make`` checks the values before the library sees them."""
+    _fields_ = [("struct_size", C.c_int32), ("max_terms", C.c_int32), ("dep_tol", C.c_double), ("min_gain", C.c_double)]
+
+    @classmethod
+    def make(cls, max_terms: int = 8, dep_tol: float = 1e-10, min_gain: float = 1e-12) -> "DiscoverParams":
+        if isinstance(max_terms, bool) or int(max_terms) != max_terms or not 1 <= int(max_terms) <= DISCOVER_MAX_SIZE:
+            raise ValueError(f"max_terms must be an integer in 1..{DISCOVER_MAX_SIZE} (got {max_terms!r})")
+        dep_tol, min_gain = float(dep_tol), float(min_gain)
+        if not dep_tol >= 0 or not min_gain >= 0:
+            raise ValueError(f"dep_tol and min_gain must be >= 0 (got {dep_tol!r}, {min_gain!r})")
+        p = cls()
+        p.struct_size, p.max_terms, p.dep_tol, p.min_gain = C.sizeof(cls), int(max_terms), dep_tol, min_gain
+        return p
+
+
 HORIZON_COLS = 9
 HORIZON_TILE = 128
 HORIZON_NAMES = ("rmse_theta", "rmse_gamma", "max_abs_theta", "max_abs_gamma", "n_ok", "ss_theta", "ss_gamma", "ss_hold_theta",
@@ -477,6 +499,11 @@ _SIGNATURES = {
                                     C.POINTER(RefitParams), _P, _P]),
     "rovmpc_refit_rows_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P,
                                            C.c_int32, C.POINTER(RefitParams), _P, _P]),
+    "rovmpc_default_discover_params": (None, [C.POINTER(DiscoverParams)]),
+    "rovmpc_discover_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32,
+                                       C.POINTER(DiscoverParams), _P, _P, _P, _P, _P]),
+    "rovmpc_discover_rows_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32,
+                                              C.POINTER(DiscoverParams), _P, _P, _P, _P, _P]),
     "rovmpc_default_horizon_params": (None, [C.POINTER(HorizonParams)]),
     "rovmpc_score_pairs": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P,
                                      C.c_int64, C.c_int64, _P, _P, C.POINTER(HorizonParams), _P, _P]),

@@ -7,6 +7,7 @@
 #include "track_kernels.h"
 #include "score_kernels.h"
 #include "refit_kernels.h"
+#include "discover_kernels.h"
 #include "horizon_kernels.h"
 
 // ---- batched helper mirrors (host pointers, fp64) ---------------------------------------------
@@ -1091,6 +1092,171 @@ extern "C" int rovmpc_refit_rows_device(rovmpc_handle *h, const int32_t *code, c
     plan.a.X = d_X; plan.a.target = d_target; plan.a.consts_out = d_consts_out; plan.a.out = d_out;
     launch_refit(h, R, plan.a);
     return launched(h, "row refit");
+}
+
+// ---- equation rows discovered by sparse regression over a term library (discover_kernels.h) ----
+
+extern "C" void rovmpc_default_discover_params(rovmpc_discover_params *p) {
+    if (!p) return;
+    p->struct_size = (int32_t)sizeof(rovmpc_discover_params);
+    p->max_terms = ROVMPC_DISCOVER_MAX_SIZE;
+    p->dep_tol = 1e-10;
+    p->min_gain = 1e-12;
+}
+
+namespace {
+// a checked call: the kernels' arguments with offsets into the packed copy where discover_bind puts device addresses
+struct DiscoverPlan {
+    ScoreArgs s;                                  // the programs and lengths, packed as for rovmpc_score_rows
+    size_t o_crec, o_crow, o_gchunk, o_gn;        // behind them: the chunk table and the groups' chunk ranges and row counts
+    size_t n_chunks, E;
+    bool has_len;
+    DiscoverArgs a;
+};
+}  // namespace
+
+// the checks both entries share; then everything the kernels read from host arrays packed for one copy
+static int discover_args(rovmpc_handle *h, const char *entry, const int32_t *code, const int32_t *code_off, const double *consts,
+                         const int32_t *const_off, int32_t M, const void *X, int32_t F, const int64_t *len, int64_t T, int64_t B,
+                         const void *target, const int32_t *group_off, int32_t G, const rovmpc_discover_params *params,
+                         const void *picks, const void *coef, const void *loss, const void *info, std::vector<unsigned char> &blob,
+                         DiscoverPlan &plan) {
+    if (!code || !code_off || !const_off || !X || !target || !picks || !coef || !loss || !info)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: null pointer (code, code_off, const_off, X, target, picks, coef, loss or info)", entry);
+    if (M < 1 || M > ROVMPC_DISCOVER_MAX_TERMS) FAIL(h, ROVMPC_ERR_INVALID, "%s: M must be in 1..%d (got %d)", entry, ROVMPC_DISCOVER_MAX_TERMS, M);
+    if (int rc = check_row_call(h, entry, M, F, T, B)) return rc;
+    if (int rc = check_programs(h, entry, code, code_off, consts, const_off, M, F)) return rc;
+    if (int rc = check_lengths(h, entry, len, T, B)) return rc;
+    if (G < 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: G must be >= 1 (got %d)", entry, G);
+    if (!group_off && G != 1) FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off is NULL, which pools all recordings: G must be 1 (got %d)", entry, G);
+    if (group_off) {
+        if (group_off[0] != 0 || (int64_t)group_off[G] != B)
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off must run from 0 to B = %lld (got %d .. %d)", entry, (long long)B, group_off[0], group_off[G]);
+        for (int g = 0; g < G; ++g)
+            if (group_off[g + 1] <= group_off[g]) FAIL(h, ROVMPC_ERR_INVALID, "%s: group_off must increase (group %d is empty or runs backwards)", entry, g);
+    }
+    rovmpc_discover_params p;
+    rovmpc_default_discover_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(rovmpc_discover_params))
+            FAIL(h, ROVMPC_ERR_INVALID, "%s: rovmpc_discover_params.struct_size %d != %d (ABI mismatch)", entry, params->struct_size, (int)sizeof(rovmpc_discover_params));
+        p = *params;
+    }
+    if (p.max_terms < 1 || p.max_terms > ROVMPC_DISCOVER_MAX_SIZE)
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: max_terms must be in 1..%d (got %d)", entry, ROVMPC_DISCOVER_MAX_SIZE, p.max_terms);
+    if (!(p.dep_tol >= 0.0) || !(p.min_gain >= 0.0)) FAIL(h, ROVMPC_ERR_INVALID, "%s: dep_tol and min_gain must be >= 0 (got %g, %g)", entry, p.dep_tol, p.min_gain);
+    // the chunk table: recording after recording, chunk after chunk, so a group's chunks are one range in the law's order
+    const int64_t per_full = (T + ROVMPC_DISCOVER_CHUNK - 1) / ROVMPC_DISCOVER_CHUNK;
+    if (per_full > ((int64_t)1 << 24) || per_full * B > ((int64_t)1 << 24))
+        FAIL(h, ROVMPC_ERR_INVALID, "%s: more than 2^24 chunks of %d rows in one call (got %lld x %lld rows)", entry, ROVMPC_DISCOVER_CHUNK, (long long)B, (long long)T);
+    std::vector<int64_t> crec, crow, gchunk((size_t)G + 1, 0), gn((size_t)G, 0);
+    for (int g = 0; g < G; ++g) {
+        const int64_t b0 = group_off ? group_off[g] : 0, b1 = group_off ? group_off[g + 1] : B;
+        for (int64_t b = b0; b < b1; ++b) {
+            const int64_t n = len ? len[b] : T;
+            for (int64_t r0 = 0; r0 < n; r0 += ROVMPC_DISCOVER_CHUNK) { crec.push_back(b); crow.push_back(r0); }
+            gn[g] += n;
+        }
+        gchunk[g + 1] = (int64_t)crec.size();
+    }
+    pack_programs(code, code_off, consts, const_off, M, F, len, T, B, blob, plan.s);
+    const size_t nc = crec.size();
+    plan.o_crec = (blob.size() + 7) & ~(size_t)7;
+    plan.o_crow = plan.o_crec + nc * sizeof(int64_t);
+    plan.o_gchunk = plan.o_crow + nc * sizeof(int64_t);
+    plan.o_gn = plan.o_gchunk + gchunk.size() * sizeof(int64_t);
+    blob.resize(plan.o_gn + gn.size() * sizeof(int64_t), 0);
+    memcpy(blob.data() + plan.o_crec, crec.data(), nc * sizeof(int64_t));
+    memcpy(blob.data() + plan.o_crow, crow.data(), nc * sizeof(int64_t));
+    memcpy(blob.data() + plan.o_gchunk, gchunk.data(), gchunk.size() * sizeof(int64_t));
+    memcpy(blob.data() + plan.o_gn, gn.data(), gn.size() * sizeof(int64_t));
+    plan.n_chunks = nc; plan.E = (size_t)(M + 1) * (M + 2) / 2; plan.has_len = len != nullptr;
+    DiscoverArgs &a = plan.a;
+    memset(&a, 0, sizeof(a));
+    a.T = T; a.F = F; a.M = M; a.S = p.max_terms; a.dep_tol = p.dep_tol; a.min_gain = p.min_gain;
+    return ROVMPC_OK;
+}
+
+static void discover_bind(DiscoverPlan &plan, const unsigned char *d_blob) {
+    score_bind(plan.s, d_blob, plan.has_len);
+    DiscoverArgs &a = plan.a;
+    a.code = plan.s.code; a.code_off = plan.s.code_off; a.consts = plan.s.consts; a.const_off = plan.s.const_off; a.len = plan.s.len;
+    a.chunk_rec = (const long long *)(d_blob + plan.o_crec);
+    a.chunk_row = (const long long *)(d_blob + plan.o_crow);
+    a.group_chunk = (const long long *)(d_blob + plan.o_gchunk);
+    a.group_n = (const long long *)(d_blob + plan.o_gn);
+}
+
+// the handle's buffer of chunk partials, at least n doubles (hipFree waits for the work that still reads the old one)
+static int discover_partials(rovmpc_handle *h, size_t n) {
+    if (n > h->discover_partial_n) {
+        if (h->d_discover_partial) HIPCHK(h, hipFree(h->d_discover_partial));
+        h->d_discover_partial = nullptr; h->discover_partial_n = 0;
+        HIPCHK(h, hipMalloc(&h->d_discover_partial, n * sizeof(double)));
+        h->discover_partial_n = n;
+    }
+    return ROVMPC_OK;
+}
+
+static void launch_discover(rovmpc_handle *h, int32_t G, const DiscoverPlan &plan) {
+    hipLaunchKernelGGL(discover_gram_kernel, dim3((unsigned)plan.n_chunks), dim3(DISC_NT), discover_gram_lds_bytes(plan.a.M), h->stream, plan.a);
+    hipLaunchKernelGGL(discover_select_kernel, dim3((unsigned)G), dim3(DISC_WAVE), 0, h->stream, plan.a);
+}
+
+extern "C" int rovmpc_discover_rows(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                    const int32_t *const_off, int32_t M, const double *X, int32_t F, const int64_t *len, int64_t T,
+                                    int64_t B, const double *target, const int32_t *group_off, int32_t G,
+                                    const rovmpc_discover_params *params, int32_t *picks, double *coef, double *loss, int64_t *info,
+                                    double *gram) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    DiscoverPlan plan;
+    if (int rc = discover_args(h, "rovmpc_discover_rows", code, code_off, consts, const_off, M, X, F, len, T, B, target, group_off, G, params,
+                               picks, coef, loss, info, blob, plan))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = discover_partials(h, plan.n_chunks * plan.E)) return rc;
+    HelperCall c(h);
+    const size_t n = (size_t)B * T, S = (size_t)plan.a.S;
+    const auto dP = c.upload((const unsigned char *)blob.data(), blob.size());
+    const auto dX = c.upload(X, n * F);
+    const auto dT = c.upload(target, n);
+    const auto dK = c.buffer<int32_t>((size_t)G * S);
+    const auto dC = c.buffer<double>((size_t)G * S * S);
+    const auto dL = c.buffer<double>((size_t)G * (S + 1));
+    const auto dI = c.buffer<long long>((size_t)G * 3);
+    const auto dG = gram ? c.buffer<double>((size_t)G * plan.E) : DevArray<double>{nullptr, 0};
+    discover_bind(plan, dP.p);
+    plan.a.X = dX.p; plan.a.target = dT.p; plan.a.partial = h->d_discover_partial;
+    plan.a.picks = dK.p; plan.a.coef = dC.p; plan.a.loss = dL.p; plan.a.info = dI.p; plan.a.gram = dG.p;
+    if (c.ok()) launch_discover(h, G, plan);
+    c.download(picks, dK);
+    c.download(coef, dC);
+    c.download(loss, dL);
+    c.download((long long *)info, dI);
+    if (gram) c.download(gram, dG);
+    return c.finish();
+}
+
+extern "C" int rovmpc_discover_rows_device(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                           const int32_t *const_off, int32_t M, const double *d_X, int32_t F, const int64_t *len,
+                                           int64_t T, int64_t B, const double *d_target, const int32_t *group_off, int32_t G,
+                                           const rovmpc_discover_params *params, int32_t *d_picks, double *d_coef, double *d_loss,
+                                           int64_t *d_info, double *d_gram) {
+    if (!h) return ROVMPC_ERR_INVALID;
+    std::vector<unsigned char> blob;
+    DiscoverPlan plan;
+    if (int rc = discover_args(h, "rovmpc_discover_rows_device", code, code_off, consts, const_off, M, d_X, F, len, T, B, d_target, group_off,
+                               G, params, d_picks, d_coef, d_loss, d_info, blob, plan))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = discover_partials(h, plan.n_chunks * plan.E)) return rc;
+    if (int rc = stage_programs(h, blob)) return rc;
+    discover_bind(plan, (const unsigned char *)h->d_score_prog);
+    plan.a.X = d_X; plan.a.target = d_target; plan.a.partial = h->d_discover_partial;
+    plan.a.picks = d_picks; plan.a.coef = d_coef; plan.a.loss = d_loss; plan.a.info = (long long *)d_info; plan.a.gram = d_gram;
+    launch_discover(h, G, plan);
+    return launched(h, "row discovery");
 }
 
 // ---- (theta, gamma) row pairs scored by closed-loop N-step-ahead skill (horizon_kernels.h) -----

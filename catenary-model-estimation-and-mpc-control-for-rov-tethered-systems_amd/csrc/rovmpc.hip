@@ -368,7 +368,8 @@ extern "C" void rovmpc_destroy(rovmpc_handle *h) {
     void *ptrs[] = {h->d_U, h->d_J, h->d_traj_all, h->d_state, h->d_blk_traj,
                     h->d_result, h->d_code_th, h->d_code_ga, h->d_consts, h->d_consts64, h->d_Rtab, h->d_k, h->d_stamps,
                     h->d_granules, h->d_gtab, h->d_Jb, h->d_blk_trajb, h->d_granulesb, h->d_step_seq, h->d_Us[0], h->d_Us[1], h->d_cl_granules, h->d_cl_blk_traj, h->d_best, h->d_blk_u,
-                    h->d_nav_track, h->d_nav_spheres, h->d_tether_spheres, h->d_tether_traj, h->d_score_prog};
+                    h->d_nav_track, h->d_nav_spheres, h->d_tether_spheres, h->d_tether_traj, h->d_score_prog,
+                    h->d_discover_partial};
     for (auto &ev : h->pipe_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->score_prog_ev) (void)hipEventDestroy(h->score_prog_ev);
     calib_free(h);

@@ -110,6 +110,8 @@ struct rovmpc_handle {
     size_t score_prog_bytes = 0;              // their host copy (the source of the upload) and the event behind that upload
     std::vector<unsigned char> score_prog_host;
     hipEvent_t score_prog_ev = nullptr;
+    double *d_discover_partial = nullptr;     // rovmpc_discover_rows*: the chunk partials of the last call, grown on demand
+    size_t discover_partial_n = 0;
     struct CalibWork *calib = nullptr;        // rovmpc_calibrate_cable*: its working buffers, grown on demand (helpers_host.hip)
     // rovmpc_mpc_step_sampled: two candidate tensors (the sampler of step s+1 reads the winner of step s for the warm
     // start) and the mailbox of the record (its sequence numbers are samp_steps)

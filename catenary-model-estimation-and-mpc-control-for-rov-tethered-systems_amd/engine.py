@@ -1101,6 +1101,49 @@ class Engine:
         torch.cuda.synchronize(dev)                     # (the device: the refit runs on the handle's own stream)
         return dK.cpu().numpy().reshape(-1)[:G * NK].reshape(G, NK), dO.cpu().numpy()
 
+    def discover_rows(self, programs, X, target, lengths=None, group_off=None, params=None, return_gram: bool = False,
+                      device: bool = False):
+        """Rows of sizes 1 .. S chosen from M compiled terms on G groups of recordings (rovmpc_discover_rows; law in
+        include/rovmpc.h).  ``programs`` as in ``score_rows``, one per term; X (B, T, F), target (B, T), lengths (B,) or None,
+        group_off int32 (G + 1,) or None (all recordings pooled), params a DiscoverParams or None, checked and laid out by
+        ``scoring.discover_rows``.  Returns (picks (G, S) int32, coef (G, S, S), loss (G, S + 1), info (G, 3) int64, gram
+        (G, (M + 1)(M + 2) / 2) or None).  ``device=True`` goes through rovmpc_discover_rows_device: the same bits."""
+        code_off, const_off = [0], [0]
+        for code, consts in programs:
+            code_off.append(code_off[-1] + len(code)); const_off.append(const_off[-1] + len(consts))
+        code = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in programs]), np.int32)
+        consts = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float64).reshape(-1) for _, k in programs] + [np.zeros(1)]))
+        code_off, const_off = np.asarray(code_off, np.int32), np.asarray(const_off, np.int32)
+        M, (B, T, F) = len(programs), X.shape
+        G = 1 if group_off is None else len(group_off) - 1
+        goff = None if group_off is None else np.ascontiguousarray(group_off, np.int32)
+        lens = None if lengths is None else np.ascontiguousarray(lengths, np.int64)
+        if params is None:
+            params = _lib.DiscoverParams.make()
+        S, E = int(params.max_terms), (M + 1) * (M + 2) // 2
+        head = (self._h, _ptr(code), _ptr(code_off), _ptr(consts), _ptr(const_off), M)
+        if not device:
+            picks, coef, loss = np.empty((G, S), np.int32), np.empty((G, S, S)), np.empty((G, S + 1))
+            info = np.empty((G, 3), np.int64)
+            gram = np.empty((G, E)) if return_gram else None
+            self._check(self.lib.rovmpc_discover_rows(*head, _ptr(X), F, _ptr(lens), T, B, _ptr(target), _ptr(goff), G, C.byref(params),
+                                                      _ptr(picks), _ptr(coef), _ptr(loss), _ptr(info), _ptr(gram)))
+            return picks, coef, loss, info, gram
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        dX, dT = torch.tensor(X, device=dev), torch.tensor(target, device=dev)
+        dK = torch.empty((G, S), dtype=torch.int32, device=dev)
+        dC = torch.empty((G, S, S), dtype=torch.float64, device=dev)
+        dL = torch.empty((G, S + 1), dtype=torch.float64, device=dev)
+        dI = torch.empty((G, 3), dtype=torch.int64, device=dev)
+        dG = torch.empty((G, E), dtype=torch.float64, device=dev) if return_gram else None
+        torch.cuda.synchronize(dev)
+        self._check(self.lib.rovmpc_discover_rows_device(*head, dX.data_ptr(), F, _ptr(lens), T, B, dT.data_ptr(), _ptr(goff), G,
+                                                         C.byref(params), dK.data_ptr(), dC.data_ptr(), dL.data_ptr(), dI.data_ptr(),
+                                                         None if dG is None else dG.data_ptr()))
+        torch.cuda.synchronize(dev)                     # (the device: the discovery runs on the handle's own stream)
+        return dK.cpu().numpy(), dC.cpu().numpy(), dL.cpu().numpy(), dI.cpu().numpy(), None if dG is None else dG.cpu().numpy()
+
     def score_pairs(self, theta_programs, gamma_programs, pairs, X, time, theta, gamma, mean, scale, params, lengths=None,
                     return_pred: bool = False, device: bool = False):
         """Q (theta row, gamma row) pairs rolled ``params.H`` steps on their own predictions from every start row of B

@@ -216,6 +216,19 @@ def default_free(code, n_consts: int, text: str = "") -> np.ndarray:
     return free
 
 
+def _group_offsets(groups, B: int):
+    """``groups`` of ``refit_rows`` / ``discover_rows`` as the library's group_off: None for "pooled", else int32 offsets."""
+    if isinstance(groups, str):
+        if groups not in ("pooled", "each"):
+            raise ValueError(f"groups must be 'pooled', 'each' or an offsets array (got {groups!r})")
+        return None if groups == "pooled" else np.arange(B + 1, dtype=np.int32)
+    group_off = np.asarray(groups)
+    if group_off.ndim != 1 or len(group_off) < 2 or not np.issubdtype(group_off.dtype, np.integer) or group_off[0] != 0 or \
+            group_off[-1] != B or (np.diff(group_off) <= 0).any():
+        raise ValueError(f"groups must be offsets that run from 0 to B = {B} increasing (got {groups!r})")
+    return np.ascontiguousarray(group_off, dtype=np.int32)
+
+
 def refit_rows(rows, X, target, lengths=None, groups="pooled", free=None, max_iter: int = 50, gtol: float = 1e-10,
                xtol: float = 1e-12, variable_names=None, engine=None, device: bool = False) -> RowRefit:
     """Refit the constants of every row of ``rows`` to the derivative series ``target`` on the recordings X (T, F) or
@@ -235,17 +248,7 @@ def refit_rows(rows, X, target, lengths=None, groups="pooled", free=None, max_it
     if target is None:
         raise ValueError("target is required: the derivative series the constants are fitted to")
     X, _, target, _, lengths, _, _ = _recordings(X, target, target, None, lengths, None, names=("target", "target"))
-    B = X.shape[0]
-    if isinstance(groups, str):
-        if groups not in ("pooled", "each"):
-            raise ValueError(f"groups must be 'pooled', 'each' or an offsets array (got {groups!r})")
-        group_off = None if groups == "pooled" else np.arange(B + 1, dtype=np.int32)
-    else:
-        group_off = np.asarray(groups)
-        if group_off.ndim != 1 or len(group_off) < 2 or not np.issubdtype(group_off.dtype, np.integer) or group_off[0] != 0 or \
-                group_off[-1] != B or (np.diff(group_off) <= 0).any():
-            raise ValueError(f"groups must be offsets that run from 0 to B = {B} increasing (got {groups!r})")
-        group_off = np.ascontiguousarray(group_off, dtype=np.int32)
+    group_off = _group_offsets(groups, X.shape[0])
     params = _lib.RefitParams.make(max_iter, gtol, xtol)
     if free is not None and len(free) != len(texts):
         raise ValueError(f"free must hold one mask per row ({len(texts)}; got {len(free)})")
@@ -273,6 +276,121 @@ def refit_rows(rows, X, target, lengths=None, groups="pooled", free=None, max_it
     expressions = [[rewrite_constants(text, c, variable_names) for c in per_row[r]] for r, text in enumerate(texts)]
     col = lambda k, t=np.float64: np.ascontiguousarray(out[..., k]).astype(t)
     return RowRefit(per_row, expressions, col(0), col(1), col(2), col(3, np.int64), col(4, np.int64), col(5, np.int64))
+
+
+class DiscoverStatus(enum.IntEnum):
+    """``rovmpc_discover_status``: how the forward selection of ``discover_rows`` ended."""
+    FULL = _lib.DISCOVER_FULL
+    MIN_GAIN = _lib.DISCOVER_MIN_GAIN
+    EXHAUSTED = _lib.DISCOVER_EXHAUSTED
+    NONFINITE = _lib.DISCOVER_NONFINITE
+
+
+def term_library(F: int, unary=("id", "sin", "cos"), intercept: bool = True, products=(), variable_names=None) -> list:
+    """Term texts for ``discover_rows`` over F features, in this order: the intercept ``1.0`` (if asked for); then for every
+    entry of ``unary`` in the order given, that function of every feature x0 .. x{F-1} in turn ("id" is the feature itself,
+    the others the one-argument functions of the expression grammar: sin, cos, tanh, exp, ...); then ``x_i*x_j`` for every
+    index pair of ``products`` in the order given.  F = 18 with the defaults: 1 + 3 * 18 = 55 texts.  ``variable_names``: the
+    names written instead of x0 ...  More than 64 terms is an error: the library takes no more."""
+    from .expr import _UNARY_CALLS
+    if isinstance(F, bool) or int(F) != F or not 1 <= int(F) <= _lib.MAX_FEATURES:
+        raise ValueError(f"F must be an integer in 1..{_lib.MAX_FEATURES} (got {F!r})")
+    F = int(F)
+    if variable_names is not None and len(variable_names) != F:
+        raise ValueError(f"variable_names must hold F = {F} names (got {len(variable_names)})")
+    name = (lambda i: variable_names[i]) if variable_names is not None else (lambda i: f"x{i}")
+    terms = ["1.0"] if intercept else []
+    for u in unary:
+        if u != "id" and u not in _UNARY_CALLS:
+            raise ValueError(f"unary must name 'id' or one of {sorted(_UNARY_CALLS)} (got {u!r})")
+        terms += [name(i) if u == "id" else f"{u}({name(i)})" for i in range(F)]
+    for pair in products:
+        i, j = pair
+        if not (0 <= int(i) < F and 0 <= int(j) < F):
+            raise ValueError(f"a product names a feature outside 0..{F - 1} (got {pair!r})")
+        terms.append(f"{name(int(i))}*{name(int(j))}")
+    if len(terms) > _lib.DISCOVER_MAX_TERMS:
+        raise ValueError(f"{len(terms)} terms: a library holds at most {_lib.DISCOVER_MAX_TERMS}")
+    return terms
+
+
+@dataclass
+class RowFront:
+    """What rovmpc_discover_rows returns for M terms on G groups with S = max_terms.  ``picks`` (G, S): the term of every
+    step, -1 beyond ``n_sel``; ``coef`` (G, S, S): row s the coefficients of the size-(s+1) row in pick order; ``loss``
+    (G, S + 1): loss[:, 0] is the mean square of the target, NaN beyond ``n_sel``; ``n_sel``, ``status``
+    (``DiscoverStatus``), ``n`` (the counted rows), each (G,); ``terms``: the library's texts; ``gram`` (G, (M+1)(M+2)/2) where
+    it was asked for.  ``expressions[g][s]``: the size-(s+1) row as text, ``a0*(t0) + a1*(t1) + ...`` with ``repr`` literals,
+    for s < n_sel[g]; ``complexities[g][s]``: its compiled instruction count."""
+    picks: np.ndarray
+    coef: np.ndarray
+    loss: np.ndarray
+    n_sel: np.ndarray
+    status: np.ndarray
+    n: np.ndarray
+    terms: Sequence[str]
+    gram: Optional[np.ndarray] = None
+    expressions: Sequence = ()
+    complexities: Sequence = ()
+
+    def rows(self, g: int = 0) -> list:
+        """The front of group g as row dicts (``complexity``, ``loss``, ``equation``, ``sympy_format``), smallest first:
+        what ``read_equation_csv`` returns for an equations_*.csv, and what ``score_rows``, ``refit_rows``, ``score_pairs``
+        and ``select_model`` accept as they are.  ``complexity`` is the compiled row's instruction count, NOT PySR's
+        complexity measure (which counts the nodes of its own expression tree)."""
+        return [{"complexity": int(self.complexities[g][s]), "loss": float(self.loss[g, s + 1]), "equation": text, "sympy_format": text}
+                for s, text in enumerate(self.expressions[g])]
+
+
+def _front_texts(picks, coef, n_sel, terms, F, variable_names):
+    """expressions[g][s] and their instruction counts; every text compiled once under the interpreter's limits."""
+    expressions, complexities = [], []
+    for g in range(len(picks)):
+        texts, counts = [], []
+        for s in range(int(n_sel[g])):
+            text = " + ".join(f"{float(coef[g, s, i])!r}*({terms[int(picks[g, i])]})" for i in range(s + 1))
+            try:
+                prog = compile_expression(text, [], F, variable_names)
+            except ValueError as e:
+                raise ValueError(f"the size-{s + 1} row of group {g} does not compile: {e}") from None
+            texts.append(text); counts.append(len(prog.code))
+        expressions.append(texts); complexities.append(counts)
+    return expressions, complexities
+
+
+def discover_rows(terms, X, target, lengths=None, groups="pooled", max_terms: int = 8, dep_tol: float = 1e-10,
+                  min_gain: float = 1e-12, variable_names=None, return_gram: bool = False, engine=None,
+                  device: bool = False) -> RowFront:
+    """Find equation rows on the recordings X (T, F) or (B, T, F) of already-scaled feature rows: for the sizes 1 ..
+    ``max_terms`` the subset of ``terms`` (expression texts, e.g. ``term_library(F)``) whose linear combination fits the
+    derivative series ``target`` best, by forward orthogonal least squares on the Gram matrix (rovmpc_discover_rows; law in
+    include/rovmpc.h).  An intercept is the term ``"1.0"``; nothing is centred.  ``groups``: "pooled", "each" or an offsets
+    array 0 .. B, one front per group; ``lengths``: the rows of each recording that count.  The selection stops before a
+    term whose gain is at most ``min_gain`` times the target's sum of squares, and never takes a term whose part orthogonal
+    to the picked ones is below ``dep_tol`` of its own square sum.  ``RowFront.rows()`` goes to ``score_rows``,
+    ``refit_rows``, ``score_pairs`` and ``select_model`` as it is."""
+    if isinstance(terms, (str, dict)):
+        raise ValueError("terms must be a sequence of expression texts, not a single one")
+    texts = [row_text(t) for t in terms]
+    if not 1 <= len(texts) <= _lib.DISCOVER_MAX_TERMS:
+        raise ValueError(f"1 to {_lib.DISCOVER_MAX_TERMS} terms (got {len(texts)})")
+    if target is None:
+        raise ValueError("target is required: the derivative series the rows are fitted to")
+    X, _, target, _, lengths, _, _ = _recordings(X, target, target, None, lengths, None, names=("target", "target"))
+    group_off = _group_offsets(groups, X.shape[0])
+    params = _lib.DiscoverParams.make(max_terms, dep_tol, min_gain)
+    programs = []
+    for text in texts:
+        consts: list = []
+        prog = compile_expression(text, consts, X.shape[2], variable_names)
+        programs.append((prog.code, consts))
+    if engine is None:
+        from .engine import default_engine
+        engine = default_engine()
+    picks, coef, loss, info, gram = engine.discover_rows(programs, X, target, lengths, group_off, params, return_gram, device)
+    n_sel, status, n = (np.ascontiguousarray(info[:, k]) for k in range(3))
+    expressions, complexities = _front_texts(picks, coef, n_sel, texts, X.shape[2], variable_names)
+    return RowFront(picks, coef, loss, n_sel, status, n, tuple(texts), gram, expressions, complexities)
 
 
 PREV_MODES = {"interp": _lib.PREV_INTERP, "hold": _lib.PREV_HOLD}

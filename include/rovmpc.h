@@ -1081,7 +1081,8 @@ int rovmpc_score_rows_device(rovmpc_handle *h, const int32_t *code, const int32_
  * refuses; a null target, consts_out or out; G < 1 or R G > 2^24; group_off NULL with G != 1, or a group_off that does not run
  * from 0 to B strictly increasing; more than ROVMPC_REFIT_MAX_PARAMS free constants in a row, or a free constant in a POW
  * exponent (the row is named); a struct_size mismatch; max_iter outside 1 .. 1000; gtol or xtol negative or NaN.
- * Not provided: an integrated-trajectory objective, robust losses, bounds on the constants, structure search, fp32. */
+ * Not provided: an integrated-trajectory objective, robust losses, bounds on the constants, fp32.  Structure search is
+ * rovmpc_discover_rows, below. */
 #define ROVMPC_REFIT_MAX_PARAMS 8
 #define ROVMPC_REFIT_OUT 6
 #define ROVMPC_REFIT_MU0 1e-3
@@ -1111,6 +1112,86 @@ int rovmpc_refit_rows_device(rovmpc_handle *h, const int32_t *code, const int32_
                              const int32_t *const_off, const uint8_t *free, int32_t R, const double *d_X, int32_t F,
                              const int64_t *len, int64_t T, int64_t B, const double *d_target, const int32_t *group_off,
                              int32_t G, const rovmpc_refit_params *params, double *d_consts_out, double *d_out);
+
+/* ---- discover equation rows: sparse regression over a term library (structure search, SINDy style) ------------------------
+ * Scoring, refitting and pair scoring take their rows as given.  This entry finds rows on the caller's own recordings: given
+ * M candidate TERMS, each an expression in the bytecode, it returns for the sizes 1 .. S the subset chosen by forward
+ * orthogonal least squares and its coefficients -- a front of rows ordered by size, the shape of an equations_*.csv front.
+ * Term j is the program code[code_off[j] .. code_off[j+1]) with its own constants consts[const_off[j] .. const_off[j+1]); every
+ * term must pass the validation of rovmpc_eval_expression for F features.  An intercept is the term `1.0`; nothing is centred.
+ * X[B][T][F], len[B], target[B][T] (required), group_off and G mean what they mean in rovmpc_refit_rows.  A PROBLEM is one
+ * group; problems are independent.  params: max_terms = S, dep_tol, min_gain.
+ * Law (fp64 only).
+ *   Stage 1, the Gram matrix.  Columns v_0 .. v_{M-1}: the term values on a counted row, bit for bit the `pred` of
+ *          rovmpc_score_rows for that term as a row; column v_M: the target.  The counted rows of a recording are cut into
+ *          CHUNKS of ROVMPC_DISCOVER_CHUNK consecutive rows (the last chunk of a recording may be short).  A chunk's partial
+ *          is, for k <= j, P[j][k] = the chain acc = fma(v_j(i), v_k(i), acc) from acc = +0 over the chunk's rows i in increasing
+ *          order: one fused multiply-add per row, the diagonal included.  A partial is a function of the chunk's rows and the
+ *          terms alone.  The group's Gram G[j][k] is the sum of the chunk partials from +0, left to right: recording after
+ *          recording in the group's order, chunk after chunk, plain additions.  G is symmetric by definition (G[k][j] = G[j][k]).
+ *   Stage 2, forward orthogonal least squares on G.  Plain IEEE operations (correctly rounded + - * / sqrt) in the order
+ *          written, no fused multiply-add; "sum" is always s = +0, s = s + term in increasing index, every product rounded first.
+ *          b_j = G[M][j], c = G[M][M], n = the counted rows of the group.  loss[0] = c / n.  c not finite: status NONFINITE, n_sel
+ *          = 0.  Term j is ADMISSIBLE if 0 < G[j][j] < inf and b_j is finite (this drops an all-zero term, and a term with a
+ *          non-finite value on a counted row: only its own row and column of G carry that value).
+ *          rho_j = G[j][j], q_j = b_j, F_0 = c.  At step s = 0 .. S - 1:
+ *            1. candidates: the admissible, unpicked j with rho_j > dep_tol * G[j][j] whose gain_j = (q_j * q_j) / rho_j is a
+ *               number (a NaN gain is never chosen);
+ *            2. no candidate: stop, EXHAUSTED.  p = the candidate of the largest gain, the lowest j on ties;
+ *            3. gain_p <= min_gain * c: stop, MIN_GAIN (so c = 0 stops at size 0);
+ *            4. l = sqrt(rho_p), z_s = q_p / l;
+ *            5. for every admissible unpicked j other than p: w_j[s] = (G[p][j] - sum_{t<s} w_p[t] * w_j[t]) / l; w_p[s] = l;
+ *            6. for those j: rho_j = rho_j - w_j[s] * w_j[s], q_j = q_j - w_j[s] * z_s; p is picked;
+ *            7. F_{s+1} = F_s - z_s * z_s; loss[s+1] = (F_{s+1} > 0 ? F_{s+1} : 0) / n;
+ *            8. the coefficients a_0 .. a_s of size s + 1, in pick order, by back substitution of L^T a = z with L[i][t] =
+ *               w_{p_i}[t]: for i = s down to 0, a_i = (z_i - sum_{m = i+1 .. s} L[m][i] * a_m) / L[i][i].
+ *          All S steps taken: FULL.
+ *   Outputs per group g: picks[g][S] (the term of step s; -1 at and beyond n_sel), coef[g][S][S] (row s: the s + 1
+ *          coefficients of the size-(s+1) row in pick order, then zeros; rows at and beyond n_sel are zero), loss[g][S+1]
+ *          (NaN beyond n_sel), info[g][3] = n_sel, status (a rovmpc_discover_status), n.  Optional gram[g][(M+1)(M+2)/2]: the
+ *          lower triangle of G packed row after row, entry j (j + 1) / 2 + k for k <= j.
+ *   loss comes by subtraction: below about u c / n (u = 2^-53) it is rounding.  The exact loss of a discovered row is column 4
+ *          of rovmpc_score_rows for that row.
+ *   determinism  the bits of a group's outputs are a function of the terms, the group's recordings in order and the params
+ *          alone: not of G, B, T, the group's place in the call, or the entry.
+ *   Two launches: one workgroup per chunk writes its partial (terms evaluated by the interpreter with the operand stack in LDS,
+ *   the tile's columns staged in LDS, the packed triangle accumulated in registers over the lanes); one wave per group adds the
+ *   partials and selects (lane j = term j).  No atomics, nothing between workgroups.  The partials live in a buffer of the
+ *   handle that grows as needed and goes with rovmpc_destroy.
+ * ROVMPC_ERR_INVALID with a message, before anything is launched and with nothing written: a null handle or required pointer
+ * (code, code_off, consts when a term has constants, const_off, X, target, picks, coef, loss, info); M outside 1 ..
+ * ROVMPC_DISCOVER_MAX_TERMS; B < 1, T < 1; F outside 1 .. ROVMPC_MAX_FEATURES; offsets that do not start at 0 or decrease; a
+ * term that fails validation (its index is in the message); len[b] outside 1 .. T; G < 1; group_off NULL with G != 1, or a
+ * group_off that does not run from 0 to B strictly increasing; more than 2^24 chunks in one call; a struct_size mismatch;
+ * max_terms outside 1 .. ROVMPC_DISCOVER_MAX_SIZE; dep_tol or min_gain negative or NaN.
+ * Not provided: libraries beyond 64 terms, backward elimination or swaps, ridge or lasso selection, information criteria (the
+ * front goes to rovmpc_score_rows and rovmpc_score_pairs for that), fp32, evolutionary search. */
+#define ROVMPC_DISCOVER_MAX_TERMS 64
+#define ROVMPC_DISCOVER_MAX_SIZE 8
+#define ROVMPC_DISCOVER_CHUNK 1024
+typedef enum rovmpc_discover_status {
+    ROVMPC_DISCOVER_FULL = 0, ROVMPC_DISCOVER_MIN_GAIN = 1, ROVMPC_DISCOVER_EXHAUSTED = 2, ROVMPC_DISCOVER_NONFINITE = 3
+} rovmpc_discover_status;
+typedef struct rovmpc_discover_params {
+    int32_t struct_size;             /* = sizeof(rovmpc_discover_params), ABI check                      */
+    int32_t max_terms;               /* S, 1 .. ROVMPC_DISCOVER_MAX_SIZE; default 8                      */
+    double dep_tol;                  /* dependence test, >= 0; default 1e-10                             */
+    double min_gain;                 /* relative stop rule, >= 0; default 1e-12                          */
+} rovmpc_discover_params;
+void rovmpc_default_discover_params(rovmpc_discover_params *p);
+/* Host pointers; params NULL: the defaults; gram may be NULL.  Uploads, two launches, one synchronise. */
+int rovmpc_discover_rows(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                         const int32_t *const_off, int32_t M, const double *X, int32_t F, const int64_t *len, int64_t T,
+                         int64_t B, const double *target, const int32_t *group_off, int32_t G,
+                         const rovmpc_discover_params *params, int32_t *picks, double *coef, double *loss, int64_t *info,
+                         double *gram);
+/* X, target and the five results in device memory, enqueued on the handle's stream without a synchronise.  The programs, len
+ * and group_off stay HOST arrays, checked here and staged as rovmpc_score_rows_device stages them. */
+int rovmpc_discover_rows_device(rovmpc_handle *h, const int32_t *code, const int32_t *code_off, const double *consts,
+                                const int32_t *const_off, int32_t M, const double *d_X, int32_t F, const int64_t *len,
+                                int64_t T, int64_t B, const double *d_target, const int32_t *group_off, int32_t G,
+                                const rovmpc_discover_params *params, int32_t *d_picks, double *d_coef, double *d_loss,
+                                int64_t *d_info, double *d_gram);
 
 /* ---- score (theta, gamma) row pairs by closed-loop N-step-ahead skill on recordings ----------------------------------------
  * rovmpc_score_rows is open loop: a row is integrated along measured feature rows, never reads its own prediction, and the
